@@ -24,6 +24,14 @@ the adapter's default write-through form, one learner per GPU at every N.
     pick the transport of the timed run by the median rate.  Per-GPU work is fixed ->
     "scaling": "weak".  Every rank logs its phases to stderr (``[bench rN +s]``).
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) sets up the learners (at N>1: binds them
+and picks the transport by the trials), warms up, times the K steps, writes its outputs if
+``--dump-outputs DIR`` is given and prints the result line: ``value``, ``ms_per_step`` and the
+round rates.  Everything else described here -- ``cpu_baseline``, ``parity``, ``roofline``'s kernel
+timings, ``value_cold``, ``co_resident_pair``, the adapter loop, the other publish form, the
+overlap leg behind ``scaling_basis.weak``, the sweeps over the north_star sizes -- runs only with
+``--full``.
+
 ``value`` = algorithmic averaged bytes (3 * numel * sizeof(dtype) per completed averaging,
 SURVEY.md §8d) summed over all learners / the max-over-ranks wall time of the K timed steps,
 from a pass with no instrumentation.  ``roofline`` prices the averaging kernel alone, cold, per
@@ -97,6 +105,19 @@ def parse(argv=None):
     ap.add_argument("--warmup-s", type=float, default=0.25,
                     help="after the W warmup steps, more untimed rounds until about this many seconds of rounds "
                          "have run (the same count on every rank), so the timed steps see steady-state clocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: the CPU baselines, the parity leg, the "
+                         "in-loop and cold kernel timings (roofline), the other publish form, the overlap leg, "
+                         "value_cold, the adapter loop, the co-resident pair and the sweeps over the north_star "
+                         "sizes.  Without it a run sets up, warms up, times the --steps rounds and prints the line; "
+                         "the options below that shape or skip those legs only matter with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed round left its caller to DIR as .npy: "
+                         "parameters.npy (the averaged parameters as float32; a fixed seeded sample above "
+                         "DUMP_MAX_ELEMS elements), factor.npy and clock.npy (float64); at N>1 one set per rank "
+                         "(*_rank<r>.npy).  The untimed rounds after the --warmup steps are then a count fixed by "
+                         "the arguments (dump_warmup_rounds) instead of a timed one, so the same arguments give "
+                         "the same inputs to every timed step in every run")
     ap.add_argument("--numel", type=int, default=RESNET18_NUMEL)
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--interpolation", choices=["constant", "clock", "loss"], default="constant")
@@ -159,8 +180,15 @@ def parse(argv=None):
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
                     help="self-launch (N>1 without torchrun): seconds before the child job is stopped")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_write_through:
         args.publish, args.no_secondary = "full", True
+    if not args.full:
+        # a plain run measures the headline figure only: every other leg is off
+        args.no_cpu_baseline = args.no_parity = args.no_cold = args.no_sweep = True
+        args.no_secondary = args.no_value_cold = args.no_provisional = True
+        args.compute_us = 0.0
     return args
 
 
@@ -1634,6 +1662,40 @@ def size_sweep(device, rows=None):
     return rows
 
 
+DUMP_MAX_ELEMS = 15_000_000    # float32 parameters written by --dump-outputs, all ranks together (60 MB)
+
+
+def dump_warmup_rounds(numel, esize, warmup, warmup_s):
+    """--dump-outputs: how many untimed rounds follow the W warmup steps.  Without the option
+    that count comes from the warmup steps' time (about `warmup_s` seconds of rounds in all) and
+    differs from run to run; with it, it comes from the arguments alone -- `warmup_s` over the time
+    a round of this size takes at 5 TB/s of its 4*N*s bytes (at least 20 us), less the W steps, at
+    most 200,000 -- so the timed steps start from the same state in every run of every build."""
+    per = max(20e-6, 4 * numel * esize / 5e12)
+    return int(min(200_000, max(0, np.ceil(warmup_s / per) - warmup)))
+
+
+def dump_outputs(dirpath, rank, world, learners):
+    """--dump-outputs: what the last timed round left its caller, per learner (conn, parameters) of
+    this rank -- the averaged parameters (float32; above DUMP_MAX_ELEMS / world elements a sorted
+    sample drawn with a fixed seed), the factor of that round's average and the learner's clock
+    (float64, one element each).  Files: <what>.npy at N=1, <what>_rank<r>.npy at N>1."""
+    os.makedirs(dirpath, exist_ok=True)
+    if any(p.is_cuda for _, p in learners):
+        torch.cuda.synchronize()
+    cap = max(1, DUMP_MAX_ELEMS // (world * max(1, len(learners))))
+    for i, (conn, params) in enumerate(learners):
+        tag = ("_rank%d" % rank if world > 1 else "") + ("_learner%d" % i if len(learners) > 1 else "")
+        if params.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, params.numel(), cap))
+            params = params[torch.from_numpy(idx).to(params.device)]
+        np.save(os.path.join(dirpath, "parameters%s.npy" % tag), params.float().cpu().numpy())
+        factor = conn._learner.read_coef().factor if conn._learner is not None else float("nan")
+        np.save(os.path.join(dirpath, "factor%s.npy" % tag), np.array([factor], dtype=np.float64))
+        np.save(os.path.join(dirpath, "clock%s.npy" % tag), np.array([conn.clock], dtype=np.float64))
+    progress("outputs written to %s" % dirpath)
+
+
 SCALING_DEFINITION = ("one learner per GPU at every N (N=1: its peer is its own snapshot, configs[1]; N>1: one "
                       "rank per GPU, peers over xGMI), the same publish form at every N.  raw = aggregate "
                       "gossip rounds/s of the bandwidth loop (update_send -> update_wait, no training step): "
@@ -1808,13 +1870,13 @@ def main(argv=None):
             return 1.0
         return 2.0 * float(np.exp(-loss_t[0] / 200.0)) + 0.05 * float(loss_rngs[i].random())
 
-    def run(steps, warmup, write_through, sample_every=0, warmup_s=0.0):
+    def run(steps, warmup, write_through, sample_every=0, warmup_s=0.0, extra_rounds=None):
         """`steps` timed lock-step rounds.  sample_every == 0: nothing but the rounds (the
         pass `value` comes from).  sample_every = k > 0: the averaging dispatch of every k-th
         step is timed by its own dispatch events (and/or bracketed by an event pair on its
         stream) -- the in-loop kernel figure, from a separate pass.  warmup_s: after the
         `warmup` rounds, more untimed rounds up to about that many seconds in all (a count agreed
-        by every rank from the warmup rounds' time)."""
+        by every rank from the warmup rounds' time; `extra_rounds` fixes that count instead)."""
         lerp_events = []
         sampled = []        # batched: per timed dispatch (learner whose pair timed it, averages in it)
         n_slots = (steps // sample_every + 1) * len(learners) if sample_every else 0
@@ -1889,6 +1951,8 @@ def main(argv=None):
             torch.cuda.synchronize()
             per = (time.perf_counter() - t_w) / max(1, warmup)
             extra = int(min(200_000, max(0, np.ceil(warmup_s / max(per, 1e-6)) - warmup)))
+            if extra_rounds is not None:    # a count fixed by the arguments (--dump-outputs)
+                extra = extra_rounds
             if world > 1:
                 got = [None] * world
                 dist.all_gather_object(got, extra, group=ctl)
@@ -2112,14 +2176,23 @@ def main(argv=None):
     wt_main = pull.endswith("+wt") if sel_async else wt_lockstep
     form = "resident" if resident_main else "write-through" if wt_main else "full"
     wd.enter("timed run: %s, %s publish" % (pull, form), 600.0 + 0.05 * (args.steps + args.warmup))
-    elapsed, averaged, rounds, _ = run(args.steps, args.warmup, wt_main, warmup_s=args.warmup_s)
+    # --dump-outputs: the rounds after the W warmup steps are a fixed count, not a timed one, so the
+    # dumped state is that of the same number of rounds in every run
+    fixed = dump_warmup_rounds(args.numel, esize, args.warmup, args.warmup_s) if args.dump_outputs else None
+    elapsed, averaged, rounds, _ = run(args.steps, args.warmup, wt_main, warmup_s=args.warmup_s, extra_rounds=fixed)
     progress("timed run: %.4f ms/step" % (1e3 * elapsed / args.steps))
-    # the averaging kernel inside the loop: a separate sampled pass of the same rounds
-    wd.enter("in-loop kernel timing", 600.0)
+    if args.dump_outputs:
+        wd.enter("dump outputs", 300.0)
+        dump_outputs(args.dump_outputs, rank, world, [(c, params_of(c, f)) for c, f in learners])
     s_steps = max(args.steps, 8 * args.sample_every)
-    s_el, _, _, (lerp_ms, bracket_ms, lerp_navg) = run(s_steps, 2, wt_main, args.sample_every)
+    nan1 = np.array([np.nan])
+    s_el, lerp_ms, bracket_ms, lerp_navg = float("nan"), nan1, nan1, nan1
+    if args.full:
+        # the averaging kernel inside the loop: a separate sampled pass of the same rounds
+        wd.enter("in-loop kernel timing", 600.0)
+        s_el, _, _, (lerp_ms, bracket_ms, lerp_navg) = run(s_steps, 2, wt_main, args.sample_every)
     pull_us = []
-    if world > 1 and not sel_mode.startswith("relay"):
+    if args.full and world > 1 and not sel_mode.startswith("relay"):
         # the pull alone (side-stream events around each copying fetch), in a short extra run
         wd.enter("pull timing", 300.0)
         p_steps = max(20, args.steps // 4)
@@ -2284,7 +2357,7 @@ def main(argv=None):
     out = None
     if rank == 0:
         value = averaged * unit_bytes / elapsed / 1e9
-        lerp_us = float(np.nanmean(lerp_ms) * 1e3)
+        lerp_us = float(np.nanmean(lerp_ms) * 1e3) if np.isfinite(lerp_ms).any() else float("nan")
         k1 = kbytes / per_launch
         live_gbs = float(np.nansum(lerp_navg * k1) / np.nansum(lerp_ms * 1e-3) / 1e9) if np.isfinite(lerp_us) \
             else float("nan")
@@ -2395,6 +2468,13 @@ def main(argv=None):
                               "note": "untimed rounds before the timed steps: W, then more up to about warmup_s "
                                       "seconds in all, so the timed steps run at steady-state clocks"},
         })
+        if not args.full:
+            # a plain run times no kernel on its own: the roofline block names it and its bytes
+            out["roofline"] = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                               "traffic": traffic, "bytes_per_launch": kbytes, "avg_launch_us": None,
+                               "metric_bytes_per_averaging": unit_bytes, "learners_per_launch": per_launch,
+                               "kernel": kname + " (timed alone only with --full)"}
+            out["config"]["frac_moved_bytes_cold"] = None
         if mix is not None:
             out["roofline"]["mix_ceiling_frac"] = mix["frac"]
             out["roofline"]["kernel_over_mix_ceiling"] = round(achieved / mix["achieved"], 4)
@@ -2403,7 +2483,7 @@ def main(argv=None):
                 "shape and cache policy, no factor or lerp), each launch interleaved with a product launch in the "
                 "same cold rotation: what one launch of this size reaches on this chip (kernel_over_mix_ceiling "
                 "= the product kernel's rate over it)"))
-        if wt_kernel and args.numel == RESNET18_NUMEL and args.dtype == "f32":
+        if args.full and wt_kernel and args.numel == RESNET18_NUMEL and args.dtype == "f32":
             out["roofline"]["vs_mix_ceiling"] = dict(MIX_CEILING_11M, kernel_frac_over_ceiling=round(
                 achieved / HBM_PEAK_GBS / MIX_CEILING_11M["frac"], 4),
                 note="round 2's stream_tune ceiling for one 11.17M-element 2R:2W launch (mix_ceiling: this run's)")

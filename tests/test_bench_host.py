@@ -3,7 +3,9 @@ trial (at N>1 the parity leg runs before the trials and only verified transports
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import pytest
+
+ROOT =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_every_trial_maps_to_a_parity_transport():
@@ -88,6 +90,61 @@ def test_partial_line_keeps_the_contract_keys():
               "vs_baseline", "dtype", "data"):
         assert k in out
     assert out["n_gpus"] == 8 and out["steps"] == 20 and out["value"] is None
+
+
+def test_plain_run_turns_every_side_leg_off_and_full_keeps_them():
+    """Without --full only the headline is measured: every leg beside it is off whatever else the
+    command line says; with --full the legs are on as their own options leave them."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    legs = ("no_cpu_baseline", "no_parity", "no_cold", "no_sweep", "no_secondary", "no_value_cold", "no_provisional")
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3", "--compute-us", "300"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    assert all(getattr(a, k) for k in legs) and a.compute_us == 0
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3", "--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and not any(getattr(a, k) for k in legs) and a.compute_us == 1000.0
+    a = bench.parse(["--full", "--no-sweep", "--compute-us", "0"])
+    assert a.no_sweep and not a.no_parity and a.compute_us == 0
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    # a dump run's untimed rounds after the W steps: a function of the arguments alone
+    import numpy as np
+    n = bench.RESNET18_NUMEL
+    assert bench.dump_warmup_rounds(n, 4, 5, 0.25) == int(np.ceil(0.25 / (16 * n / 5e12))) - 5 == 6987
+    assert bench.dump_warmup_rounds(1000, 4, 5, 0.25) == 12495          # no round is taken to be under 20 us
+    assert bench.dump_warmup_rounds(n, 4, 9000, 0.25) == 0 and bench.dump_warmup_rounds(n, 4, 5, 0.0) == 0
+    assert bench.dump_warmup_rounds(10, 4, 0, 100.0) == 200_000
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_vectors(tmp_path, monkeypatch):
+    """--dump-outputs: float32 parameters, float64 factor and clock; a vector above the cap is
+    written as the same seeded, sorted sample every time, and the ranks of an N>1 run share the cap."""
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+
+    class Conn:
+        _learner = None
+        clock = 25.0
+
+    p = torch.arange(1000, dtype=torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "a"), 0, 1, [(Conn(), p)])
+    got = np.load(tmp_path / "a" / "parameters.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, p.float().numpy())
+    clock = np.load(tmp_path / "a" / "clock.npy")
+    assert clock.dtype == np.float64 and clock.tolist() == [25.0]
+    assert np.load(tmp_path / "a" / "factor.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 200)
+    p = torch.arange(1000, dtype=torch.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), 1, 2, [(Conn(), p)])
+    b, c = (np.load(tmp_path / d / "parameters_rank1.npy") for d in ("b", "c"))
+    assert b.shape == (100,) and np.array_equal(b, c) and np.all(np.diff(b) >= 0) and len(np.unique(b)) > 50
+    monkeypatch.undo()       # the real cap: 64 MB in all, the two scalar files and the headers included
+    assert bench.DUMP_MAX_ELEMS * 4 + 16 * 1024 <= 64_000_000
 
 
 def _watchdog_child(held, rc, detail=None):

@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
-ARGS = ["--gpus", "2", "--dist-backend", "gloo", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-sweep",
-        "--compute-us", "0", "--no-secondary", "--trial-passes", "1", "--trial-ms", "5"]
+ARGS = ["--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+        "--no-sweep", "--compute-us", "0", "--no-secondary", "--trial-passes", "1", "--trial-ms", "5"]
 
 
 LINE_MAX = 6144     # the driver keeps ~9 KB of stdout: the line stays well inside it
@@ -101,7 +101,7 @@ def test_two_ranks_report_scaling_basis_and_a_shared_device_xgmi_line(tmp_path):
     assert x["peak_gbs"] == 76.8 and x["ranks_share_device"] is True and x["frac"] is None
     assert det["scaling_basis"]["definition"] and det["value"] == out["value"]
     # the N=1 line's scaling block has the same schema
-    rc, lines, err = _bench(tmp_path, args=["--numel", "1000003", "--steps", "5", "--warmup", "2",
+    rc, lines, err = _bench(tmp_path, args=["--full", "--numel", "1000003", "--steps", "5", "--warmup", "2",
                                             "--no-cpu-baseline", "--no-sweep", "--compute-us", "300",
                                             "--no-secondary", "--no-value-cold"])
     assert rc == 0, err[-3000:]
@@ -188,8 +188,8 @@ def test_resident_parity_failure_falls_back_to_write_through(tmp_path):
 
 
 def _one_gpu(tmp_path, n, *extra):
-    rc, lines, err = _bench(tmp_path, args=["--numel", str(n), "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
-                                            "--no-sweep", "--compute-us", "0"] + list(extra))
+    rc, lines, err = _bench(tmp_path, args=["--full", "--numel", str(n), "--steps", "20", "--warmup", "5",
+                                            "--no-cpu-baseline", "--no-sweep", "--compute-us", "0"] + list(extra))
     assert rc == 0, err[-3000:]
     out = _line(lines)
     return out, _detail(out)
@@ -231,19 +231,56 @@ def test_one_gpu_line_is_configs1_self_peer_within_the_roofline(tmp_path):
     assert ad["resident"]["ms_per_step"] <= 1.35 * ad["resident_no_guard"]["ms_per_step"], ad
 
 
+def test_plain_run_times_the_steps_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: one line with the headline (`value` = 3*N*s per averaging over K *
+    `ms_per_step`), no parity / CPU / kernel-timing legs; --dump-outputs writes the last timed
+    round's parameters (float32), factor and clock (float64).  The learner averages with its own
+    snapshot at constant 0.5, so the parameters are the seeded N(0,1) vector itself, bit for bit,
+    and the clock counts the W warmup steps, the fixed count of further untimed rounds that a dump
+    run uses in place of the timed one, and the K steps."""
+    import numpy as np
+    import torch
+    n, K, W = 1_000_003, 7, 3
+    d = tmp_path / "out"
+    rc, lines, err = _bench(tmp_path, args=["--gpus", "1", "--numel", str(n), "--steps", str(K), "--warmup", str(W),
+                                            "--dump-outputs", str(d)])
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1 and len(lines[0].encode()) <= LINE_MAX, lines
+    out = json.loads(lines[0])
+    assert out["steps"] == K and out["warmup"] == W and out["averagings"] == K and out["ms_per_step"] > 0
+    assert abs(out["value"] / (3 * n * 4 / (out["ms_per_step"] * 1e-3) / 1e9) - 1) < 0.02     # both are rounded
+    assert out["unit"] == "GB/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert "parity" not in out and "error" not in out and out["n_gpus"] == 1
+    assert out["cpu_baseline"] is None and out["value_cold"] is None and out["roofline"]["achieved"] is None
+    for leg in ("parity", "in-loop kernel timing", "cold kernel", "size sweep", "round sweep", "cpu baseline",
+                "overlap", "value_cold", "adapter loop"):
+        assert "s] %s" % leg not in err, leg
+    p = np.load(d / "parameters.npy")
+    g = torch.Generator(device="cuda:0").manual_seed(0)
+    want = torch.randn(n, device="cuda:0", generator=g, dtype=torch.float32).cpu().numpy()
+    assert p.dtype == np.float32 and p.tobytes() == want.tobytes()
+    sys.path.insert(0, ROOT)
+    import bench
+    fixed = bench.dump_warmup_rounds(n, 4, W, 0.25)
+    assert fixed == 12500 - W and np.load(d / "clock.npy").tolist() == [float(W + fixed + K)]
+    f = np.load(d / "factor.npy")
+    assert f.dtype == np.float64 and f.tolist() == [0.5]
+    assert sorted(x.name for x in d.iterdir()) == ["clock.npy", "factor.npy", "parameters.npy"]
+
+
 @pytest.mark.timeout(900)
 def test_driver_command_prints_one_bounded_line(tmp_path):
-    """The driver's exact N=1 command (`bench.py --gpus 1 --steps 20 --warmup 5`: CPU baseline,
-    restatement rows, value_cold, side loops and both sweeps all on) prints one line of at most
+    """The N=1 command with every leg on (`bench.py --gpus 1 --steps 20 --warmup 5 --full`: CPU
+    baseline, restatement rows, value_cold, side loops and both sweeps all on) prints one line of at most
     LINE_MAX bytes that json.loads, with the headline scalars; the sweeps and rows are in the
     detail file the line names.  (Round 5's 21.7 KB line was cut by the driver and left unparsed.)
     Progress goes to gpurun_out/ so a long run is visibly alive."""
     log_dir = os.path.join(ROOT, "gpurun_out")
     os.makedirs(log_dir, exist_ok=True)
     with open(os.path.join(log_dir, "driver_command.err"), "w") as err:
-        p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=ROOT,
-                           env=_env(tmp_path / "detail.json"), stdout=subprocess.PIPE, stderr=err, text=True,
-                           timeout=880)
+        p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
+                           cwd=ROOT, env=_env(tmp_path / "detail.json"), stdout=subprocess.PIPE, stderr=err,
+                           text=True, timeout=880)
     assert p.returncode == 0
     out = _line([ln for ln in p.stdout.splitlines() if ln.strip()])
     for k in ROOFLINE_KEYS + ("in_loop_frac", "mix_ceiling_frac", "traffic_x"):

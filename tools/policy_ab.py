@@ -13,7 +13,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE = ["--no-cpu-baseline", "--no-sweep", "--compute-us", "0", "--no-secondary", "--no-parity"]
+BASE = ["--full", "--no-cpu-baseline", "--no-sweep", "--compute-us", "0", "--no-secondary", "--no-parity"]
 
 
 def main():
