@@ -18,9 +18,9 @@ LIB_PATH = os.environ.get("DPWA_HIP_LIB", os.path.join(_HERE, "libdpwa_hip.so"))
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dpwa_hip.h")
 
 # Constants mirrored from include/dpwa_hip.h
-ABI_VERSION = 10
+ABI_VERSION = 11
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
-F32, BF16, F64 = 0, 1, 2
+F32, BF16, F64, F16 = 0, 1, 2, 3
 INTERP_CONSTANT, INTERP_CLOCK, INTERP_LOSS = 0, 1, 2
 STATUS_OK, STATUS_ZERO_DIVISION = 0, 1
 IPC_HANDLE_BYTES = 128
@@ -91,8 +91,10 @@ SIGNATURES = {
     "dpwa_last_words_written": [ctypes.POINTER(ctypes.c_int)],
     "dpwa_lerp_f32": [_vp, _vp, _i64, _vp, _vp],
     "dpwa_lerp_bf16": [_vp, _vp, _i64, _vp, _vp],
+    "dpwa_lerp_f16": [_vp, _vp, _i64, _vp, _vp],
     "dpwa_lerp_f32_host": [_vp, _vp, _i64, _dbl, _vp],
     "dpwa_lerp_bf16_host": [_vp, _vp, _i64, _dbl, _vp],
+    "dpwa_lerp_f16_host": [_vp, _vp, _i64, _dbl, _vp],
     "dpwa_factor": [ctypes.POINTER(Interp), _vp, _vp, _dbl, _vp, _vp, _vp],
     "dpwa_average": [_i32, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp],
     "dpwa_average_many": [_i32, _vp, _int, ctypes.POINTER(Interp), _vp, _vp, _vp],

@@ -7,8 +7,10 @@ three temporaries each (pytorch.py:66-68), the parameters live in one flat HBM b
 in place with one fused HIP kernel whose coefficients come from the device factor.
 
 Differences that are intentional: the average is written in place (the reference
-rebinds ``param.data`` to a new tensor), and float32 *and* bfloat16 models are accepted
-(the reference maps only FloatTensor, pytorch.py:11-14).
+rebinds ``param.data`` to a new tensor), and float32, bfloat16 *and* float16 models are
+accepted (the reference maps only FloatTensor, pytorch.py:11-14); the 16-bit types round as
+torch-eager does on them.  Not accepted: a model that mixes dtypes (one flat buffer, one dtype),
+and 16-bit parameters over the wire bridge (dpwa_amd/bridge.py carries float32 only).
 """
 import ctypes
 import logging

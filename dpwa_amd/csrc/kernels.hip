@@ -50,6 +50,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 
 static inline int64_t blocks_for(int64_t items)
 {
@@ -84,6 +85,46 @@ __device__ __forceinline__ uint32_t lerp_bf16x2(float a, float b, uint32_t q, ui
     return pk_bf16(bf_lo(x) + bf_lo(y), bf_hi(x) + bf_hi(y));
 }
 
+// Two f32 -> packed f16, round-to-nearest-even (v_cvt_pk_f16_f32; never the pkrtz form, which
+// rounds toward zero).  fp16 subnormals are kept: the kernels run with the default
+// float_denorm_mode_16_64 = 3 and no flush-to-zero build flag.
+__device__ __forceinline__ uint32_t pk_f16(float lo, float hi)
+{
+    float2v v = {lo, hi};
+    f16x2v r = __builtin_convertvector(v, f16x2v);
+    return __builtin_bit_cast(uint32_t, r);
+}
+
+__device__ __forceinline__ float2v unpk_f16(uint32_t w)
+{
+    return __builtin_convertvector(__builtin_bit_cast(f16x2v, w), float2v);
+}
+
+// f16(f16(a*q) + f16(b*p)) for the two fp16 held in each 32-bit word (torch-eager form on
+// torch.float16: each product is an fp32 product rounded to fp16, then the fp16 sum).  The fp32
+// sum of two fp16 values is exact, so rounding it once to fp16 is the fp16 addition.
+__device__ __forceinline__ uint32_t lerp_f16x2(float a, float b, uint32_t q, uint32_t p)
+{
+    const float2v qf = unpk_f16(q), pf = unpk_f16(p);
+    const float2v x = unpk_f16(pk_f16(a * qf.x, a * qf.y));
+    const float2v y = unpk_f16(pk_f16(b * pf.x, b * pf.y));
+    return pk_f16(x.x + y.x, x.y + y.y);
+}
+
+// One element, for the ragged tail and the unaligned kernel.  Left alone, the compiler selects
+// f16(a * f32(q)) as v_fma_mixlo_f16 with a +0.0 addend, and (-0.0) + (+0.0) is +0.0 where torch
+// keeps the product's -0.0 (0.0 * q for a negative q, or q = -0.0); the empty asm keeps the fp32
+// product a value of its own, so it is rounded by v_cvt_f16_f32 as in the packed form.
+__device__ __forceinline__ uint16_t lerp_f16x1(float a, float b, uint16_t q, uint16_t p)
+{
+    float x = a * (float)__builtin_bit_cast(_Float16, q);
+    float y = b * (float)__builtin_bit_cast(_Float16, p);
+    asm("" : "+v"(x));
+    asm("" : "+v"(y));
+    const _Float16 xh = (_Float16)x, yh = (_Float16)y;
+    return __builtin_bit_cast(uint16_t, (_Float16)((float)xh + (float)yh));
+}
+
 struct OpsF32 {
     using V = f32x4;
     using S = float;
@@ -113,6 +154,25 @@ struct OpsBF16 {
     __device__ static __forceinline__ S lerp_s(float a, float b, S q, S p)
     {
         return (S)(lerp_bf16x2(a, b, (uint32_t)q, (uint32_t)p) & 0xffffu);
+    }
+};
+
+struct OpsF16 {
+    using V = u32x4;
+    using S = uint16_t;
+    static constexpr int PER = 8;
+    __device__ static __forceinline__ V lerp(float a, float b, V q, V p)
+    {
+        V r;
+        r.x = lerp_f16x2(a, b, q.x, p.x);
+        r.y = lerp_f16x2(a, b, q.y, p.y);
+        r.z = lerp_f16x2(a, b, q.z, p.z);
+        r.w = lerp_f16x2(a, b, q.w, p.w);
+        return r;
+    }
+    __device__ static __forceinline__ S lerp_s(float a, float b, S q, S p)
+    {
+        return lerp_f16x1(a, b, q, p);
     }
 };
 
@@ -682,6 +742,7 @@ static hipError_t launch_any(int32_t dtype, int mode, void *param, const void *p
     if (n == 0 && mode != COEF_FUSED) return hipSuccess;
     if (dtype == DPWA_F32) return launch_ops<OpsF32>(mode, param, peer, n, args, s, t);
     if (dtype == DPWA_BF16) return launch_ops<OpsBF16>(mode, param, peer, n, args, s, t);
+    if (dtype == DPWA_F16) return launch_ops<OpsF16>(mode, param, peer, n, args, s, t);
     return hipErrorInvalidValue;
 }
 
@@ -737,6 +798,7 @@ hipError_t launch_average(int32_t dtype, void *param, const void *peer, int64_t 
         if (n < 0 || (!snap && n > 0) || !aligned16(param) || !aligned16(peer) || !aligned16(snap)) return hipErrorInvalidValue;
         if (dtype == DPWA_F32) return launch_oop<OpsF32>(param, peer, n, args, s, timing);
         if (dtype == DPWA_BF16) return launch_oop<OpsBF16>(param, peer, n, args, s, timing);
+        if (dtype == DPWA_F16) return launch_oop<OpsF16>(param, peer, n, args, s, timing);
         return hipErrorInvalidValue;
     }
     return launch_any(dtype, COEF_FUSED, param, peer, n, args, s, timing);
@@ -802,7 +864,7 @@ hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hip
     if (b.count < 1 || b.count > kMaxAvgBatch || (oop && !dual)) return hipErrorInvalidValue;
     AvgBatch x = b;
     uint32_t g = 0;
-    const int per = dtype == DPWA_F32 ? OpsF32::PER : dtype == DPWA_BF16 ? OpsBF16::PER : 0;
+    const int per = dtype == DPWA_F32 ? OpsF32::PER : dtype == DPWA_BF16 ? OpsBF16::PER : dtype == DPWA_F16 ? OpsF16::PER : 0;
     if (!per) return hipErrorInvalidValue;
     for (int i = 0; i < x.count; ++i) {
         const AvgEntry &e = x.e[i];
@@ -883,9 +945,12 @@ hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hip
         if (dtype == DPWA_F32) {
             if (p0) DPWA_GROUP_G(OpsF32, 0);
             else DPWA_GROUP_G(OpsF32, kProductPolicy);
-        } else {
+        } else if (dtype == DPWA_BF16) {
             if (p0) DPWA_GROUP_G(OpsBF16, 0);
             else DPWA_GROUP_G(OpsBF16, kProductPolicy);
+        } else {
+            if (p0) DPWA_GROUP_G(OpsF16, 0);
+            else DPWA_GROUP_G(OpsF16, kProductPolicy);
         }
 #undef DPWA_GROUP_G
 #undef DPWA_GROUP_LAUNCH
@@ -912,9 +977,12 @@ hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hip
             case 32: DPWA_PAIR_LAUNCH(OpsF32, 32); break;
             default: DPWA_PAIR_LAUNCH(OpsF32, kProductPolicy); break;
             }
-        } else {
+        } else if (dtype == DPWA_BF16) {
             if (lerp_policy() == 0) DPWA_PAIR_LAUNCH(OpsBF16, 0);
             else DPWA_PAIR_LAUNCH(OpsBF16, kProductPolicy);
+        } else {
+            if (lerp_policy() == 0) DPWA_PAIR_LAUNCH(OpsF16, 0);
+            else DPWA_PAIR_LAUNCH(OpsF16, kProductPolicy);
         }
 #undef DPWA_PAIR_LAUNCH
         return hipGetLastError();
@@ -963,10 +1031,14 @@ hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hip
         if (oop) DPWA_BATCH_LAUNCH_OOP(OpsF32);
         else if (dual) DPWA_BATCH_LAUNCH(OpsF32, true);
         else DPWA_BATCH_LAUNCH(OpsF32, false);
-    } else {
+    } else if (dtype == DPWA_BF16) {
         if (oop) DPWA_BATCH_LAUNCH_OOP(OpsBF16);
         else if (dual) DPWA_BATCH_LAUNCH(OpsBF16, true);
         else DPWA_BATCH_LAUNCH(OpsBF16, false);
+    } else {
+        if (oop) DPWA_BATCH_LAUNCH_OOP(OpsF16);
+        else if (dual) DPWA_BATCH_LAUNCH(OpsF16, true);
+        else DPWA_BATCH_LAUNCH(OpsF16, false);
     }
 #undef DPWA_BATCH_LAUNCH_OOP
 #undef DPWA_BATCH_LAUNCH
@@ -1027,6 +1099,10 @@ hipError_t launch_average_relay(int32_t dtype, void *param, int64_t n, const Fus
         if (oop) launch_relay_kernel<OpsBF16, true, true>(param, n, args, src, s, timing);
         else if (snap) launch_relay_kernel<OpsBF16, true>(param, n, args, src, s, timing);
         else launch_relay_kernel<OpsBF16, false>(param, n, args, src, s, timing);
+    } else if (dtype == DPWA_F16) {
+        if (oop) launch_relay_kernel<OpsF16, true, true>(param, n, args, src, s, timing);
+        else if (snap) launch_relay_kernel<OpsF16, true>(param, n, args, src, s, timing);
+        else launch_relay_kernel<OpsF16, false>(param, n, args, src, s, timing);
     } else {
         return hipErrorInvalidValue;
     }

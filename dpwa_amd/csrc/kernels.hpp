@@ -12,7 +12,7 @@ namespace dpwa {
 // Size in bytes of one element of `dtype`, 0 if unknown.
 inline size_t dtype_size(int32_t dtype)
 {
-    return dtype == DPWA_F32 ? 4 : dtype == DPWA_BF16 ? 2 : 0;
+    return dtype == DPWA_F32 ? 4 : dtype == DPWA_BF16 || dtype == DPWA_F16 ? 2 : 0;
 }
 
 // Inputs/outputs of the device factor computation (dpwa.py:139-155).  clock_in and

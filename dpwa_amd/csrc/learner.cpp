@@ -515,6 +515,21 @@ int dpwa_lerp_bf16_host(uint16_t *param, const uint16_t *peer, int64_t n, double
     return DPWA_OK;
 }
 
+int dpwa_lerp_f16(uint16_t *param, const uint16_t *peer, int64_t n, const dpwa_coef *coef_dev,
+                  dpwa_stream_t stream)
+{
+    if (n < 0 || (n > 0 && (!param || !peer || !coef_dev))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_f16: bad arguments");
+    HIP_TRY(launch_lerp(DPWA_F16, param, peer, n, coef_dev, 0.f, 0.f, (hipStream_t)stream));
+    return DPWA_OK;
+}
+
+int dpwa_lerp_f16_host(uint16_t *param, const uint16_t *peer, int64_t n, double factor, dpwa_stream_t stream)
+{
+    if (n < 0 || (n > 0 && (!param || !peer))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_f16_host: bad arguments");
+    HIP_TRY(launch_lerp(DPWA_F16, param, peer, n, nullptr, (float)factor, (float)(1.0 - factor), (hipStream_t)stream));
+    return DPWA_OK;
+}
+
 int dpwa_factor(const dpwa_interp *cfg, double *clock_dev, const dpwa_header *peer_header_dev, double loss,
                 const double *loss_dev, dpwa_coef *coef_dev, dpwa_stream_t stream)
 {

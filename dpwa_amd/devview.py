@@ -39,7 +39,8 @@ class DLManagedTensor(ctypes.Structure):
 _DELETER = ctypes.CFUNCTYPE(None, ctypes.POINTER(DLManagedTensor))
 DLManagedTensor._fields_ = [("dl_tensor", DLTensor), ("manager_ctx", ctypes.c_void_p), ("deleter", _DELETER)]
 
-_DTYPES = {torch.float32: (_KDL_FLOAT, 32), torch.bfloat16: (_KDL_BFLOAT, 16), torch.uint8: (1, 8)}
+_DTYPES = {torch.float32: (_KDL_FLOAT, 32), torch.bfloat16: (_KDL_BFLOAT, 16), torch.float16: (_KDL_FLOAT, 16),
+           torch.uint8: (1, 8)}
 _libc = ctypes.CDLL(None)
 _libc.malloc.restype = ctypes.c_void_p
 _libc.malloc.argtypes = [ctypes.c_size_t]

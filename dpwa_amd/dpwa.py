@@ -569,7 +569,7 @@ class DpwaConnection:
             raise TypeError("DpwaConnection.update_send expects the flat parameter buffer as a GPU tensor")
         if parameters.dtype not in DTYPES:
             # the reference's TYPE_CONVERSION lookup raises KeyError (pytorch.py:11-14, 22)
-            raise KeyError("dpwa averages float32 or bfloat16 parameters, got %s" % parameters.dtype)
+            raise KeyError("dpwa averages float32, bfloat16 or float16 parameters, got %s" % parameters.dtype)
         _lib.call("dpwa_node_bind", self._node, parameters.device.index, parameters.numel(),
                   DTYPES[parameters.dtype])
         h = ctypes.c_void_p()

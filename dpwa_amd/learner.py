@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 
-DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 
 _c_void_p = ctypes.c_void_p
 MAX_FDS = 240          # chunks (1 GiB each) one exported allocation may have; < SCM_MAX_FD (253)
@@ -32,7 +32,7 @@ class Learner:
     def __init__(self, device, numel, dtype, interp_cfg=None, handle=None):
         """Creates a learner, or wraps (without owning) `handle` from dpwa_node_handles."""
         if dtype not in DTYPES:
-            raise KeyError("dpwa averages float32 or bfloat16 parameters, got %s" % dtype)
+            raise KeyError("dpwa averages float32, bfloat16 or float16 parameters, got %s" % dtype)
         self.device = torch.device(device)
         self.numel = int(numel)
         self.dtype = dtype

@@ -27,7 +27,8 @@
 extern "C" {
 #endif
 
-#define DPWA_ABI_VERSION 10
+/* 11: DPWA_F16 -- float16 parameters through every averaging form, dpwa_lerp_f16{,_host}. */
+#define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
 #define DPWA_ERR_ARG (-1)     /* bad argument (API misuse)                          */
@@ -39,6 +40,7 @@ extern "C" {
 #define DPWA_F32 0            /* the reference's only type: TYPE_CONVERSION, pytorch.py:11-14 */
 #define DPWA_BF16 1           /* extension: torch-eager bf16 rounding, no reference path      */
 #define DPWA_F64 2            /* loss scalars only (dpwa_learner_set_loss_dtype)              */
+#define DPWA_F16 3            /* extension: torch-eager fp16 rounding, no reference path       */
 
 /* interpolation methods: INTERPOLATION_METHODS, dpwa/dpwa.py:11-15 */
 #define DPWA_INTERP_CONSTANT 0   /* interpolation.py:8-15  factor = value                       */
@@ -64,7 +66,7 @@ typedef struct dpwa_header {
     double loss;         /* loss given to update_send (dpwa.py:115)                      */
     uint64_t version;    /* publishes so far; 0 = never published (have_state, conn.py:60) */
     int64_t n;           /* payload elements                                              */
-    int32_t dtype;       /* DPWA_F32 / DPWA_BF16                                          */
+    int32_t dtype;       /* DPWA_F32 / DPWA_BF16 / DPWA_F16: what a peer checks first   */
     int32_t reserved0;
     uint8_t pad[216];
 } dpwa_header;
@@ -123,10 +125,16 @@ int dpwa_lerp_f32(float *param, const float *peer, int64_t n, const dpwa_coef *c
 /* bf16 form: bf16(bf16(a*peer) + bf16(b*param)), RNE (torch-eager bf16). */
 int dpwa_lerp_bf16(uint16_t *param, const uint16_t *peer, int64_t n, const dpwa_coef *coef_dev,
                    dpwa_stream_t stream);
+/* fp16 form: f16(f16(a*peer) + f16(b*param)), RNE, subnormals kept (torch-eager float16).  bf16 and
+ * fp16 elements have the same size: the dtype code is all that tells them apart.  ABI version 11. */
+int dpwa_lerp_f16(uint16_t *param, const uint16_t *peer, int64_t n, const dpwa_coef *coef_dev,
+                  dpwa_stream_t stream);
 /* Same kernels with the factor given by the host, as pytorch.py:68 receives it. */
 int dpwa_lerp_f32_host(float *param, const float *peer, int64_t n, double factor, dpwa_stream_t stream);
 int dpwa_lerp_bf16_host(uint16_t *param, const uint16_t *peer, int64_t n, double factor,
                         dpwa_stream_t stream);
+int dpwa_lerp_f16_host(uint16_t *param, const uint16_t *peer, int64_t n, double factor,
+                       dpwa_stream_t stream);
 
 /* The fused average of dpwa_learner_average without a learner (the product kernel over
  * caller-owned buffers): reads clock_dev[0] and the 256-B dpwa_header at `peer_slot`, lerps the
