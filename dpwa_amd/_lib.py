@@ -20,7 +20,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dpwa_hip.h")
 # Constants mirrored from include/dpwa_hip.h
 ABI_VERSION = 11
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
-F32, BF16, F64, F16 = 0, 1, 2, 3
+F32, BF16, F64, F16, MIXED = 0, 1, 2, 3, 4
+LAYOUT_MAX_SEGMENTS, LAYOUT_ALIGN = 3, 4096
 INTERP_CONSTANT, INTERP_CLOCK, INTERP_LOSS = 0, 1, 2
 STATUS_OK, STATUS_ZERO_DIVISION = 0, 1
 IPC_HANDLE_BYTES = 128
@@ -64,6 +65,16 @@ class AverageDesc(ctypes.Structure):
                 ("snap_payload", ctypes.c_void_p)]
 
 
+class Segment(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32), ("byte_offset", ctypes.c_int64),
+                ("byte_length", ctypes.c_int64)]
+
+
+class Layout(ctypes.Structure):
+    """dpwa_layout: the segments of a DPWA_MIXED payload."""
+    _fields_ = [("count", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seg", Segment * LAYOUT_MAX_SEGMENTS)]
+
+
 class Interp(ctypes.Structure):
     _fields_ = [("method", ctypes.c_int32), ("reserved", ctypes.c_int32), ("value", ctypes.c_double),
                 ("divergence_threshold", ctypes.c_double)]
@@ -97,6 +108,10 @@ SIGNATURES = {
     "dpwa_lerp_f16_host": [_vp, _vp, _i64, _dbl, _vp],
     "dpwa_factor": [ctypes.POINTER(Interp), _vp, _vp, _dbl, _vp, _vp, _vp],
     "dpwa_average": [_i32, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_average_mixed": [ctypes.POINTER(Layout), _vp, _vp, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_layout_digest": [ctypes.POINTER(Layout), _i64, ctypes.POINTER(ctypes.c_uint32)],
+    "dpwa_learner_set_layout": [_vp, ctypes.POINTER(Layout)],
+    "dpwa_node_set_layout": [_vp, ctypes.POINTER(Layout)],
     "dpwa_average_many": [_i32, _vp, _int, ctypes.POINTER(Interp), _vp, _vp, _vp],
     "dpwa_average_many_resident": [_i32, _vp, _int, ctypes.POINTER(Interp), _vp, _vp, _vp],
     "dpwa_learner_average_many": [_vp, _vp, _vp, _vp, _vp, _int, _vp],
@@ -221,7 +236,10 @@ def load():
         _load_error = "cannot load %s: %s" % (LIB_PATH, e)
         raise DpwaLibraryError(_load_error) from e
     for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:      # an older build of the same ABI version (entries are added compatibly)
+            _load_error = "%s lacks %s: rebuild it (make -C dpwa_amd/csrc)" % (LIB_PATH, name)
+            raise DpwaLibraryError(_load_error)
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, ctypes.c_int)
     if lib.dpwa_abi_version() != ABI_VERSION:

@@ -9,8 +9,13 @@ in place with one fused HIP kernel whose coefficients come from the device facto
 Differences that are intentional: the average is written in place (the reference
 rebinds ``param.data`` to a new tensor), and float32, bfloat16 *and* float16 models are
 accepted (the reference maps only FloatTensor, pytorch.py:11-14); the 16-bit types round as
-torch-eager does on them.  Not accepted: a model that mixes dtypes (one flat buffer, one dtype),
-and 16-bit parameters over the wire bridge (dpwa_amd/bridge.py carries float32 only).
+torch-eager does on them.  A model that mixes the three (fp32 norm layers in a bf16 or fp16 body)
+is accepted too, in the write-through, plain and resident forms: its flat buffer is segmented by
+dtype (dpwa_amd/flat.py) and every parameter is averaged with its own dtype's rounding, as the
+reference's tensor-by-tensor loop would.  Not accepted: 16-bit or mixed parameters over the wire
+bridge (dpwa_amd/bridge.py carries float32 only), and ``pull='relay-avg'`` with a mixed model
+(``'relay'``, ``'kernel'`` and ``'copy'`` move bytes and work); co-resident mixed learners are
+averaged one launch each instead of one batched dispatch.
 """
 import ctypes
 import logging
@@ -80,7 +85,7 @@ class DpwaPyTorchAdapter:
             self._conn = WireConnection(name, config_file, codec=SnapshotCodec.from_flat(self._flat),
                                         **connection_kwargs)
         elif transport == "device":
-            self._conn = DpwaConnection(name, config_file, **connection_kwargs)
+            self._conn = DpwaConnection(name, config_file, layout=self._flat.layout, **connection_kwargs)
         else:
             raise ValueError("transport must be 'device' or 'wire'")
         self._write_through = bool(write_through) and transport == "device"

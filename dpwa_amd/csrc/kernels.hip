@@ -18,6 +18,8 @@
 //             share them through LDS); block 0
 //             also writes the new clock (into the other half of a double-buffered clock,
 //             so no workgroup ever reads a clock another one is writing) and dpwa_coef.
+//  * mixed:   the same pass over the segmented payload of a model that mixes float32, bfloat16
+//             and float16 parameters (k_lerp_mixed): each one-wave span rounds as its segment's type.
 //  * factor:  the same fp64 math as a one-thread kernel for the split API.
 //  * publish: update_send's snapshot (dpwa.py:111-116, pytorch.py:49-53) -- clock += 1 on
 //             the device and one copy of the flat buffer into a snapshot slot behind its
@@ -446,6 +448,79 @@ __global__ __launch_bounds__(BLOCK) void k_lerp(typename Ops::V *__restrict__ pa
                                                               args);
 }
 
+// ---------------------------------------------------------------- segmented (DPWA_MIXED) payloads
+// A model that mixes float32, bfloat16 and float16 parameters has a payload of up to three
+// segments, one per type, each a whole number of 4-KiB blocks (dpwa_layout, include/dpwa_hip.h): a
+// 1-KiB span lies inside one segment.  The table travels by value; unused entries begin at
+// INT64_MAX, so the lookup is two compares whatever the count.
+struct SegTable {
+    int64_t begin[DPWA_LAYOUT_MAX_SEGMENTS];   // ascending, begin[0] = 0
+    int32_t dtype[DPWA_LAYOUT_MAX_SEGMENTS];
+};
+
+// The type of the segment holding byte `off` (uniform: from kernel arguments and the span offset).
+__device__ __forceinline__ int32_t seg_dtype(const SegTable &t, int64_t off)
+{
+    int32_t d = t.dtype[0];
+#pragma unroll
+    for (int k = 1; k < DPWA_LAYOUT_MAX_SEGMENTS; ++k)
+        if (off >= t.begin[k]) d = t.dtype[k];
+    return d;
+}
+
+// The single-dtype span code (lerp_span: one 16-byte item per lane, loads first, the fp64 factor
+// by every lane while they are in flight, the commit by one lane of the grid, the no-op round)
+// for a segmented payload: the span's element op -- OpsF32 / OpsBF16 / OpsF16 ::lerp, so each
+// type rounds exactly as its own kernel -- is chosen under a uniform branch by the span's byte
+// offset (not by the workgroup index: right for any span order).  No ragged tail and no
+// unaligned form: `total` is a multiple of 4 KiB and the grid is exact.  One-wave workgroups.
+template <int MODE, bool DUAL, int POLICY, bool OOP>
+__global__ __launch_bounds__(kStreamBlock) void k_lerp_mixed(u32x4 *__restrict__ param,
+                                                             const u32x4 *__restrict__ peer, int64_t total,
+                                                             LerpArgs args, SegTable segs)
+{
+    using V = u32x4;
+    constexpr int SPAN = kStreamBlock * 16;
+    const ContigSrc src{(const char *)peer};
+    const uint32_t blk = blockIdx.x;
+    const int64_t span_off = src.template span_of<SPAN>(blk);
+    const int lane_off = threadIdx.x * 16;
+    const __amdgpu_buffer_rsrc_t rq = span_rsrc<SPAN>(src.span_base(span_off), span_off, total);
+    const __amdgpu_buffer_rsrc_t rp = span_rsrc<SPAN>(param, span_off, total);
+    // issue this lane's loads before anything else
+    const V q = span_load<V>(rq, lane_off);
+    const V p = span_load<V, LerpPolicy<POLICY>::param_load>(rp, lane_off);
+    const int32_t dtype = seg_dtype(segs, span_off);
+    float a, b;
+    if (MODE == COEF_DEV) {
+        if (args.coef->status != DPWA_STATUS_OK) return;
+        a = args.coef->a;
+        b = args.coef->b;
+    } else {
+        // every lane evaluates the (uniform) fp64 factor while the loads are in flight; global
+        // workgroup 0 -- not the first workgroup of each segment -- commits it, once
+        const FusedArgs &fa = args.fused;
+        const double loss = read_loss(fa.loss_d, fa.loss_f32, fa.loss_h);
+        const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss, loss);
+        if (blk == 0 && threadIdx.x == 0) factor_commit(fa, c);
+        a = c.a;
+        b = c.b;
+        if (c.status != DPWA_STATUS_OK) {   // no-op round; a write-through snapshot still gets the parameters
+            if (DUAL) span_store<V, LerpPolicy<POLICY>::snap_store>(span_rsrc<SPAN>(args.snap, span_off, total), lane_off, p);
+            return;
+        }
+    }
+    V r;
+    if (dtype == DPWA_F32)
+        r = __builtin_bit_cast(V, OpsF32::lerp(a, b, __builtin_bit_cast(f32x4, q), __builtin_bit_cast(f32x4, p)));
+    else if (dtype == DPWA_BF16)
+        r = OpsBF16::lerp(a, b, q, p);
+    else
+        r = OpsF16::lerp(a, b, q, p);
+    if (!OOP) span_store<V, LerpPolicy<POLICY>::store>(rp, lane_off, r);
+    if (DUAL) span_store<V, LerpPolicy<POLICY>::snap_store>(span_rsrc<SPAN>(args.snap, span_off, total), lane_off, r);
+}
+
 // The relay's fused second phase: the fused average reads the peer's snapshot stripe by stripe
 // where the relay left it (stripe s in rank s's relay buffer, the peer's own stripe in its slot,
 // ours in local HBM) instead of gathering it into staging first.
@@ -802,6 +877,73 @@ hipError_t launch_average(int32_t dtype, void *param, const void *peer, int64_t 
         return hipErrorInvalidValue;
     }
     return launch_any(dtype, COEF_FUSED, param, peer, n, args, s, timing);
+}
+
+const char *layout_problem(const dpwa_layout &layout, int64_t total_bytes)
+{
+    if (layout.count < 1) return "no segment";
+    if (layout.count > DPWA_LAYOUT_MAX_SEGMENTS) return "more than three segments";
+    int64_t end = 0;
+    for (int i = 0; i < layout.count; ++i) {
+        const dpwa_segment &g = layout.seg[i];
+        if (g.dtype != DPWA_F32 && g.dtype != DPWA_BF16 && g.dtype != DPWA_F16)
+            return "a segment's dtype is not DPWA_F32, DPWA_BF16 or DPWA_F16";
+        for (int j = 0; j < i; ++j)
+            if (layout.seg[j].dtype == g.dtype) return "a dtype is repeated";
+        if (g.byte_offset < 0 || g.byte_offset % DPWA_LAYOUT_ALIGN) return "a segment does not begin on a 4096-byte boundary";
+        if (g.byte_length <= 0 || g.byte_length % DPWA_LAYOUT_ALIGN)
+            return "a segment's length is not a positive multiple of 4096 bytes";
+        if (g.byte_offset < end) return "segments overlap or are out of order";
+        if (g.byte_offset > end) return i ? "a hole between two segments" : "the first segment does not begin at byte 0";
+        if (g.byte_length > INT64_MAX - end) return "the segments' total overflows";
+        end += g.byte_length;
+    }
+    if (total_bytes >= 0 && end != total_bytes) return "the segments do not cover the payload's bytes exactly";
+    return nullptr;
+}
+
+template <int MODE, bool DUAL, bool OOP>
+static hipError_t launch_mixed(const dpwa_layout &layout, void *param, const void *peer, const LerpArgs &args,
+                               hipStream_t s, const LaunchTiming *timing)
+{
+    if (layout_problem(layout, -1) || !param || !peer || !aligned16(param) || !aligned16(peer) || !aligned16(args.snap) ||
+        (DUAL && !args.snap))
+        return hipErrorInvalidValue;
+    SegTable t;
+    for (int i = 0; i < DPWA_LAYOUT_MAX_SEGMENTS; ++i) {
+        t.begin[i] = i < layout.count ? layout.seg[i].byte_offset : INT64_MAX;
+        t.dtype[i] = i < layout.count ? layout.seg[i].dtype : layout.seg[0].dtype;
+    }
+    const int64_t total = layout_bytes(layout);
+    const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
+    if (g > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (timing)
+        hipExtLaunchKernelGGL((k_lerp_mixed<MODE, DUAL, kProductPolicy, OOP>), dim3((uint32_t)g), dim3(kStreamBlock), 0,
+                              s, timing->start, timing->stop, 0, (u32x4 *)param, (const u32x4 *)peer, total, args, t);
+    else
+        hipLaunchKernelGGL((k_lerp_mixed<MODE, DUAL, kProductPolicy, OOP>), dim3((uint32_t)g), dim3(kStreamBlock), 0, s,
+                           (u32x4 *)param, (const u32x4 *)peer, total, args, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_lerp_mixed(const dpwa_layout &layout, void *param, const void *peer, const dpwa_coef *coef,
+                             hipStream_t s)
+{
+    if (!coef) return hipErrorInvalidValue;
+    LerpArgs args{};
+    args.coef = coef;
+    return launch_mixed<COEF_DEV, false, false>(layout, param, peer, args, s, nullptr);
+}
+
+hipError_t launch_average_mixed(const dpwa_layout &layout, void *param, const void *peer, const FusedArgs &fa,
+                                void *snap, hipStream_t s, const LaunchTiming *timing, bool oop)
+{
+    LerpArgs args{};
+    args.fused = fa;
+    args.snap = snap;
+    if (oop) return launch_mixed<COEF_FUSED, true, true>(layout, param, peer, args, s, timing);
+    if (snap) return launch_mixed<COEF_FUSED, true, false>(layout, param, peer, args, s, timing);
+    return launch_mixed<COEF_FUSED, false, false>(layout, param, peer, args, s, timing);
 }
 
 // Span order of a batched dispatch of equal-size entries.  Dealt round-robin, every span is

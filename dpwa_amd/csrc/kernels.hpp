@@ -12,7 +12,17 @@ namespace dpwa {
 // Size in bytes of one element of `dtype`, 0 if unknown.
 inline size_t dtype_size(int32_t dtype)
 {
-    return dtype == DPWA_F32 ? 4 : dtype == DPWA_BF16 || dtype == DPWA_F16 ? 2 : 0;
+    return dtype == DPWA_F32 ? 4 : dtype == DPWA_BF16 || dtype == DPWA_F16 ? 2 : dtype == DPWA_MIXED ? 1 : 0;
+}
+
+// The rules of a dpwa_layout (include/dpwa_hip.h); total_bytes >= 0: it must cover exactly that
+// many.  Returns null when valid, else the rule broken.  Host only, no HIP call.
+const char *layout_problem(const dpwa_layout &layout, int64_t total_bytes);
+// Total bytes of a valid layout.
+inline int64_t layout_bytes(const dpwa_layout &layout)
+{
+    const dpwa_segment &last = layout.seg[layout.count - 1];
+    return last.byte_offset + last.byte_length;
 }
 
 // Inputs/outputs of the device factor computation (dpwa.py:139-155).  clock_in and
@@ -53,6 +63,15 @@ struct LaunchTiming {
 // resident form): the result goes to `snap` only and `param` is read, never written.
 hipError_t launch_average(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa,
                           void *snap, hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
+
+// The averaging kernel of a DPWA_MIXED payload (k_lerp_mixed): every 1-KiB span is averaged with the
+// element op of the segment it lies in.  param / peer / snap 16-B aligned, the layout valid
+// (layout_problem), else hipErrorInvalidValue.  lerp_mixed: the coefficients from `coef` (device);
+// average_mixed: the fused average, `snap` and `oop` as launch_average.
+hipError_t launch_lerp_mixed(const dpwa_layout &layout, void *param, const void *peer, const dpwa_coef *coef,
+                             hipStream_t s);
+hipError_t launch_average_mixed(const dpwa_layout &layout, void *param, const void *peer, const FusedArgs &fa,
+                                void *snap, hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
 
 // Several fused averages (co-resident learners) in one dispatch: entry i's workgroups follow
 // entry i-1's.  Every pointer 16-B aligned; `dual` = every entry writes through (snap non-null).

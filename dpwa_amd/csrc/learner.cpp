@@ -68,6 +68,7 @@ struct IpcBlob {
     int32_t device;
     int32_t pid;
     int32_t vmm;                // 1: the allocation is shared as fds (dpwa_learner_export_fds)
+    int32_t layout_digest;      // DPWA_MIXED: dpwa_layout_digest of the payload's layout; else 0
 };
 static_assert(sizeof(IpcBlob) <= DPWA_IPC_HANDLE_BYTES, "IPC blob too large");
 
@@ -344,6 +345,10 @@ struct dpwa_learner {
     int device = 0;
     int64_t n = 0;
     int32_t dtype = DPWA_F32;
+    // DPWA_MIXED: which bytes of the payload hold which type (dpwa_learner_set_layout); the
+    // digest is what peers compare, 0 until the layout is set
+    dpwa_layout layout{};
+    uint32_t layout_digest = 0;
     dpwa_interp cfg{};
     size_t payload_bytes = 0;
     size_t slot_stride = 0;
@@ -554,6 +559,8 @@ int dpwa_average(int32_t dtype, void *param, const void *peer_slot, int64_t n, c
     if (!cfg || !clock_dev || !coef_dev || !peer_slot || n < 0 || (n > 0 && !param) || dtype_size(dtype) == 0 ||
         (!start_event) != (!stop_event))
         return set_error(DPWA_ERR_ARG, "dpwa_average: bad arguments");
+    if (dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_average: a DPWA_MIXED payload needs its layout (dpwa_average_mixed)");
     if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "dpwa_average: unknown method %d", cfg->method);
     FusedArgs fa{};
     fa.cfg = *cfg;
@@ -565,6 +572,54 @@ int dpwa_average(int32_t dtype, void *param, const void *peer_slot, int64_t n, c
     LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
     HIP_TRY(launch_average(dtype, param, (const char *)peer_slot + kPayloadOff, n, fa, snap_payload, (hipStream_t)stream,
                            start_event ? &t : nullptr));
+    return DPWA_OK;
+}
+
+static uint32_t layout_fnv(const dpwa_layout &layout)
+{
+    uint32_t h = 2166136261u;
+    auto mix = [&h](uint64_t v, int bytes) {
+        for (int k = 0; k < bytes; ++k) {
+            h ^= (uint32_t)((v >> (8 * k)) & 0xffu);
+            h *= 16777619u;
+        }
+    };
+    for (int i = 0; i < layout.count; ++i) {
+        mix((uint64_t)(uint32_t)layout.seg[i].dtype, 4);
+        mix((uint64_t)layout.seg[i].byte_offset, 8);
+        mix((uint64_t)layout.seg[i].byte_length, 8);
+    }
+    return h ? h : 1u;
+}
+
+int dpwa_layout_digest(const dpwa_layout *layout, int64_t total_bytes, uint32_t *digest)
+{
+    if (!layout || !digest) return set_error(DPWA_ERR_ARG, "dpwa_layout_digest: NULL argument");
+    if (const char *why = layout_problem(*layout, total_bytes)) return set_error(DPWA_ERR_ARG, "dpwa_layout_digest: %s", why);
+    *digest = layout_fnv(*layout);
+    return DPWA_OK;
+}
+
+int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_slot, const dpwa_interp *cfg,
+                       double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, dpwa_stream_t stream,
+                       void *start_event, void *stop_event)
+{
+    if (!layout || !cfg || !clock_dev || !coef_dev || !peer_slot || !param || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: bad arguments");
+    if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: %s", why);
+    if (((uintptr_t)param | (uintptr_t)peer_slot | (uintptr_t)snap_payload) & 15)
+        return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: a segmented payload is 16-byte aligned");
+    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: unknown method %d", cfg->method);
+    FusedArgs fa{};
+    fa.cfg = *cfg;
+    fa.clock_in = clock_dev;
+    fa.clock_out = clock_dev + 1;
+    fa.hdr = (const dpwa_header *)peer_slot;
+    fa.loss_h = loss;
+    fa.coef_out = coef_dev;
+    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
+    HIP_TRY(launch_average_mixed(*layout, param, (const char *)peer_slot + kPayloadOff, fa, snap_payload,
+                                 (hipStream_t)stream, start_event ? &t : nullptr));
     return DPWA_OK;
 }
 
@@ -889,6 +944,39 @@ int dpwa_learner_publish_reuse(dpwa_learner *l, const void *flat, double loss, c
     return publish_impl(l, flat, loss, loss_dev, (hipStream_t)stream, true);
 }
 
+// A DPWA_MIXED learner averages only once it knows its layout.
+static int need_layout(const dpwa_learner *l, const char *fn)
+{
+    if (l->dtype == DPWA_MIXED && !l->layout_digest)
+        return set_error(DPWA_ERR_STATE, "%s: a DPWA_MIXED learner has no layout yet (dpwa_learner_set_layout)", fn);
+    return DPWA_OK;
+}
+
+int dpwa_learner_set_layout(dpwa_learner *l, const dpwa_layout *layout)
+{
+    if (!l || !layout) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_layout: NULL argument");
+    if (l->dtype != DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_set_layout: the learner holds dtype %d, not DPWA_MIXED", l->dtype);
+    if (const char *why = layout_problem(*layout, l->n))
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_set_layout: %s (%lld payload bytes)", why, (long long)l->n);
+    const uint32_t digest = layout_fnv(*layout);
+    if (l->layout_digest && l->layout_digest != digest)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_set_layout: the learner already has another layout");
+    l->layout = *layout;
+    l->layout_digest = digest;
+    return DPWA_OK;
+}
+
+// The node's forwarder lives here, over the node's public handles: node.cpp is also built against
+// a host-only stand-in of the learner (tests/native), which knows no layouts.
+int dpwa_node_set_layout(dpwa_node *n, const dpwa_layout *layout)
+{
+    dpwa_learner *l = nullptr;
+    if (!n || dpwa_node_handles(n, &l, nullptr) != DPWA_OK || !l)
+        return set_error(DPWA_ERR_STATE, "dpwa_node_set_layout: node not bound");
+    return dpwa_learner_set_layout(l, layout);
+}
+
 int dpwa_learner_version(const dpwa_learner *l, uint64_t *version)
 {
     if (!l || !version) return set_error(DPWA_ERR_ARG, "dpwa_learner_version: NULL argument");
@@ -903,6 +991,9 @@ int dpwa_learner_attach_local(dpwa_learner *l, int peer_id, dpwa_learner *peer)
     if (peer->n != l->n || peer->dtype != l->dtype)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_attach_local: peer holds %lld elements of dtype %d, this learner %lld of %d",
                          (long long)peer->n, peer->dtype, (long long)l->n, l->dtype);
+    if (peer->layout_digest != l->layout_digest)
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_attach_local: peer's layout (digest %08x) is not this learner's (%08x)",
+                         peer->layout_digest, l->layout_digest);
     if (peer->device != l->device) {
         DeviceGuard dg(l->device);
         int can = 0;
@@ -938,6 +1029,7 @@ static IpcBlob make_blob(const dpwa_learner *l, const DevMem &m, int64_t stride)
     b.device = l->device;
     b.pid = (int32_t)getpid();
     b.vmm = m.vmm() ? 1 : 0;
+    b.layout_digest = (int32_t)l->layout_digest;
     return b;
 }
 
@@ -972,6 +1064,9 @@ static int check_blob(const dpwa_learner *l, const void *handle, int64_t handle_
     if (b.n != l->n || b.dtype != l->dtype)
         return set_error(DPWA_ERR_ARG, "%s: peer holds %lld elements of dtype %d, this learner %lld of %d", fn,
                          (long long)b.n, b.dtype, (long long)l->n, l->dtype);
+    if ((uint32_t)b.layout_digest != l->layout_digest)
+        return set_error(DPWA_ERR_ARG, "%s: peer's layout (digest %08x) is not this learner's (%08x)", fn,
+                         (uint32_t)b.layout_digest, l->layout_digest);
     return DPWA_OK;
 }
 
@@ -1235,6 +1330,7 @@ int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dp
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_factor: NULL learner");
     if (!l->have_fetch) return set_error(DPWA_ERR_STATE, "dpwa_learner_factor: no fetch in flight");
     if (l->have_factor) return set_error(DPWA_ERR_STATE, "dpwa_learner_factor: factor already computed for this fetch");
+    if (int rc = need_layout(l, "dpwa_learner_factor")) return rc;
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
     int rc = relay_materialize(l);
@@ -1278,7 +1374,12 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_lerp: a resident learner averages with dpwa_learner_average");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_lerp(l->dtype, flat, l->src + kPayloadOff, l->n, &l->ctl->coef, 0.f, 0.f, s));
+    if (l->dtype == DPWA_MIXED) {   // (its layout is known: the factor was computed)
+        if ((uintptr_t)flat & 15) return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
+        HIP_TRY(launch_lerp_mixed(l->layout, flat, l->src + kPayloadOff, &l->ctl->coef, s));
+    } else {
+        HIP_TRY(launch_lerp(l->dtype, flat, l->src + kPayloadOff, l->n, &l->ctl->coef, 0.f, 0.f, s));
+    }
     HIP_TRY(staging_read(l, s));
     l->wt_valid = false;
     l->consume_stream = s;
@@ -1298,6 +1399,7 @@ struct AvgPlan {
     bool relay = false;           // the relay's phase 2 fused into this average (k_lerp_relay)
     bool write_through = false;
     bool oop = false;             // resident: the result goes to `snap` only
+    bool mixed = false;           // a segmented payload (k_lerp_mixed): a launch of its own
     int snap_slot = -1;
 };
 
@@ -1305,7 +1407,11 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
                            bool write_through, AvgPlan &p)
 {
     if (!l->have_fetch || l->have_factor) return set_error(DPWA_ERR_STATE, "dpwa_learner_average: no fetch in flight");
+    if (int rc = need_layout(l, "dpwa_learner_average")) return rc;
+    if (l->dtype == DPWA_MIXED && ((uintptr_t)flat & 15))
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_average: a segmented payload is 16-byte aligned");
     p = AvgPlan();
+    p.mixed = l->dtype == DPWA_MIXED;
     if (l->resident) {   // read where the parameters are (the published slot), write the next slot
         if (flat != slot_payload(l, l->res_slot))
             return set_error(DPWA_ERR_ARG, "resident learner: average the parameters where they are "
@@ -1379,7 +1485,9 @@ static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 
 static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
-    if (p.relay) {
+    if (p.mixed) {   // never p.relay: relay_phase2 refuses to defer for a segmented payload
+        HIP_TRY(launch_average_mixed(l->layout, p.flat, p.peer, p.fa, p.snap, s, take_timing(l), p.oop));
+    } else if (p.relay) {
         HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
                                      take_timing(l), p.oop));
     } else {
@@ -1400,10 +1508,11 @@ static int average_impl(dpwa_learner *l, void *flat, double loss, const double *
     return average_commit(l, p, s);
 }
 
-// Can plan p join a batched dispatch (k_lerp_batch)?  Contiguous source, 16-B aligned operands.
+// Can plan p join a batched dispatch (k_lerp_batch)?  Contiguous source, 16-B aligned operands, one
+// element type (a segmented payload is not batched).
 static bool batchable(const AvgPlan &p)
 {
-    return !p.relay && ((((uintptr_t)p.flat | (uintptr_t)p.peer | (uintptr_t)p.snap) & 15) == 0);
+    return !p.relay && !p.mixed && ((((uintptr_t)p.flat | (uintptr_t)p.peer | (uintptr_t)p.snap) & 15) == 0);
 }
 
 // Launches the batchable plans in groups of the same (dtype, write-through), up to
@@ -1502,6 +1611,7 @@ static int average_many_impl(const char *fn, int32_t dtype, const dpwa_average_d
 {
     if (count < 1 || count > kMaxAvgBatch || !descs || !cfg || dtype_size(dtype) == 0 || (!start_event) != (!stop_event))
         return set_error(DPWA_ERR_ARG, "%s: bad arguments (1..%d descriptors)", fn, kMaxAvgBatch);
+    if (dtype == DPWA_MIXED) return set_error(DPWA_ERR_ARG, "%s: segmented (DPWA_MIXED) payloads are not batched", fn);
     if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "%s: unknown method %d", fn, cfg->method);
     AvgBatch b{};
     bool dual = oop;   // an empty entry may pass no buffers at all
@@ -1885,6 +1995,9 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
 {
     if (!l || !l->relay_on || !picks_dev || blocks < 1 || my_pick >= l->relay_world || my_pick == l->relay_rank)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_phase2: bad arguments");
+    if (fuse && l->dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_phase2: the fused second phase is not built for segmented "
+                                       "(DPWA_MIXED) payloads; gather (fuse = 0)");
     RelayArgs a;
     int rc = relay_args(l, picks_dev, version, a);
     if (rc) return rc;

@@ -21,13 +21,17 @@ import torch
 import yaml
 
 from . import _lib
+from .flat import c_layout
 from .group import default_group
 from .interpolation import INTERPOLATION_METHODS
-from .learner import DTYPES, Learner, loss_args
+from .learner import Learner, loss_args, native_dtype
 from .sched import Scheduler, seed_key
 
 LOGGER = logging.getLogger(__name__)
 RELAY_PULLS = ("relay", "relay-avg")   # DistGroup's multi-link transports (dpwa_amd/group.py)
+MIXED_RELAY_AVG = ("pull='relay-avg' is not available for a model that mixes dtypes: the relay's fused second "
+                   "phase is built for one element type; use 'relay' (the same relay, gathered first), 'kernel' "
+                   "or 'copy'")
 _MANY_CALLS = {}    # update_wait_average_many: argument arrays per set of nodes
 
 
@@ -92,7 +96,9 @@ class PeerSnapshot:
     """What update_wait returns in place of the reference's pickled payload bytes: the
     fetched snapshot, resident on the learner's GPU.  ``tensor()`` materialises it (a
     stream-ordered device copy) for callers that do the reference adapter's arithmetic
-    themselves (pytorch.py:64-68); it is valid until the fetch is averaged or abandoned."""
+    themselves (pytorch.py:64-68); it is valid until the fetch is averaged or abandoned.  The
+    snapshot of a learner whose model mixes dtypes materialises as the segmented buffer's bytes
+    (``torch.uint8``, ``numel`` bytes; ``FlatParameters.layout`` says which hold what)."""
 
     def __init__(self, conn, peer_index, version):
         self.peer = conn.peers[peer_index].name
@@ -187,8 +193,14 @@ class DeviceFactor:
 
 
 class DpwaConnection:
-    def __init__(self, name, config_file, seed=None, group=None, pull=None):
+    def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None):
+        """layout (extension): ``FlatParameters.layout`` when the flat buffer given to update_send
+        is the segmented ``torch.uint8`` buffer of a model that mixes dtypes (dpwa_amd/flat.py);
+        every peer must hold the same layout."""
         self.name = name
+        self._layout = tuple(layout) if layout is not None else None
+        if self._layout is not None and pull is not None and pull.partition(":")[0] == "relay-avg":
+            raise ValueError(MIXED_RELAY_AVG)
         self.config = DpwaConfiguration(config_file)
         self.nodes = self.config.get_nodes()
         self.fetch_probability = self.config.get_fetch_probability()
@@ -567,14 +579,18 @@ class DpwaConnection:
                              % (self.name, gpu, parameters.device))
         if not isinstance(parameters, torch.Tensor) or parameters.device.type != "cuda":
             raise TypeError("DpwaConnection.update_send expects the flat parameter buffer as a GPU tensor")
-        if parameters.dtype not in DTYPES:
-            # the reference's TYPE_CONVERSION lookup raises KeyError (pytorch.py:11-14, 22)
-            raise KeyError("dpwa averages float32, bfloat16 or float16 parameters, got %s" % parameters.dtype)
-        _lib.call("dpwa_node_bind", self._node, parameters.device.index, parameters.numel(),
-                  DTYPES[parameters.dtype])
+        # KeyError for any other dtype, a uint8 buffer without its layout included, as the
+        # reference's TYPE_CONVERSION lookup (pytorch.py:11-14, 22)
+        code = native_dtype(parameters.dtype, self._layout)
+        if self._layout is not None and self._pull.partition(":")[0] == "relay-avg":
+            raise ValueError(MIXED_RELAY_AVG)
+        _lib.call("dpwa_node_bind", self._node, parameters.device.index, parameters.numel(), code)
+        if self._layout is not None:     # before on_bind: peers compare layouts when they attach
+            _lib.call("dpwa_node_set_layout", self._node, ctypes.byref(c_layout(self._layout)))
         h = ctypes.c_void_p()
         _lib.call("dpwa_node_handles", self._node, ctypes.byref(h), None)
-        self._learner = Learner(parameters.device, parameters.numel(), parameters.dtype, handle=h.value)
+        self._learner = Learner(parameters.device, parameters.numel(), parameters.dtype, handle=h.value,
+                                layout=self._layout)
         if self._pending_clock is not None:           # load_state_dict before the first round
             self._learner.write_clock(self._pending_clock)
             self._pending_clock = None
@@ -597,6 +613,8 @@ class DpwaConnection:
         if kind not in ("copy", "kernel") + RELAY_PULLS:
             raise ValueError("pull must be 'copy', 'kernel[:blocks]', 'relay[:blocks]' or 'relay-avg[:blocks]', "
                              "got %r" % mode)
+        if kind == "relay-avg" and self._layout is not None:
+            raise ValueError(MIXED_RELAY_AVG)
         self._pull = mode
         learner = self._learner
         if learner is None:

@@ -6,10 +6,48 @@ parameters are re-homed once into a single contiguous buffer -- each tensor star
 256-byte boundary, in ``named_parameters()`` order, gaps zero-filled -- and every
 ``param.data`` becomes a view into it, so publishing and averaging are one kernel each
 over one buffer.  Gaps average to zero (0*a + 0*b).
+
+A model whose parameters share one dtype gets a buffer of that dtype.  A model that mixes
+float32, bfloat16 and float16 parameters (fp32 norms in a bf16 body, say) gets a *segmented*
+buffer: one segment per dtype present, in the fixed order float32, bfloat16, float16; inside a
+segment the tensors in ``named_parameters()`` order, each 256-byte aligned; every segment starting
+on a 4096-byte boundary and zero-filled up to a multiple of 4096 bytes, so that no 16-byte word, no
+1-KiB wave span of the averaging kernel and no relay stripe holds two dtypes.  That buffer is one
+``torch.uint8`` tensor, every ``param.data`` a typed view into it, and ``layout`` says which bytes
+hold which dtype (include/dpwa_hip.h ``dpwa_layout``).
 """
+import struct
+
 import torch
 
+from . import _lib
+
 ALIGN_BYTES = 256
+SEGMENT_BYTES = 4096          # DPWA_LAYOUT_ALIGN
+# the segments' order, and their codes in a dpwa_layout
+SEGMENT_DTYPES = ((torch.float32, _lib.F32), (torch.bfloat16, _lib.BF16), (torch.float16, _lib.F16))
+
+
+def layout_digest(layout):
+    """The 32-bit digest peers compare (dpwa_layout_digest in include/dpwa_hip.h, mirrored here):
+    FNV-1a over each segment's little-endian (int32 dtype code, int64 offset, int64 length); a
+    result of 0 becomes 1.  `layout`: tuples of (torch dtype, byte offset, byte length)."""
+    codes = dict(SEGMENT_DTYPES)
+    h = 2166136261
+    for dtype, off, length in layout:
+        for byte in struct.pack("<iqq", codes[dtype], off, length):
+            h = ((h ^ byte) * 16777619) & 0xffffffff
+    return h or 1
+
+
+def c_layout(layout):
+    """`layout` as the C ABI's dpwa_layout."""
+    codes = dict(SEGMENT_DTYPES)
+    out = _lib.Layout()
+    out.count = len(layout)
+    for i, (dtype, off, length) in enumerate(layout):
+        out.seg[i] = _lib.Segment(codes[dtype], 0, off, length)
+    return out
 
 
 class FlatParameters:
@@ -22,11 +60,15 @@ class FlatParameters:
             raise ValueError("the model has no parameters")
         dtypes = {p.dtype for _, p in params}
         devices = {p.device for _, p in params}
-        if len(dtypes) != 1 or len(devices) != 1:
-            raise TypeError("all parameters must share one dtype and one device, got %s on %s"
-                            % (sorted(map(str, dtypes)), sorted(map(str, devices))))
-        self.dtype = dtypes.pop()
+        if len(devices) != 1:
+            raise TypeError("all parameters must be on one device, got %s" % sorted(map(str, devices)))
         self.device = devices.pop() if device is None else torch.device(device)
+        self.layout = None            # segmented buffers only: ((dtype, byte offset, byte length), ...)
+        self.layout_digest = 0
+        if len(dtypes) != 1:
+            self._init_segmented(params, dtypes)
+            return
+        self.dtype = dtypes.pop()
         esize = torch.empty((), dtype=self.dtype).element_size()
         align = ALIGN_BYTES // esize
         self.names, self.params, self.offsets = [], [], []
@@ -43,10 +85,51 @@ class FlatParameters:
                 self.buffer[o:o + p.numel()].copy_(p.data.reshape(-1))
         self._rebind()
 
+    def _init_segmented(self, params, dtypes):
+        """Parameters of several dtypes: `buffer` is uint8, `offsets` and `numel` count bytes."""
+        known = [d for d, _ in SEGMENT_DTYPES]
+        for d in sorted(dtypes, key=str):
+            if d not in known:
+                # the reference's TYPE_CONVERSION lookup raises KeyError (pytorch.py:11-14, 22)
+                raise KeyError("dpwa averages float32, bfloat16 or float16 parameters, got %s" % d)
+        self.dtype = torch.uint8
+        self.names = [name for name, _ in params]
+        self.params = [p for _, p in params]
+        self._pdtypes = [p.dtype for p in self.params]
+        self._pbytes = [p.numel() * p.element_size() for p in self.params]
+        self.offsets = [0] * len(params)
+        layout, off = [], 0
+        for d in known:
+            if d not in dtypes:
+                continue
+            begin = off
+            for i, p in enumerate(self.params):
+                if p.dtype == d:
+                    self.offsets[i] = off
+                    off += (self._pbytes[i] + ALIGN_BYTES - 1) // ALIGN_BYTES * ALIGN_BYTES
+            off = max(off, begin + 1)         # a segment of empty tensors still takes a block
+            off = (off + SEGMENT_BYTES - 1) // SEGMENT_BYTES * SEGMENT_BYTES
+            layout.append((d, begin, off - begin))
+        self.layout = tuple(layout)
+        self.layout_digest = layout_digest(self.layout)
+        self.numel = off
+        self.buffer = torch.zeros(self.numel, dtype=torch.uint8, device=self.device)
+        with torch.no_grad():
+            for i, p in enumerate(self.params):
+                self._view(self.buffer, i).reshape(-1).copy_(p.data.reshape(-1))
+        self._rebind()
+
+    def _view(self, buffer, i):
+        """Parameter i's view into `buffer` (a tensor of this layout)."""
+        p, o = self.params[i], self.offsets[i]
+        if self.layout is None:
+            return buffer[o:o + p.numel()].view(p.shape)
+        return buffer[o:o + self._pbytes[i]].view(self._pdtypes[i]).view(p.shape)
+
     def _rebind(self):
         self._ptrs = []
-        for p, o in zip(self.params, self.offsets):
-            p.data = self.buffer[o:o + p.numel()].view(p.shape)
+        for i, p in enumerate(self.params):
+            p.data = self._view(self.buffer, i)
             self._ptrs.append(p.data_ptr())
 
     def rehome(self, buffer):
@@ -64,7 +147,7 @@ class FlatParameters:
         if views is None:
             if len(cache) >= 2:
                 cache.clear()
-            views = cache[key] = [buffer[o:o + p.numel()].view(p.shape) for p, o in zip(self.params, self.offsets)]
+            views = cache[key] = [self._view(buffer, i) for i in range(len(self.params))]
         self.buffer = buffer
         for p, v in zip(self.params, views):
             p.data = v
@@ -77,14 +160,15 @@ class FlatParameters:
             return 0          # the common case: one pointer read per parameter
         moved = 0
         with torch.no_grad():
-            for i, (p, o) in enumerate(zip(self.params, self.offsets)):
-                if p.data_ptr() != self._ptrs[i] or p.device != self.device or p.dtype != self.dtype:
-                    self.buffer[o:o + p.numel()].copy_(p.data.reshape(-1))
-                    p.data = self.buffer[o:o + p.numel()].view(p.shape)
+            for i, p in enumerate(self.params):
+                dtype = self.dtype if self.layout is None else self._pdtypes[i]
+                if p.data_ptr() != self._ptrs[i] or p.device != self.device or p.dtype != dtype:
+                    home = self._view(self.buffer, i)
+                    home.reshape(-1).copy_(p.data.reshape(-1))
+                    p.data = home
                     self._ptrs[i] = p.data_ptr()
                     moved += 1
         return moved
 
     def view(self, name):
-        i = self.names.index(name)
-        return self.buffer[self.offsets[i]:self.offsets[i] + self.params[i].numel()].view(self.params[i].shape)
+        return self._view(self.buffer, self.names.index(name))

@@ -10,11 +10,24 @@ import ctypes
 import torch
 
 from . import _lib
+from .flat import c_layout
 
 DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 
 _c_void_p = ctypes.c_void_p
 MAX_FDS = 240          # chunks (1 GiB each) one exported allocation may have; < SCM_MAX_FD (253)
+
+
+def native_dtype(dtype, layout=None):
+    """The DPWA_* code of a flat buffer's dtype; a torch.uint8 buffer is a segmented one and needs
+    its layout.  KeyError otherwise, as the reference's TYPE_CONVERSION lookup (pytorch.py:11-14)."""
+    if layout is not None:
+        if dtype != torch.uint8:
+            raise ValueError("a layout describes a torch.uint8 (segmented) buffer, got %s" % dtype)
+        return _lib.MIXED
+    if dtype not in DTYPES:
+        raise KeyError("dpwa averages float32, bfloat16 or float16 parameters, got %s" % dtype)
+    return DTYPES[dtype]
 
 
 def loss_args(loss, device):
@@ -29,20 +42,26 @@ def loss_args(loss, device):
 
 
 class Learner:
-    def __init__(self, device, numel, dtype, interp_cfg=None, handle=None):
-        """Creates a learner, or wraps (without owning) `handle` from dpwa_node_handles."""
-        if dtype not in DTYPES:
-            raise KeyError("dpwa averages float32, bfloat16 or float16 parameters, got %s" % dtype)
+    def __init__(self, device, numel, dtype, interp_cfg=None, handle=None, layout=None):
+        """Creates a learner, or wraps (without owning) `handle` from dpwa_node_handles.
+
+        layout: for a segmented buffer of a model that mixes dtypes (dpwa_amd/flat.py): `dtype` is
+        then torch.uint8, `numel` the buffer's bytes and the learner is DPWA_MIXED; a created
+        learner is given the layout here, a wrapped one has it already."""
+        code = native_dtype(dtype, layout)
         self.device = torch.device(device)
         self.numel = int(numel)
         self.dtype = dtype
+        self.layout = tuple(layout) if layout is not None else None
         lib = _lib.load()
         self._lib = lib
         self._owned = handle is None
         if handle is None:
             self._h = ctypes.c_void_p()
-            _lib.call("dpwa_learner_create", ctypes.byref(self._h), self.device.index, self.numel, DTYPES[dtype],
+            _lib.call("dpwa_learner_create", ctypes.byref(self._h), self.device.index, self.numel, code,
                       ctypes.byref(interp_cfg))
+            if layout is not None:
+                _lib.call("dpwa_learner_set_layout", self._h, ctypes.byref(c_layout(self.layout)))
         else:
             self._h = ctypes.c_void_p(handle)
         clock, coef, sh, sp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()

@@ -27,7 +27,10 @@
 extern "C" {
 #endif
 
-/* 11: DPWA_F16 -- float16 parameters through every averaging form, dpwa_lerp_f16{,_host}. */
+/* 11: DPWA_F16 -- float16 parameters through every averaging form, dpwa_lerp_f16{,_host}.
+ * Still 11, by additions only (every ABI-11 caller runs unchanged): DPWA_MIXED -- segmented payloads
+ * (dpwa_layout): dpwa_average_mixed, dpwa_layout_digest, dpwa_learner_set_layout,
+ * dpwa_node_set_layout; the IPC handle carries the layout digest in bytes that were zero. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -41,6 +44,8 @@ extern "C" {
 #define DPWA_BF16 1           /* extension: torch-eager bf16 rounding, no reference path      */
 #define DPWA_F64 2            /* loss scalars only (dpwa_learner_set_loss_dtype)              */
 #define DPWA_F16 3            /* extension: torch-eager fp16 rounding, no reference path       */
+#define DPWA_MIXED 4          /* extension: a segmented payload of the three types above; its element is
+                                 one byte (n = payload bytes) and a dpwa_layout says which bytes hold what */
 
 /* interpolation methods: INTERPOLATION_METHODS, dpwa/dpwa.py:11-15 */
 #define DPWA_INTERP_CONSTANT 0   /* interpolation.py:8-15  factor = value                       */
@@ -66,7 +71,7 @@ typedef struct dpwa_header {
     double loss;         /* loss given to update_send (dpwa.py:115)                      */
     uint64_t version;    /* publishes so far; 0 = never published (have_state, conn.py:60) */
     int64_t n;           /* payload elements                                              */
-    int32_t dtype;       /* DPWA_F32 / DPWA_BF16 / DPWA_F16: what a peer checks first   */
+    int32_t dtype;       /* DPWA_F32 / BF16 / F16 / MIXED: what a peer checks first      */
     int32_t reserved0;
     uint8_t pad[216];
 } dpwa_header;
@@ -91,8 +96,37 @@ typedef struct dpwa_interp {
     double divergence_threshold;  /* 0 disables (README.md:62)                     */
 } dpwa_interp;
 
+/* The layout of a DPWA_MIXED payload (a model that mixes parameter dtypes): 1..3 segments, one per
+ * element type, each a whole number of 4 KiB blocks -- so no 16-byte word, no 1-KiB wave span and no
+ * relay stripe (4 KiB multiples) ever holds two types.  A valid layout has segment 0 at byte 0, every
+ * segment beginning where the one before ends (ascending, no overlap, no hole), byte_offset and
+ * byte_length positive multiples of DPWA_LAYOUT_ALIGN (the offset may be 0), every dtype one of
+ * DPWA_F32 / DPWA_BF16 / DPWA_F16 and none repeated.  Bytes of a segment no parameter occupies are
+ * zero and average to zero. */
+#define DPWA_LAYOUT_MAX_SEGMENTS 3
+#define DPWA_LAYOUT_ALIGN 4096
+typedef struct dpwa_segment {
+    int32_t dtype;        /* DPWA_F32 / DPWA_BF16 / DPWA_F16 */
+    int32_t reserved;
+    int64_t byte_offset;  /* from the payload's first byte */
+    int64_t byte_length;
+} dpwa_segment;
+typedef struct dpwa_layout {
+    int32_t count;        /* segments in use, 1..DPWA_LAYOUT_MAX_SEGMENTS */
+    int32_t reserved;
+    dpwa_segment seg[DPWA_LAYOUT_MAX_SEGMENTS];
+} dpwa_layout;
+
 const char *dpwa_last_error(void);
 int dpwa_abi_version(void);
+
+/* Validates `layout` (DPWA_ERR_ARG with a message naming the rule it breaks; total_bytes >= 0: it
+ * must also cover exactly that many bytes) and returns its 32-bit digest, what two peers compare
+ * before they average each other's bytes: FNV-1a (offset basis 2166136261, prime 16777619) over, for
+ * each segment in order, the little-endian bytes of dtype (4), byte_offset (8) and byte_length (8);
+ * a result of 0 is replaced by 1, so 0 always means "no layout".  No device is needed.
+ * dpwa_amd/flat.py layout_digest mirrors it. */
+int dpwa_layout_digest(const dpwa_layout *layout, int64_t total_bytes, uint32_t *digest);
 
 /* roctx ranges on the round (the reference's LOGGER.debug sites dpwa.py:119,152-153,
  * conn.py:242-243,296).  On only when DPWA_ROCTX=1 is set when the library loads: then
@@ -146,11 +180,21 @@ int dpwa_average(int32_t dtype, void *param, const void *peer_slot, int64_t n, c
                  double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, dpwa_stream_t stream,
                  void *start_event, void *stop_event);
 
+/* dpwa_average for a DPWA_MIXED payload: `layout` in place of (dtype, n).  param, the payload at
+ * peer_slot + DPWA_SLOT_PAYLOAD_OFFSET and snap_payload (NULL or as large) are 16-B aligned buffers of
+ * the layout's total bytes; every segment is averaged with its own type's rounding (exactly what
+ * dpwa_average computes on that segment alone), the new clock and *coef_dev are written once.
+ * DPWA_ERR_ARG for an invalid layout or an unaligned pointer.  Events as dpwa_average. */
+int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_slot, const dpwa_interp *cfg,
+                       double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, dpwa_stream_t stream,
+                       void *start_event, void *stop_event);
+
 /* dpwa_average over several independent (param, peer slot) pairs in ONE dispatch -- the averages
  * of co-resident learners of one round (pytorch.py:66-68 once per learner).  Each descriptor is
  * one dpwa_average call: its own clock_dev (reads [0], writes [1]), coefficient block and loss;
  * all share `cfg` and `dtype`, and either all or none write through (snap_payload).  Every
- * pointer 16-B aligned; 1..8 descriptors.  Events as dpwa_average (the whole dispatch). */
+ * pointer 16-B aligned; 1..8 descriptors.  Events as dpwa_average (the whole dispatch).
+ * DPWA_MIXED is refused (DPWA_ERR_ARG): segmented payloads are not batched. */
 typedef struct dpwa_average_desc {
     void *param;
     const void *peer_slot;   /* [dpwa_header | pad | payload] */
@@ -185,6 +229,15 @@ int dpwa_factor(const dpwa_interp *cfg, double *clock_dev, const dpwa_header *pe
 typedef struct dpwa_learner dpwa_learner;
 
 int dpwa_learner_create(dpwa_learner **out, int device, int64_t n, int32_t dtype, const dpwa_interp *cfg);
+/* A learner created as DPWA_MIXED (n = payload bytes) is given its layout here, before it is
+ * attached to peers and before its first average: DPWA_ERR_ARG for a learner of another dtype, a
+ * layout that is invalid or does not cover exactly n bytes; DPWA_ERR_STATE for a second, different
+ * layout.  Without one, publishes and pulls work (they move bytes) and every average, factor-then-lerp
+ * included, is DPWA_ERR_STATE.  Peers must hold the same layout: attach_local and the IPC attach
+ * compare its digest next to n and dtype.  Mixed learners are never batched
+ * (dpwa_learner_average_many gives each its own launch) and refuse the relay's fused second phase
+ * (dpwa_learner_relay_phase2 with fuse != 0). */
+int dpwa_learner_set_layout(dpwa_learner *l, const dpwa_layout *layout);
 
 /* Measurement only (bench.py `roofline.mix_ceiling`; no reference interface): the averaging
  * kernels' access mix with nothing else in it -- every 1-KiB span of `nr` (1-2) source buffers
@@ -525,6 +578,8 @@ int dpwa_node_create(dpwa_node **out, int n_peers, const uint32_t *seed_key, int
 int dpwa_node_destroy(dpwa_node *n);
 /* Creates the node's learner for an n-element flat buffer of `dtype` on `device`. */
 int dpwa_node_bind(dpwa_node *n, int device, int64_t numel, int32_t dtype);
+/* dpwa_learner_set_layout for the node's learner (bound as DPWA_MIXED), before its peers attach. */
+int dpwa_node_set_layout(dpwa_node *n, const dpwa_layout *layout);
 /* Borrowed handles of the node's learner (NULL before bind) and scheduler. */
 int dpwa_node_handles(dpwa_node *n, dpwa_learner **learner, dpwa_sched **sched);
 /* How peer `peer` (scheduler index) is reached: DPWA_NODE_PEER_*; `local` for LOCAL (may be n
