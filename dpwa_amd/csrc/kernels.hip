@@ -24,25 +24,24 @@
 //  * publish: update_send's snapshot (dpwa.py:111-116, pytorch.py:49-53) -- clock += 1 on
 //             the device and one copy of the flat buffer into a snapshot slot behind its
 //             header.
+//  * launches: the host half picks a kernel instantiation through with_ops (dtype) and Choice
+//             (workgroup size, cache policy -- "the policy table" says what each averaging form
+//             launches for a requested DPWA_LERP_POLICY) and starts it with launch().
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <type_traits>
 
 #include "kernels.hpp"
 
 #include <hip/hip_ext.h>
-
-#ifndef DPWA_FACTOR_LDS
-#define DPWA_FACTOR_LDS 0     // 1: one-wave workgroups hand the factor over through LDS too (A/B builds)
-#endif
-#ifndef DPWA_GROUP_FACTORS_FIRST
-#define DPWA_GROUP_FACTORS_FIRST 0   // 1: group_span evaluates every entry's factor before any store (A/B builds)
-#endif
 
 namespace dpwa {
 
@@ -58,6 +57,50 @@ static inline int64_t blocks_for(int64_t items)
 {
     int64_t g = (items + kBlock - 1) / kBlock;
     return g < 1 ? 1 : g;
+}
+
+// ---------------------------------------------------------------- host helpers
+// One launch.  With `timing` the dispatch itself is timed (the kernel's begin/end, as a profiler
+// sees it).  The arguments are converted to the kernel's parameter types.
+template <class... Params, class... Args>
+static hipError_t launch(void (*kernel)(Params...), dim3 grid, dim3 block, hipStream_t s, const LaunchTiming *timing,
+                         const Args &...args)
+{
+    if (timing)
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, s, timing->start, timing->stop, 0, (Params)args...);
+    else
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, (Params)args...);
+    return hipGetLastError();
+}
+
+// A run-time integer as a template argument: with(v, f) calls f(std::integral_constant<int, V>{})
+// for the listed V equal to v, or for FALLBACK.  Only the listed values and FALLBACK are
+// instantiated.
+template <int FALLBACK, int... Vs> struct Choice {
+    static constexpr int launched(int v) { return ((v == Vs) || ...) ? v : FALLBACK; }
+    template <class F> static hipError_t with(int v, F &&f)
+    {
+        hipError_t r = hipSuccess;
+        const bool listed = ((v == Vs && (r = f(std::integral_constant<int, Vs>{}), true)) || ...);
+        return listed ? r : f(std::integral_constant<int, FALLBACK>{});
+    }
+};
+
+// A tuning knob: environment variable `name`, where parse(text) is its value, or kNoValue for a
+// text that is not accepted; unset or not accepted, the knob is `dflt`.  Every knob reads its
+// variable once (a static at its call site).
+constexpr int kNoValue = INT_MIN;
+
+template <class Parse> static int env_knob(const char *name, int dflt, Parse parse)
+{
+    const char *e = getenv(name);
+    const int v = e ? parse(e) : kNoValue;
+    return v == kNoValue ? dflt : v;
+}
+
+static int one_of(int v, std::initializer_list<int> accepted)
+{
+    return std::find(accepted.begin(), accepted.end(), v) != accepted.end() ? v : kNoValue;
 }
 
 // ---------------------------------------------------------------- element ops
@@ -131,6 +174,7 @@ struct OpsF32 {
     using V = f32x4;
     using S = float;
     static constexpr int PER = 4;
+    static constexpr bool TAIL = true;   // n counts elements; those past the last whole V are the ragged tail
     __device__ static __forceinline__ V lerp(float a, float b, V q, V p)
     {
         V x = a * q;
@@ -144,6 +188,7 @@ struct OpsBF16 {
     using V = u32x4;
     using S = uint16_t;
     static constexpr int PER = 8;
+    static constexpr bool TAIL = true;
     __device__ static __forceinline__ V lerp(float a, float b, V q, V p)
     {
         V r;
@@ -163,6 +208,7 @@ struct OpsF16 {
     using V = u32x4;
     using S = uint16_t;
     static constexpr int PER = 8;
+    static constexpr bool TAIL = true;
     __device__ static __forceinline__ V lerp(float a, float b, V q, V p)
     {
         V r;
@@ -177,6 +223,17 @@ struct OpsF16 {
         return lerp_f16x1(a, b, q, p);
     }
 };
+
+// A run-time dtype as an element-op type: f(OpsF32{}) and so on.
+template <class F> static hipError_t with_ops(int32_t dtype, F &&f)
+{
+    switch (dtype) {
+    case DPWA_F32: return f(OpsF32{});
+    case DPWA_BF16: return f(OpsBF16{});
+    case DPWA_F16: return f(OpsF16{});
+    default: return hipErrorInvalidValue;
+    }
+}
 
 // The loss given to update_send / update_wait: a host double, or read on the device from a
 // float64 or float32 scalar (a loss tensor, so the host never synchronises).
@@ -243,12 +300,20 @@ __device__ __forceinline__ void factor_commit(const FusedArgs &fa, const dpwa_co
     }
 }
 
+// The fused-factor prologue: the (uniform) factor, evaluated by every lane that calls this;
+// `commit` is true for the one lane of the grid that also writes it out.
+__device__ __forceinline__ dpwa_coef fused_factor(const FusedArgs &fa, bool commit)
+{
+    const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss,
+                                    read_loss(fa.loss_d, fa.loss_f32, fa.loss_h));
+    if (commit) factor_commit(fa, c);
+    return c;
+}
+
 __global__ void k_factor(FusedArgs fa)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const double loss = read_loss(fa.loss_d, fa.loss_f32, fa.loss_h);
-    const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss, loss);
-    factor_commit(fa, c);
+    fused_factor(fa, true);
 }
 
 hipError_t launch_factor(const FusedArgs &fa, hipStream_t s)
@@ -266,6 +331,48 @@ struct LerpArgs {
     FusedArgs fused;             // COEF_FUSED
     void *snap;                  // DUAL: second destination (the next snapshot's payload)
 };
+
+// The MODE ladder: this launch's (a, b).  False: nothing to average -- COEF_DEV after a factor
+// kernel that failed, COEF_FUSED in a no-op round.  The fused factor is evaluated in fp64 by
+// every lane, which keeps the uniform (a, b) in registers (no LDS hand-off, no barrier), or with
+// LDS (workgroups of more than one wave) by wave 0, which shares them through LDS; callers
+// issue their loads first, so that they are in flight meanwhile.  Lane 0 of the workgroup for
+// which `first_wg` holds commits the factor.
+template <int MODE, bool LDS = false>
+__device__ __forceinline__ bool lerp_coef(const LerpArgs &args, bool first_wg, float &a, float &b)
+{
+    if (MODE == COEF_HOST) {
+        a = args.a;
+        b = args.b;
+        return true;
+    } else if (MODE == COEF_DEV) {
+        if (args.coef->status != DPWA_STATUS_OK) return false;
+        a = args.coef->a;
+        b = args.coef->b;
+        return true;
+    } else if (!LDS) {
+        const dpwa_coef c = fused_factor(args.fused, first_wg && threadIdx.x == 0);
+        a = c.a;
+        b = c.b;
+        return c.status == DPWA_STATUS_OK;
+    } else {
+        __shared__ float s_a, s_b;
+        __shared__ int s_ok;
+        if (threadIdx.x < 64) {
+            const dpwa_coef c = fused_factor(args.fused, false);   // (lane 0's commit follows its hand-off)
+            if (threadIdx.x == 0) {
+                s_a = c.a;
+                s_b = c.b;
+                s_ok = c.status == DPWA_STATUS_OK;
+                if (first_wg) factor_commit(args.fused, c);
+            }
+        }
+        __syncthreads();
+        a = s_a;
+        b = s_b;
+        return s_ok != 0;
+    }
+}
 
 // ---------------------------------------------------------------- streaming buffer access
 // Every workgroup covers one span (BLOCK lanes x 16 B) of each operand through its own
@@ -312,9 +419,8 @@ template <int POLICY> struct LerpPolicy {
     static constexpr int base_store = kAuxStore | ((POLICY & 2) ? 1 : 0) | ((POLICY & 4) ? kAuxStream : 0);
     // bit 16: only the next snapshot is stored `nt` (a co-resident peer reads it two averages
     // later; this learner's parameters, re-read by its next average one average later, keep
-    // the Infinity Cache); bit 32: only the next snapshot is stored `sc0 sc1` (system scope:
-    // written through the XCD L2, so the launch's end-of-kernel L2 write-back finds it clean)
-    static constexpr int snap_store = base_store | ((POLICY & 16) ? kAuxStream : 0) | ((POLICY & 32) ? 1 : 0);
+    // the Infinity Cache)
+    static constexpr int snap_store = base_store | ((POLICY & 16) ? kAuxStream : 0);
     // bit 8: the parameters are stored `nt`, leaving the Infinity Cache to the snapshot a peer
     // reads next (the product policy)
     static constexpr int store = base_store | ((POLICY & 8) ? kAuxStream : 0);
@@ -364,79 +470,46 @@ struct StripeSrc {
 // averaging's own bytes; learner.cpp "resident").  BLOCK lanes per workgroup (kStreamBlock).
 template <class Ops, int MODE, bool DUAL, int BLOCK, int POLICY, class Src, bool OOP = false>
 __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restrict__ param, const Src &src,
-                                          int64_t n, const LerpArgs &args)
+                                          int64_t n, const LerpArgs &args, const Ops &ops = Ops{})
 {
     using V = typename Ops::V;
+    using P = LerpPolicy<POLICY>;
     constexpr int SPAN = BLOCK * 16;
-    const int64_t nv = n / Ops::PER;
+    const int64_t vbytes = Ops::TAIL ? n / Ops::PER * 16 : n;   // the whole 16-byte items
     const int64_t span_off = src.template span_of<SPAN>(blk);
     const int lane_off = threadIdx.x * 16;
-    const __amdgpu_buffer_rsrc_t rq = span_rsrc<SPAN>(src.span_base(span_off), span_off, nv * 16);
-    const __amdgpu_buffer_rsrc_t rp = span_rsrc<SPAN>(param, span_off, nv * 16);
+    const __amdgpu_buffer_rsrc_t rq = span_rsrc<SPAN>(src.span_base(span_off), span_off, vbytes);
+    const __amdgpu_buffer_rsrc_t rp = span_rsrc<SPAN>(param, span_off, vbytes);
     // issue this lane's loads before anything else
     const V q = span_load<V>(rq, lane_off);
-    const V p = span_load<V, LerpPolicy<POLICY>::param_load>(rp, lane_off);
+    const V p = span_load<V, P::param_load>(rp, lane_off);
     float a, b;
-    if (MODE == COEF_HOST) {
-        a = args.a;
-        b = args.b;
-    } else if (MODE == COEF_DEV) {
-        if (args.coef->status != DPWA_STATUS_OK) return;
-        a = args.coef->a;
-        b = args.coef->b;
-    } else {
-        bool ok;
-        if (BLOCK == 64 && !DPWA_FACTOR_LDS) {
-            // one-wave workgroup: every lane evaluates the (uniform) fp64 factor while the loads
-            // are in flight and keeps it in registers -- no LDS hand-off, no barrier
-            const FusedArgs &fa = args.fused;
-            const double loss = read_loss(fa.loss_d, fa.loss_f32, fa.loss_h);
-            const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss, loss);
-            if (blk == 0 && threadIdx.x == 0) factor_commit(fa, c);
-            a = c.a;
-            b = c.b;
-            ok = c.status == DPWA_STATUS_OK;
-        } else {
-            __shared__ float s_a, s_b;
-            __shared__ int s_ok;
-            if (threadIdx.x < 64) {  // wave 0: fp64 factor while the loads are in flight
-                const FusedArgs &fa = args.fused;
-                const double loss = read_loss(fa.loss_d, fa.loss_f32, fa.loss_h);
-                const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss, loss);
-                if (threadIdx.x == 0) {
-                    s_a = c.a;
-                    s_b = c.b;
-                    s_ok = c.status == DPWA_STATUS_OK;
-                    if (blk == 0) factor_commit(fa, c);
+    if (!lerp_coef<MODE, BLOCK != 64>(args, blk == 0, a, b)) {
+        if (MODE == COEF_FUSED && DUAL) {   // no-op round; a write-through snapshot still gets the parameters
+            span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, p);
+            if constexpr (Ops::TAIL) {
+                const int64_t tail = n / Ops::PER * Ops::PER;
+                if (blk == 0 && threadIdx.x < n - tail) {
+                    const int64_t j = tail + threadIdx.x;
+                    reinterpret_cast<typename Ops::S *>(args.snap)[j] = reinterpret_cast<typename Ops::S *>(param)[j];
                 }
             }
-            __syncthreads();
-            a = s_a;
-            b = s_b;
-            ok = s_ok != 0;
         }
-        if (!ok) {            // no-op round; a write-through snapshot still gets the parameters
-            if (DUAL)
-                span_store<V, LerpPolicy<POLICY>::snap_store>(span_rsrc<SPAN>(args.snap, span_off, nv * 16), lane_off, p);
-            if (DUAL && blk == 0 && threadIdx.x < n - nv * Ops::PER) {
-                const int64_t j = nv * Ops::PER + threadIdx.x;
-                reinterpret_cast<typename Ops::S *>(args.snap)[j] = reinterpret_cast<typename Ops::S *>(param)[j];
-            }
-            return;
-        }
+        return;
     }
-    {
-        const V r = Ops::lerp(a, b, q, p);
-        if (!OOP) span_store<V, LerpPolicy<POLICY>::store>(rp, lane_off, r);
-        if (DUAL) span_store<V, LerpPolicy<POLICY>::snap_store>(span_rsrc<SPAN>(args.snap, span_off, nv * 16), lane_off, r);
-    }
-    if (blk == 0 && threadIdx.x < n - nv * Ops::PER) {
+    const V r = ops.lerp(a, b, q, p);
+    if (!OOP) span_store<V, P::store>(rp, lane_off, r);
+    if (DUAL) span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, r);
+    if constexpr (Ops::TAIL) {
         using S = typename Ops::S;
         S *ps = reinterpret_cast<S *>(param);
-        const int64_t j = nv * Ops::PER + threadIdx.x;
-        const S r = Ops::lerp_s(a, b, *reinterpret_cast<const S *>(src.at(j * (int64_t)sizeof(S))), ps[j]);
-        if (!OOP) ps[j] = r;
-        if (DUAL) reinterpret_cast<S *>(args.snap)[j] = r;
+        const int64_t tail = n / Ops::PER * Ops::PER;
+        if (blk == 0 && threadIdx.x < n - tail) {
+            const int64_t j = tail + threadIdx.x;
+            const S t = Ops::lerp_s(a, b, *reinterpret_cast<const S *>(src.at(j * (int64_t)sizeof(S))), ps[j]);
+            if (!OOP) ps[j] = t;
+            if (DUAL) reinterpret_cast<S *>(args.snap)[j] = t;
+        }
     }
 }
 
@@ -468,57 +541,40 @@ __device__ __forceinline__ int32_t seg_dtype(const SegTable &t, int64_t off)
     return d;
 }
 
+// The element op of a segmented payload's span: OpsF32 / OpsBF16 / OpsF16 ::lerp, so each type
+// rounds exactly as its own kernel, chosen under a uniform branch by the type of the segment the
+// span lies in (looked up here, after the span's loads were issued).  No ragged tail: n counts
+// the payload's bytes, a multiple of 4 KiB.
+struct OpsMixed {
+    using V = u32x4;
+    static constexpr int PER = 16;
+    static constexpr bool TAIL = false;
+    const SegTable &segs;
+    int64_t span_off;
+    __device__ __forceinline__ V lerp(float a, float b, V q, V p) const
+    {
+        const int32_t dtype = seg_dtype(segs, span_off);
+        if (dtype == DPWA_F32)
+            return __builtin_bit_cast(V, OpsF32::lerp(a, b, __builtin_bit_cast(f32x4, q), __builtin_bit_cast(f32x4, p)));
+        if (dtype == DPWA_BF16) return OpsBF16::lerp(a, b, q, p);
+        return OpsF16::lerp(a, b, q, p);
+    }
+};
+
 // The single-dtype span code (lerp_span: one 16-byte item per lane, loads first, the fp64 factor
-// by every lane while they are in flight, the commit by one lane of the grid, the no-op round)
-// for a segmented payload: the span's element op -- OpsF32 / OpsBF16 / OpsF16 ::lerp, so each
-// type rounds exactly as its own kernel -- is chosen under a uniform branch by the span's byte
-// offset (not by the workgroup index: right for any span order).  No ragged tail and no
-// unaligned form: `total` is a multiple of 4 KiB and the grid is exact.  One-wave workgroups.
+// by every lane while they are in flight, the commit by one lane of the grid -- of global
+// workgroup 0, not of the first workgroup of each segment -- and the no-op round) for a
+// segmented payload: the span's element op is chosen by the span's byte offset (not by the
+// workgroup index: right for any span order).  No unaligned form, and the grid is exact.
+// One-wave workgroups.
 template <int MODE, bool DUAL, int POLICY, bool OOP>
 __global__ __launch_bounds__(kStreamBlock) void k_lerp_mixed(u32x4 *__restrict__ param,
                                                              const u32x4 *__restrict__ peer, int64_t total,
                                                              LerpArgs args, SegTable segs)
 {
-    using V = u32x4;
-    constexpr int SPAN = kStreamBlock * 16;
     const ContigSrc src{(const char *)peer};
-    const uint32_t blk = blockIdx.x;
-    const int64_t span_off = src.template span_of<SPAN>(blk);
-    const int lane_off = threadIdx.x * 16;
-    const __amdgpu_buffer_rsrc_t rq = span_rsrc<SPAN>(src.span_base(span_off), span_off, total);
-    const __amdgpu_buffer_rsrc_t rp = span_rsrc<SPAN>(param, span_off, total);
-    // issue this lane's loads before anything else
-    const V q = span_load<V>(rq, lane_off);
-    const V p = span_load<V, LerpPolicy<POLICY>::param_load>(rp, lane_off);
-    const int32_t dtype = seg_dtype(segs, span_off);
-    float a, b;
-    if (MODE == COEF_DEV) {
-        if (args.coef->status != DPWA_STATUS_OK) return;
-        a = args.coef->a;
-        b = args.coef->b;
-    } else {
-        // every lane evaluates the (uniform) fp64 factor while the loads are in flight; global
-        // workgroup 0 -- not the first workgroup of each segment -- commits it, once
-        const FusedArgs &fa = args.fused;
-        const double loss = read_loss(fa.loss_d, fa.loss_f32, fa.loss_h);
-        const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss, loss);
-        if (blk == 0 && threadIdx.x == 0) factor_commit(fa, c);
-        a = c.a;
-        b = c.b;
-        if (c.status != DPWA_STATUS_OK) {   // no-op round; a write-through snapshot still gets the parameters
-            if (DUAL) span_store<V, LerpPolicy<POLICY>::snap_store>(span_rsrc<SPAN>(args.snap, span_off, total), lane_off, p);
-            return;
-        }
-    }
-    V r;
-    if (dtype == DPWA_F32)
-        r = __builtin_bit_cast(V, OpsF32::lerp(a, b, __builtin_bit_cast(f32x4, q), __builtin_bit_cast(f32x4, p)));
-    else if (dtype == DPWA_BF16)
-        r = OpsBF16::lerp(a, b, q, p);
-    else
-        r = OpsF16::lerp(a, b, q, p);
-    if (!OOP) span_store<V, LerpPolicy<POLICY>::store>(rp, lane_off, r);
-    if (DUAL) span_store<V, LerpPolicy<POLICY>::snap_store>(span_rsrc<SPAN>(args.snap, span_off, total), lane_off, r);
+    const OpsMixed ops{segs, src.span_of<kStreamBlock * 16>(blockIdx.x)};
+    lerp_span<OpsMixed, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP>(blockIdx.x, param, src, total, args, ops);
 }
 
 // The relay's fused second phase: the fused average reads the peer's snapshot stripe by stripe
@@ -604,34 +660,13 @@ __device__ __forceinline__ void group_span(const AvgBatch &batch)
     // live at a time
     float fa_[U], fb_[U];
     bool ok_[U];
-    if (DPWA_GROUP_FACTORS_FIRST) {
-#pragma unroll
-        for (int i = 0; i < U; ++i) {
-            if (i >= G) break;
-            const FusedArgs &fa = batch.e[i].fa;
-            const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss,
-                                            read_loss(fa.loss_d, fa.loss_f32, fa.loss_h));
-            if (blk == 0 && threadIdx.x == 0) factor_commit(fa, c);
-            fa_[i] = c.a;
-            fb_[i] = c.b;
-            ok_[i] = c.status == DPWA_STATUS_OK;
-        }
-    }
 #pragma unroll
     for (int i = 0; i < U; ++i) {
         if (i >= G) break;
-        dpwa_coef c;
-        if (DPWA_GROUP_FACTORS_FIRST) {
-            c.a = fa_[i];
-            c.b = fb_[i];
-        } else {
-            const FusedArgs &fa = batch.e[i].fa;
-            c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss, read_loss(fa.loss_d, fa.loss_f32, fa.loss_h));
-            if (blk == 0 && threadIdx.x == 0) factor_commit(fa, c);
-            fa_[i] = c.a;
-            fb_[i] = c.b;
-            ok_[i] = c.status == DPWA_STATUS_OK;
-        }
+        const dpwa_coef c = fused_factor(batch.e[i].fa, blk == 0 && threadIdx.x == 0);
+        fa_[i] = c.a;
+        fb_[i] = c.b;
+        ok_[i] = c.status == DPWA_STATUS_OK;
         const int k = batch.peer_of[i];   // uniform: a select over registers, no indexed access
         V q = v[0];
 #pragma unroll
@@ -678,31 +713,14 @@ __global__ __launch_bounds__(kBlock) void k_lerp_unaligned(typename Ops::S *__re
                                                            const typename Ops::S *__restrict__ peer, int64_t n,
                                                            LerpArgs args)
 {
-    float a, b;
-    if (MODE == COEF_HOST) {
-        a = args.a;
-        b = args.b;
-    } else if (MODE == COEF_DEV) {
-        if (args.coef->status != DPWA_STATUS_OK) return;
-        a = args.coef->a;
-        b = args.coef->b;
-    } else {
-        const FusedArgs &fa = args.fused;
-        const double loss = read_loss(fa.loss_d, fa.loss_f32, fa.loss_h);
-        const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss, loss);
-        if (blockIdx.x == 0 && threadIdx.x == 0) factor_commit(fa, c);
-        if (c.status != DPWA_STATUS_OK) {
-            if (DUAL) {
-                const int64_t stride = (int64_t)gridDim.x * kBlock;
-                for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-                    reinterpret_cast<typename Ops::S *>(args.snap)[i] = param[i];
-            }
-            return;
-        }
-        a = c.a;
-        b = c.b;
-    }
     const int64_t stride = (int64_t)gridDim.x * kBlock;
+    float a, b;
+    if (!lerp_coef<MODE>(args, blockIdx.x == 0, a, b)) {   // every lane evaluates a fused factor
+        if (MODE == COEF_FUSED && DUAL)
+            for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+                reinterpret_cast<typename Ops::S *>(args.snap)[i] = param[i];
+        return;
+    }
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const typename Ops::S r = Ops::lerp_s(a, b, peer[i], param[i]);
         param[i] = r;
@@ -712,102 +730,125 @@ __global__ __launch_bounds__(kBlock) void k_lerp_unaligned(typename Ops::S *__re
 
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
+// ---------------------------------------------------------------- tuning knobs
 // Workgroup size of the averaging kernel; DPWA_LERP_BLOCK (64/128/256/512) forces another
 // (tuning).
 static int lerp_block()
 {
-    static const int forced = [] {
-        const char *e = getenv("DPWA_LERP_BLOCK");
-        const int b = e ? atoi(e) : 0;
-        return (b == 64 || b == 128 || b == 256 || b == 512) ? b : 0;
-    }();
-    return forced ? forced : kStreamBlock;
-}
-
-template <class Ops, int MODE, bool DUAL, int BLOCK, int POLICY = 0>
-static hipError_t launch_blocks(void *param, const void *peer, int64_t n, const LerpArgs &args, hipStream_t s,
-                                const LaunchTiming *timing)
-{
-    const int64_t g = (n / Ops::PER) / BLOCK + 1;   // the last span may be empty (range-checked)
-    if (timing)   // the dispatch itself is timed (the kernel's begin/end, as a profiler sees it)
-        hipExtLaunchKernelGGL((k_lerp<Ops, MODE, DUAL, BLOCK, POLICY>), dim3((uint32_t)g), dim3(BLOCK), 0, s,
-                              timing->start, timing->stop, 0, (typename Ops::V *)param,
-                              (const typename Ops::V *)peer, n, args);
-    else
-        hipLaunchKernelGGL((k_lerp<Ops, MODE, DUAL, BLOCK, POLICY>), dim3((uint32_t)g), dim3(BLOCK), 0, s,
-                           (typename Ops::V *)param, (const typename Ops::V *)peer, n, args);
-    return hipGetLastError();
+    static const int block =
+        env_knob("DPWA_LERP_BLOCK", kStreamBlock, [](const char *e) { return one_of(atoi(e), {64, 128, 256, 512}); });
+    return block;
 }
 
 // The product policy is 8 (parameters stored `nt`, the snapshot `sc1`): with the batched
 // dispatch it lifts every cold averaging kernel by 1-3 % of peak (11.17M batched 0.78 -> 0.80-0.81,
 // 7B bf16 full 0.81 -> 0.82) and leaves the N=1 loop within noise (-0.4 %, two interleaved passes
 // with sweeps, profiles/r03_policy_ab.log).  Round 2's one-launch-per-learner loop lost 2-5 % with it
-// (profiles/r02_policy_ab2.json).  DPWA_LERP_POLICY overrides (tuning).
+// (profiles/r02_policy_ab2.json).  DPWA_LERP_POLICY (0..31) requests another (tuning); what a
+// requested value launches depends on the form, see the table below.
 constexpr int kProductPolicy = 8;
 
 static int lerp_policy()
 {
-    static const int forced = [] {
-        const char *e = getenv("DPWA_LERP_POLICY");
-        const int p = e ? atoi(e) : kProductPolicy;
-        return (p >= 0 && p <= 31) ? p : kProductPolicy;
-    }();
-    return forced;
+    static const int policy = env_knob("DPWA_LERP_POLICY", kProductPolicy, [](const char *e) {
+        const int p = atoi(e);
+        return p >= 0 && p <= 31 ? p : kNoValue;
+    });
+    return policy;
 }
+
+// Span order of a batched dispatch of equal-size entries.  Dealt round-robin, every span is
+// re-read by the next round's dispatch one round after it was written, which keeps the re-reads
+// in the 256 MiB Infinity Cache while a round writes less than that; one entry after the other,
+// half the re-reads come 1.5 rounds after their write.  Measured (profiles/r03_batch_order_ab.log,
+// three interleaved pairs): round-robin +2.8 % at 11.17M fp32 (179 MB written per round), -4 %
+// at 100M fp32 (1.6 GB: twice the concurrent streams, no cache to win).  DPWA_BATCH_ORDER=
+// interleaved / contiguous forces one (1 / 0; -1: by size).
+constexpr size_t kInfinityCacheBytes = (size_t)256 << 20;
+
+static int batch_order()
+{
+    static const int order = env_knob("DPWA_BATCH_ORDER", -1, [](const char *e) {
+        return strcmp(e, "contiguous") == 0 ? 0 : strcmp(e, "interleaved") == 0 ? 1 : kNoValue;
+    });
+    return order;
+}
+
+// (a switch that only "0" turns off)
+static int off_when_0(const char *e) { return strcmp(e, "0") == 0 ? 0 : kNoValue; }
+
+// XCD-grouped span order for resident batches whose entries share a read (k_lerp_batch);
+// DPWA_BATCH_SHARE=0 turns it off (A/B runs).  tools/pair_tune.hip: two 11.17M fp32 resident
+// learners averaging with each other, 36.8 -> 25-27 us per dispatch in the gossip loop, 41.3 ->
+// 28.5 us cold (a fused one-workgroup form of both averages: 25.6 / 28.5).
+static bool batch_share()
+{
+    static const bool on = env_knob("DPWA_BATCH_SHARE", 1, off_when_0) != 0;
+    return on;
+}
+
+// A closed resident group runs as k_lerp_pair / k_lerp_group (one workgroup per span for all its
+// averages); DPWA_PAIR_FUSED=0 keeps it on the XCD-grouped batch (A/B runs).
+static bool pair_fused()
+{
+    static const bool on = env_knob("DPWA_PAIR_FUSED", 1, off_when_0) != 0;
+    return on;
+}
+
+// ---------------------------------------------------------------- the policy table
+// Which cache policy (LerpPolicy) each averaging form launches for a requested one
+// (lerp_policy()): the listed values as themselves, every other value as the fallback, which
+// comes first.  These are the instantiated kernels; the launchers below pick through these
+// types, so the table is what runs.
+using Lerp64Policies = Choice<0, 1, 2, 3, 4, 5, 8, 9, 10, 16>;   // k_lerp, 64 lanes, not resident
+using LerpWidePolicies = Choice<0, 8>;                           // k_lerp, 128 / 256 / 512 lanes (tuning sizes)
+// the resident kernels store only the next slot, so their store policy is the snapshot one: bit
+// 16 makes it `nt`, bit 1 loads the parameters with the default policy
+using ResidentPolicies = Choice<kProductPolicy, 0, 1, 2, 16, 17>;   // k_lerp and k_lerp_batch, resident (OOP)
+using BatchPolicies = Choice<0, 1, 2, 8, 9, 10, 16>;                // k_lerp_batch, not resident
+// the pair's two loads both take the parameter load's policy (each slot is one entry's parameters
+// and the other's peer)
+using PairF32Policies = Choice<kProductPolicy, 0, 1, 2, 16>;   // k_lerp_pair, float32
+using Pair16Policies = Choice<kProductPolicy, 0>;              // k_lerp_pair, bfloat16 / float16
+using GroupPolicies = Choice<kProductPolicy, 0>;               // k_lerp_group
+using RelayPolicies = Choice<0, 8>;                            // k_lerp_relay
+using FixedPolicy = Choice<kProductPolicy>;                    // k_lerp_mixed, k_stream_mix: the knob is ignored
+
+template <class Policies, int... Ps> constexpr bool launches_as_itself() { return ((Policies::launched(Ps) == Ps) && ...); }
+static_assert(launches_as_itself<Lerp64Policies, 1, 2, 3, 4, 5, 8, 9, 10, 16>() && Lerp64Policies::launched(6) == 0);
+static_assert(launches_as_itself<LerpWidePolicies, 8>() && LerpWidePolicies::launched(1) == 0);
+static_assert(launches_as_itself<ResidentPolicies, 0, 1, 2, 16, 17>() && ResidentPolicies::launched(9) == 8 &&
+              ResidentPolicies::launched(8) == 8);
+static_assert(launches_as_itself<BatchPolicies, 1, 2, 8, 9, 10, 16>() && BatchPolicies::launched(3) == 0);
+static_assert(launches_as_itself<PairF32Policies, 0, 1, 2, 16>() && PairF32Policies::launched(17) == 8 &&
+              PairF32Policies::launched(8) == 8);
+static_assert(launches_as_itself<Pair16Policies, 0>() && Pair16Policies::launched(1) == 8 && Pair16Policies::launched(8) == 8);
+static_assert(launches_as_itself<GroupPolicies, 0>() && GroupPolicies::launched(16) == 8 && GroupPolicies::launched(8) == 8);
+static_assert(launches_as_itself<RelayPolicies, 8>() && RelayPolicies::launched(9) == 0);
+static_assert(FixedPolicy::launched(0) == 8 && FixedPolicy::launched(8) == 8);
+
+// ---------------------------------------------------------------- averaging launches
+// Workgroups of one 16-byte item per lane over n elements; the last span may be empty
+// (range-checked).
+template <class Ops> static int64_t span_grid(int64_t n, int block) { return (n / Ops::PER) / block + 1; }
 
 template <class Ops, int MODE, bool DUAL>
 static hipError_t launch_mode(void *param, const void *peer, int64_t n, const LerpArgs &args, hipStream_t s,
                               const LaunchTiming *timing)
 {
-    if (aligned16(param) && aligned16(peer) && aligned16(args.snap)) {
-        switch (lerp_block()) {
-        case 64:
-            switch (lerp_policy()) {
-            case 1: return launch_blocks<Ops, MODE, DUAL, 64, 1>(param, peer, n, args, s, timing);
-            case 2: return launch_blocks<Ops, MODE, DUAL, 64, 2>(param, peer, n, args, s, timing);
-            case 3: return launch_blocks<Ops, MODE, DUAL, 64, 3>(param, peer, n, args, s, timing);
-            case 4: return launch_blocks<Ops, MODE, DUAL, 64, 4>(param, peer, n, args, s, timing);
-            case 5: return launch_blocks<Ops, MODE, DUAL, 64, 5>(param, peer, n, args, s, timing);
-            case 8: return launch_blocks<Ops, MODE, DUAL, 64, 8>(param, peer, n, args, s, timing);
-            case 9: return launch_blocks<Ops, MODE, DUAL, 64, 9>(param, peer, n, args, s, timing);
-            case 16: return launch_blocks<Ops, MODE, DUAL, 64, 16>(param, peer, n, args, s, timing);
-            case 10: return launch_blocks<Ops, MODE, DUAL, 64, 10>(param, peer, n, args, s, timing);
-            case 40: return launch_blocks<Ops, MODE, DUAL, 64, 40>(param, peer, n, args, s, timing);
-            default: return launch_blocks<Ops, MODE, DUAL, 64>(param, peer, n, args, s, timing);
-            }
-        // (tuning sizes: the product policy, or policy 0 when DPWA_LERP_POLICY says so)
-        case 128:
-            return lerp_policy() == kProductPolicy
-                       ? launch_blocks<Ops, MODE, DUAL, 128, kProductPolicy>(param, peer, n, args, s, timing)
-                       : launch_blocks<Ops, MODE, DUAL, 128>(param, peer, n, args, s, timing);
-        case 512:
-            return lerp_policy() == kProductPolicy
-                       ? launch_blocks<Ops, MODE, DUAL, 512, kProductPolicy>(param, peer, n, args, s, timing)
-                       : launch_blocks<Ops, MODE, DUAL, 512>(param, peer, n, args, s, timing);
-        default:
-            return lerp_policy() == kProductPolicy
-                       ? launch_blocks<Ops, MODE, DUAL, 256, kProductPolicy>(param, peer, n, args, s, timing)
-                       : launch_blocks<Ops, MODE, DUAL, 256>(param, peer, n, args, s, timing);
-        }
-    } else {
+    if (!aligned16(param) || !aligned16(peer) || !aligned16(args.snap)) {
         // (callers time only the aligned product kernel; an unaligned launch is not timed)
-        int64_t g = blocks_for(n);
-        if (g > 8192) g = 8192;
-        hipLaunchKernelGGL((k_lerp_unaligned<Ops, MODE, DUAL>), dim3((uint32_t)g), dim3(kBlock), 0, s,
-                           (typename Ops::S *)param, (const typename Ops::S *)peer, n, args);
+        return launch(k_lerp_unaligned<Ops, MODE, DUAL>, dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)),
+                      dim3(kBlock), s, nullptr, param, peer, n, args);
     }
-    return hipGetLastError();
-}
-
-template <class Ops>
-static hipError_t launch_ops(int mode, void *param, const void *peer, int64_t n, const LerpArgs &args, hipStream_t s,
-                             const LaunchTiming *t)
-{
-    if (mode == COEF_HOST) return launch_mode<Ops, COEF_HOST, false>(param, peer, n, args, s, t);
-    if (mode == COEF_DEV) return launch_mode<Ops, COEF_DEV, false>(param, peer, n, args, s, t);
-    if (args.snap) return launch_mode<Ops, COEF_FUSED, true>(param, peer, n, args, s, t);
-    return launch_mode<Ops, COEF_FUSED, false>(param, peer, n, args, s, t);
+    return Choice<256, 64, 128, 512>::with(lerp_block(), [&](auto block) {
+        constexpr int BLOCK = decltype(block)::value;
+        using Policies = std::conditional_t<BLOCK == 64, Lerp64Policies, LerpWidePolicies>;
+        return Policies::with(lerp_policy(), [&](auto policy) {
+            return launch(k_lerp<Ops, MODE, DUAL, BLOCK, decltype(policy)::value>, dim3((uint32_t)span_grid<Ops>(n, BLOCK)),
+                          dim3(BLOCK), s, timing, param, peer, n, args);
+        });
+    });
 }
 
 static hipError_t launch_any(int32_t dtype, int mode, void *param, const void *peer, int64_t n, const LerpArgs &args,
@@ -815,10 +856,13 @@ static hipError_t launch_any(int32_t dtype, int mode, void *param, const void *p
 {
     if (n < 0) return hipErrorInvalidValue;
     if (n == 0 && mode != COEF_FUSED) return hipSuccess;
-    if (dtype == DPWA_F32) return launch_ops<OpsF32>(mode, param, peer, n, args, s, t);
-    if (dtype == DPWA_BF16) return launch_ops<OpsBF16>(mode, param, peer, n, args, s, t);
-    if (dtype == DPWA_F16) return launch_ops<OpsF16>(mode, param, peer, n, args, s, t);
-    return hipErrorInvalidValue;
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        if (mode == COEF_HOST) return launch_mode<Ops, COEF_HOST, false>(param, peer, n, args, s, t);
+        if (mode == COEF_DEV) return launch_mode<Ops, COEF_DEV, false>(param, peer, n, args, s, t);
+        if (args.snap) return launch_mode<Ops, COEF_FUSED, true>(param, peer, n, args, s, t);
+        return launch_mode<Ops, COEF_FUSED, false>(param, peer, n, args, s, t);
+    });
 }
 
 hipError_t launch_lerp(int32_t dtype, void *param, const void *peer, int64_t n, const dpwa_coef *coef, float a,
@@ -831,52 +875,22 @@ hipError_t launch_lerp(int32_t dtype, void *param, const void *peer, int64_t n, 
     return launch_any(dtype, coef ? COEF_DEV : COEF_HOST, param, peer, n, args, s);
 }
 
-// The resident form (OOP): one-wave workgroups, the product cache policy unless 0 is forced.
-template <class Ops, int POLICY>
-static hipError_t launch_oop_policy(void *param, const void *peer, int64_t n, const LerpArgs &args, hipStream_t s,
-                                    const LaunchTiming *timing)
-{
-    const int64_t g = (n / Ops::PER) / kStreamBlock + 1;
-    if (timing)
-        hipExtLaunchKernelGGL((k_lerp<Ops, COEF_FUSED, true, kStreamBlock, POLICY, true>), dim3((uint32_t)g),
-                              dim3(kStreamBlock), 0, s, timing->start, timing->stop, 0, (typename Ops::V *)param,
-                              (const typename Ops::V *)peer, n, args);
-    else
-        hipLaunchKernelGGL((k_lerp<Ops, COEF_FUSED, true, kStreamBlock, POLICY, true>), dim3((uint32_t)g),
-                           dim3(kStreamBlock), 0, s, (typename Ops::V *)param, (const typename Ops::V *)peer, n, args);
-    return hipGetLastError();
-}
-
-// (the resident kernel stores only the next slot, so its store policy is the snapshot one: bit 16
-// makes it `nt`, bit 1 loads the parameters with the default policy; tuning variants)
-template <class Ops>
-static hipError_t launch_oop(void *param, const void *peer, int64_t n, const LerpArgs &args, hipStream_t s,
-                             const LaunchTiming *timing)
-{
-    switch (lerp_policy()) {
-    case 0: return launch_oop_policy<Ops, 0>(param, peer, n, args, s, timing);
-    case 1: return launch_oop_policy<Ops, 1>(param, peer, n, args, s, timing);
-    case 2: return launch_oop_policy<Ops, 2>(param, peer, n, args, s, timing);
-    case 16: return launch_oop_policy<Ops, 16>(param, peer, n, args, s, timing);
-    case 17: return launch_oop_policy<Ops, 17>(param, peer, n, args, s, timing);
-    default: return launch_oop_policy<Ops, kProductPolicy>(param, peer, n, args, s, timing);
-    }
-}
-
 hipError_t launch_average(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa, void *snap,
                           hipStream_t s, const LaunchTiming *timing, bool oop)
 {
     LerpArgs args{};
     args.fused = fa;
     args.snap = snap;
-    if (oop) {   // resident: 16-B aligned slot payloads only
-        if (n < 0 || (!snap && n > 0) || !aligned16(param) || !aligned16(peer) || !aligned16(snap)) return hipErrorInvalidValue;
-        if (dtype == DPWA_F32) return launch_oop<OpsF32>(param, peer, n, args, s, timing);
-        if (dtype == DPWA_BF16) return launch_oop<OpsBF16>(param, peer, n, args, s, timing);
-        if (dtype == DPWA_F16) return launch_oop<OpsF16>(param, peer, n, args, s, timing);
-        return hipErrorInvalidValue;
-    }
-    return launch_any(dtype, COEF_FUSED, param, peer, n, args, s, timing);
+    if (!oop) return launch_any(dtype, COEF_FUSED, param, peer, n, args, s, timing);
+    // resident: 16-B aligned slot payloads only, one-wave workgroups
+    if (n < 0 || (!snap && n > 0) || !aligned16(param) || !aligned16(peer) || !aligned16(snap)) return hipErrorInvalidValue;
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        return ResidentPolicies::with(lerp_policy(), [&](auto policy) {
+            return launch(k_lerp<Ops, COEF_FUSED, true, kStreamBlock, decltype(policy)::value, true>,
+                          dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, timing, param, peer, n, args);
+        });
+    });
 }
 
 const char *layout_problem(const dpwa_layout &layout, int64_t total_bytes)
@@ -917,13 +931,8 @@ static hipError_t launch_mixed(const dpwa_layout &layout, void *param, const voi
     const int64_t total = layout_bytes(layout);
     const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
     if (g > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (timing)
-        hipExtLaunchKernelGGL((k_lerp_mixed<MODE, DUAL, kProductPolicy, OOP>), dim3((uint32_t)g), dim3(kStreamBlock), 0,
-                              s, timing->start, timing->stop, 0, (u32x4 *)param, (const u32x4 *)peer, total, args, t);
-    else
-        hipLaunchKernelGGL((k_lerp_mixed<MODE, DUAL, kProductPolicy, OOP>), dim3((uint32_t)g), dim3(kStreamBlock), 0, s,
-                           (u32x4 *)param, (const u32x4 *)peer, total, args, t);
-    return hipGetLastError();
+    return launch(k_lerp_mixed<MODE, DUAL, FixedPolicy::launched(kProductPolicy), OOP>, dim3((uint32_t)g),
+                  dim3(kStreamBlock), s, timing, param, peer, total, args, t);
 }
 
 hipError_t launch_lerp_mixed(const dpwa_layout &layout, void *param, const void *peer, const dpwa_coef *coef,
@@ -946,50 +955,6 @@ hipError_t launch_average_mixed(const dpwa_layout &layout, void *param, const vo
     return launch_mixed<COEF_FUSED, false, false>(layout, param, peer, args, s, timing);
 }
 
-// Span order of a batched dispatch of equal-size entries.  Dealt round-robin, every span is
-// re-read by the next round's dispatch one round after it was written, which keeps the re-reads
-// in the 256 MiB Infinity Cache while a round writes less than that; one entry after the other,
-// half the re-reads come 1.5 rounds after their write.  Measured (profiles/r03_batch_order_ab.log,
-// three interleaved pairs): round-robin +2.8 % at 11.17M fp32 (179 MB written per round), -4 %
-// at 100M fp32 (1.6 GB: twice the concurrent streams, no cache to win).  DPWA_BATCH_ORDER=
-// interleaved / contiguous forces one.
-constexpr size_t kInfinityCacheBytes = (size_t)256 << 20;
-
-static int batch_order()
-{
-    static const int forced = [] {
-        const char *e = getenv("DPWA_BATCH_ORDER");
-        if (e && strcmp(e, "contiguous") == 0) return 0;
-        if (e && strcmp(e, "interleaved") == 0) return 1;
-        return -1;
-    }();
-    return forced;
-}
-
-// XCD-grouped span order for resident batches whose entries share a read (k_lerp_batch);
-// DPWA_BATCH_SHARE=0 turns it off (A/B runs).  tools/pair_tune.hip: two 11.17M fp32 resident
-// learners averaging with each other, 36.8 -> 25-27 us per dispatch in the gossip loop, 41.3 ->
-// 28.5 us cold (a fused one-workgroup form of both averages: 25.6 / 28.5).
-static bool batch_share()
-{
-    static const bool on = [] {
-        const char *e = getenv("DPWA_BATCH_SHARE");
-        return !(e && strcmp(e, "0") == 0);
-    }();
-    return on;
-}
-
-// A closed resident group runs as k_lerp_pair / k_lerp_group (one workgroup per span for all its
-// averages); DPWA_PAIR_FUSED=0 keeps it on the XCD-grouped batch (A/B runs).
-static bool pair_fused()
-{
-    static const bool on = [] {
-        const char *e = getenv("DPWA_PAIR_FUSED");
-        return !(e && strcmp(e, "0") == 0);
-    }();
-    return on;
-}
-
 // Some buffer is read by two entries (as parameters or as the peer snapshot).
 static bool shares_a_read(const AvgBatch &x)
 {
@@ -1000,43 +965,38 @@ static bool shares_a_read(const AvgBatch &x)
     return false;
 }
 
-hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hipStream_t s,
-                                 const LaunchTiming *timing, bool oop)
+template <class Ops>
+static hipError_t average_batch(bool dual, const AvgBatch &b, hipStream_t s, const LaunchTiming *timing, bool oop)
 {
-    if (b.count < 1 || b.count > kMaxAvgBatch || (oop && !dual)) return hipErrorInvalidValue;
     AvgBatch x = b;
-    uint32_t g = 0;
-    const int per = dtype == DPWA_F32 ? OpsF32::PER : dtype == DPWA_BF16 ? OpsBF16::PER : dtype == DPWA_F16 ? OpsF16::PER : 0;
-    if (!per) return hipErrorInvalidValue;
     for (int i = 0; i < x.count; ++i) {
         const AvgEntry &e = x.e[i];
         if (e.n < 0 || !aligned16(e.param) || !aligned16(e.peer) || (!dual && e.snap) || (dual && !e.snap && e.n > 0) ||
             !aligned16(e.snap))
             return hipErrorInvalidValue;
-        const int64_t gi = (e.n / per) / kStreamBlock + 1;   // as launch_blocks: last span may be empty
-        if (gi > 0x7fffffffLL) return hipErrorInvalidValue;
+        if (span_grid<Ops>(e.n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
     }
     int64_t total = 0;   // in 64 bits: up to 8 entries of up to 2^31 - 1 workgroups each
     for (int i = 0; i < x.count; ++i) {
         x.begin[i] = (uint32_t)total;
-        total += (x.e[i].n / per) / kStreamBlock + 1;
+        total += span_grid<Ops>(x.e[i].n, kStreamBlock);
         if (total > 0x7fffffffLL) return hipErrorInvalidValue;
     }
-    g = (uint32_t)total;
+    uint32_t g = (uint32_t)total;
     for (int i = x.count; i < kMaxAvgBatch; ++i) x.begin[i] = 0xffffffffu;
     // span order: see batch_order()
     bool same = true;
     size_t written = 0;
     for (int i = 0; i < x.count; ++i) {
         same = same && x.e[i].n == x.e[0].n;
-        written += (size_t)x.e[i].n * (size_t)(per == OpsF32::PER ? 4 : 2) * (dual && !oop ? 2 : 1);
+        written += (size_t)x.e[i].n * sizeof(typename Ops::S) * (dual && !oop ? 2 : 1);
     }
     const int order = batch_order();
     x.interleave = same && x.count > 1 && (order == 1 || (order < 0 && written <= kInfinityCacheBytes)) ? 1 : 0;
     // resident entries of equal size that read a common buffer (a learner's published slot is its
     // own parameters and another's peer): XCD-grouped, whatever the size (nothing writes what they
     // read, so any order is safe)
-    x.spans = (uint32_t)((x.e[0].n / per) / kStreamBlock + 1);
+    x.spans = (uint32_t)span_grid<Ops>(x.e[0].n, kStreamBlock);
     // a group: entries of equal size, distinct parameters, whose reads overlap; its sources are
     // the parameters, then the peers that are no entry's parameters (at most kMaxAvgBatch)
     bool grouped = oop && same && x.count > 1 && order < 0 && batch_share() && pair_fused();
@@ -1062,72 +1022,19 @@ hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hip
     }
     grouped = grouped && nsrc < 2 * x.count;   // some read is shared
     for (int j = nsrc; j < kMaxAvgBatch; ++j) x.src[j] = nullptr;
-    const bool closed = grouped && nsrc == 2 && x.count == 2;   // the mutual pair
-    if (grouped && !closed) {
-#define DPWA_GROUP_LAUNCH(OPS, P, G)                                                                         \
-    do {                                                                                                    \
-        if (timing)                                                                                         \
-            hipExtLaunchKernelGGL((k_lerp_group<OPS, P, G>), dim3(x.spans), dim3(kStreamBlock), 0, s,        \
-                                  timing->start, timing->stop, 0, x);                                       \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_lerp_group<OPS, P, G>), dim3(x.spans), dim3(kStreamBlock), 0, s, x);     \
-    } while (0)
-#define DPWA_GROUP_G(OPS, P)                                                                                 \
-    do {                                                                                                    \
-        switch (nsrc) {                                                                                     \
-        case 3: DPWA_GROUP_LAUNCH(OPS, P, 3); break;                                                        \
-        case 4: DPWA_GROUP_LAUNCH(OPS, P, 4); break;                                                        \
-        case 5: DPWA_GROUP_LAUNCH(OPS, P, 5); break;                                                        \
-        case 6: DPWA_GROUP_LAUNCH(OPS, P, 6); break;                                                        \
-        case 7: DPWA_GROUP_LAUNCH(OPS, P, 7); break;                                                        \
-        default: DPWA_GROUP_LAUNCH(OPS, P, 8); break;                                                       \
-        }                                                                                                   \
-    } while (0)
-        const bool p0 = lerp_policy() == 0;
-        if (dtype == DPWA_F32) {
-            if (p0) DPWA_GROUP_G(OpsF32, 0);
-            else DPWA_GROUP_G(OpsF32, kProductPolicy);
-        } else if (dtype == DPWA_BF16) {
-            if (p0) DPWA_GROUP_G(OpsBF16, 0);
-            else DPWA_GROUP_G(OpsBF16, kProductPolicy);
-        } else {
-            if (p0) DPWA_GROUP_G(OpsF16, 0);
-            else DPWA_GROUP_G(OpsF16, kProductPolicy);
-        }
-#undef DPWA_GROUP_G
-#undef DPWA_GROUP_LAUNCH
-        return hipGetLastError();
+    const auto run = [&](void (*kernel)(AvgBatch), uint32_t grid) {
+        return launch(kernel, dim3(grid), dim3(kStreamBlock), s, timing, x);
+    };
+    if (grouped && nsrc == 2 && x.count == 2) {   // the mutual pair: both averages in one workgroup per span
+        using Policies = std::conditional_t<std::is_same_v<Ops, OpsF32>, PairF32Policies, Pair16Policies>;
+        return Policies::with(lerp_policy(), [&](auto policy) { return run(k_lerp_pair<Ops, decltype(policy)::value>, x.spans); });
     }
-    if (closed) {
-        // a mutual pair: both averages in one workgroup per span
-#define DPWA_PAIR_LAUNCH(OPS, P)                                                                             \
-    do {                                                                                                    \
-        if (timing)                                                                                         \
-            hipExtLaunchKernelGGL((k_lerp_pair<OPS, P>), dim3(x.spans), dim3(kStreamBlock), 0, s,            \
-                                  timing->start, timing->stop, 0, x);                                       \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_lerp_pair<OPS, P>), dim3(x.spans), dim3(kStreamBlock), 0, s, x);         \
-    } while (0)
-        // cache-policy variants for tuning (DPWA_LERP_POLICY); both loads take the parameter load's
-        // policy (each slot is one entry's parameters and the other's peer)
-        if (dtype == DPWA_F32) {
-            switch (lerp_policy()) {
-            case 0: DPWA_PAIR_LAUNCH(OpsF32, 0); break;
-            case 1: DPWA_PAIR_LAUNCH(OpsF32, 1); break;
-            case 2: DPWA_PAIR_LAUNCH(OpsF32, 2); break;
-            case 16: DPWA_PAIR_LAUNCH(OpsF32, 16); break;
-            case 32: DPWA_PAIR_LAUNCH(OpsF32, 32); break;
-            default: DPWA_PAIR_LAUNCH(OpsF32, kProductPolicy); break;
-            }
-        } else if (dtype == DPWA_BF16) {
-            if (lerp_policy() == 0) DPWA_PAIR_LAUNCH(OpsBF16, 0);
-            else DPWA_PAIR_LAUNCH(OpsBF16, kProductPolicy);
-        } else {
-            if (lerp_policy() == 0) DPWA_PAIR_LAUNCH(OpsF16, 0);
-            else DPWA_PAIR_LAUNCH(OpsF16, kProductPolicy);
-        }
-#undef DPWA_PAIR_LAUNCH
-        return hipGetLastError();
+    if (grouped) {   // 3..8 source buffers
+        return GroupPolicies::with(lerp_policy(), [&](auto policy) {
+            return Choice<8, 3, 4, 5, 6, 7>::with(nsrc, [&](auto u) {
+                return run(k_lerp_group<Ops, decltype(policy)::value, decltype(u)::value>, x.spans);
+            });
+        });
     }
     if (oop && same && x.count > 1 && order < 0 && batch_share() && shares_a_read(x)) {
         const uint64_t gg = (uint64_t)(x.spans + 7) / 8 * 8 * (uint64_t)x.count;
@@ -1135,83 +1042,24 @@ hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hip
         x.interleave = 2;
         g = (uint32_t)gg;
     }
-#define DPWA_BATCH_LAUNCH_P(OPS, DL, P, OOP)                                                                \
-    do {                                                                                                    \
-        if (timing)                                                                                         \
-            hipExtLaunchKernelGGL((k_lerp_batch<OPS, DL, P, OOP>), dim3(g), dim3(kStreamBlock), 0, s,        \
-                                  timing->start, timing->stop, 0, x);                                       \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_lerp_batch<OPS, DL, P, OOP>), dim3(g), dim3(kStreamBlock), 0, s, x);     \
-    } while (0)
-    // cache-policy variants for tuning (DPWA_LERP_POLICY, as the single-learner kernel)
-#define DPWA_BATCH_LAUNCH(OPS, DL)                                                                          \
-    do {                                                                                                    \
-        switch (lerp_policy()) {                                                                            \
-        case 1: DPWA_BATCH_LAUNCH_P(OPS, DL, 1, false); break;                                              \
-        case 2: DPWA_BATCH_LAUNCH_P(OPS, DL, 2, false); break;                                              \
-        case 8: DPWA_BATCH_LAUNCH_P(OPS, DL, 8, false); break;                                              \
-        case 9: DPWA_BATCH_LAUNCH_P(OPS, DL, 9, false); break;                                              \
-        case 16: DPWA_BATCH_LAUNCH_P(OPS, DL, 16, false); break;                                            \
-        case 10: DPWA_BATCH_LAUNCH_P(OPS, DL, 10, false); break;                                            \
-        case 40: DPWA_BATCH_LAUNCH_P(OPS, DL, 40, false); break;                                            \
-        default: DPWA_BATCH_LAUNCH_P(OPS, DL, 0, false); break;                                             \
-        }                                                                                                   \
-    } while (0)
-    // the resident form: the product policy unless 0 is forced
-#define DPWA_BATCH_LAUNCH_OOP(OPS)                                                                          \
-    do {                                                                                                    \
-        switch (lerp_policy()) {                                                                            \
-        case 0: DPWA_BATCH_LAUNCH_P(OPS, true, 0, true); break;                                             \
-        case 1: DPWA_BATCH_LAUNCH_P(OPS, true, 1, true); break;                                             \
-        case 2: DPWA_BATCH_LAUNCH_P(OPS, true, 2, true); break;                                             \
-        case 16: DPWA_BATCH_LAUNCH_P(OPS, true, 16, true); break;                                           \
-        case 17: DPWA_BATCH_LAUNCH_P(OPS, true, 17, true); break;                                           \
-        default: DPWA_BATCH_LAUNCH_P(OPS, true, kProductPolicy, true); break;                               \
-        }                                                                                                   \
-    } while (0)
-    if (dtype == DPWA_F32) {
-        if (oop) DPWA_BATCH_LAUNCH_OOP(OpsF32);
-        else if (dual) DPWA_BATCH_LAUNCH(OpsF32, true);
-        else DPWA_BATCH_LAUNCH(OpsF32, false);
-    } else if (dtype == DPWA_BF16) {
-        if (oop) DPWA_BATCH_LAUNCH_OOP(OpsBF16);
-        else if (dual) DPWA_BATCH_LAUNCH(OpsBF16, true);
-        else DPWA_BATCH_LAUNCH(OpsBF16, false);
-    } else {
-        if (oop) DPWA_BATCH_LAUNCH_OOP(OpsF16);
-        else if (dual) DPWA_BATCH_LAUNCH(OpsF16, true);
-        else DPWA_BATCH_LAUNCH(OpsF16, false);
-    }
-#undef DPWA_BATCH_LAUNCH_OOP
-#undef DPWA_BATCH_LAUNCH
-#undef DPWA_BATCH_LAUNCH_P
-    return hipGetLastError();
+    if (oop)
+        return ResidentPolicies::with(lerp_policy(), [&](auto policy) {
+            return run(k_lerp_batch<Ops, true, decltype(policy)::value, true>, g);
+        });
+    return BatchPolicies::with(lerp_policy(), [&](auto policy) {
+        constexpr int P = decltype(policy)::value;
+        return dual ? run(k_lerp_batch<Ops, true, P, false>, g) : run(k_lerp_batch<Ops, false, P, false>, g);
+    });
+}
+
+hipError_t launch_average_batch(int32_t dtype, bool dual, const AvgBatch &b, hipStream_t s,
+                                 const LaunchTiming *timing, bool oop)
+{
+    if (b.count < 1 || b.count > kMaxAvgBatch || (oop && !dual)) return hipErrorInvalidValue;
+    return with_ops(dtype, [&](auto ops) { return average_batch<decltype(ops)>(dual, b, s, timing, oop); });
 }
 
 __global__ void k_acquire_system();
-
-template <class Ops, bool DUAL, int POLICY, bool OOP>
-static void launch_relay_policy(void *param, int64_t n, const LerpArgs &args, const StripeSrc &src, hipStream_t s,
-                                const LaunchTiming *timing)
-{
-    // every span of every stripe (the spans past the payload are range-checked away)
-    const int64_t g = (int64_t)src.parts * (src.stripe / (kStreamBlock * 16));
-    if (timing)
-        hipExtLaunchKernelGGL((k_lerp_relay<Ops, DUAL, POLICY, OOP>), dim3((uint32_t)g), dim3(kStreamBlock), 0, s,
-                              timing->start, timing->stop, 0, (typename Ops::V *)param, n, args, src);
-    else
-        hipLaunchKernelGGL((k_lerp_relay<Ops, DUAL, POLICY, OOP>), dim3((uint32_t)g), dim3(kStreamBlock), 0, s,
-                           (typename Ops::V *)param, n, args, src);
-}
-
-// the product cache policy (lerp_policy(): local parameters stored nt) or, forced to 0, the old one
-template <class Ops, bool DUAL, bool OOP = false>
-static void launch_relay_kernel(void *param, int64_t n, const LerpArgs &args, const StripeSrc &src, hipStream_t s,
-                                const LaunchTiming *timing)
-{
-    if (lerp_policy() == 8) launch_relay_policy<Ops, DUAL, 8, OOP>(param, n, args, src, s, timing);
-    else launch_relay_policy<Ops, DUAL, 0, OOP>(param, n, args, src, s, timing);
-}
 
 hipError_t launch_average_relay(int32_t dtype, void *param, int64_t n, const FusedArgs &fa, void *snap,
                                 const RelayArgs &a, int my_pick, hipStream_t s, const LaunchTiming *timing, bool oop)
@@ -1233,25 +1081,38 @@ hipError_t launch_average_relay(int32_t dtype, void *param, int64_t n, const Fus
     args.fused = fa;
     args.snap = snap;
     hipLaunchKernelGGL(k_acquire_system, dim3(256), dim3(64), 0, s);   // remote lines in L2 are stale
-    if (dtype == DPWA_F32) {
-        if (oop) launch_relay_kernel<OpsF32, true, true>(param, n, args, src, s, timing);
-        else if (snap) launch_relay_kernel<OpsF32, true>(param, n, args, src, s, timing);
-        else launch_relay_kernel<OpsF32, false>(param, n, args, src, s, timing);
-    } else if (dtype == DPWA_BF16) {
-        if (oop) launch_relay_kernel<OpsBF16, true, true>(param, n, args, src, s, timing);
-        else if (snap) launch_relay_kernel<OpsBF16, true>(param, n, args, src, s, timing);
-        else launch_relay_kernel<OpsBF16, false>(param, n, args, src, s, timing);
-    } else if (dtype == DPWA_F16) {
-        if (oop) launch_relay_kernel<OpsF16, true, true>(param, n, args, src, s, timing);
-        else if (snap) launch_relay_kernel<OpsF16, true>(param, n, args, src, s, timing);
-        else launch_relay_kernel<OpsF16, false>(param, n, args, src, s, timing);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // every span of every stripe (the spans past the payload are range-checked away)
+    const dim3 grid((uint32_t)((int64_t)src.parts * (src.stripe / (kStreamBlock * 16))));
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        return RelayPolicies::with(lerp_policy(), [&](auto policy) {
+            constexpr int P = decltype(policy)::value;
+            const auto run = [&](void (*kernel)(typename Ops::V *, int64_t, LerpArgs, StripeSrc)) {
+                return launch(kernel, grid, dim3(kStreamBlock), s, timing, param, n, args, src);
+            };
+            return oop ? run(k_lerp_relay<Ops, true, P, true>) : snap ? run(k_lerp_relay<Ops, true, P>) : run(k_lerp_relay<Ops, false, P>);
+        });
+    });
 }
 
 // ---------------------------------------------------------------- publish
+// This workgroup's span of a streaming copy: one 16-B item per lane with the streaming policy of
+// the lerp (nt loads, sc1 stores); the bytes past the last whole item go to workgroup 0.
+template <int BLOCK>
+__device__ __forceinline__ void copy_span(char *__restrict__ dst, const char *__restrict__ src, int64_t nbytes)
+{
+    constexpr int SPAN = BLOCK * 16;
+    const int64_t n16 = nbytes >> 4;
+    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
+    const int lane_off = threadIdx.x * 16;
+    span_store(span_rsrc<SPAN>(dst, span_off, n16 * 16), lane_off,
+               span_load<u32x4>(span_rsrc<SPAN>(src, span_off, n16 * 16), lane_off));
+    if (blockIdx.x == 0 && threadIdx.x < (nbytes & 15)) {
+        const int64_t j = (n16 << 4) + threadIdx.x;
+        dst[j] = src[j];
+    }
+}
+
 template <bool VEC, int BLOCK = kBlock>
 __global__ __launch_bounds__(BLOCK) void k_publish(char *__restrict__ slot, const char *__restrict__ flat,
                                                    int64_t nbytes, int64_t n, int32_t dtype,
@@ -1260,17 +1121,8 @@ __global__ __launch_bounds__(BLOCK) void k_publish(char *__restrict__ slot, cons
                                                    uint64_t version)
 {
     char *payload = slot + DPWA_SLOT_PAYLOAD_OFFSET;
-    if (VEC) {   // one 16-B item per lane, streaming policy of the lerp (nt loads, sc1 stores)
-        constexpr int SPAN = BLOCK * 16;
-        const int64_t n16 = nbytes >> 4;
-        const int64_t span_off = (int64_t)blockIdx.x * SPAN;
-        const int lane_off = threadIdx.x * 16;
-        span_store(span_rsrc<SPAN>(payload, span_off, n16 * 16), lane_off,
-                   span_load<u32x4>(span_rsrc<SPAN>(flat, span_off, n16 * 16), lane_off));
-        if (blockIdx.x == 0 && threadIdx.x < (nbytes & 15)) {
-            const int64_t j = (n16 << 4) + threadIdx.x;
-            payload[j] = flat[j];
-        }
+    if (VEC) {
+        copy_span<BLOCK>(payload, flat, nbytes);
     } else {
         const int64_t stride = (int64_t)gridDim.x * kBlock;
         for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nbytes; i += stride) payload[i] = flat[i];
@@ -1293,16 +1145,7 @@ template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_copy_payload(char *__restrict__ dst, const char *__restrict__ src,
                                                         int64_t nbytes)
 {
-    constexpr int SPAN = BLOCK * 16;
-    const int64_t n16 = nbytes >> 4;
-    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
-    const int lane_off = threadIdx.x * 16;
-    span_store(span_rsrc<SPAN>(dst, span_off, n16 * 16), lane_off,
-               span_load<u32x4>(span_rsrc<SPAN>(src, span_off, n16 * 16), lane_off));
-    if (blockIdx.x == 0 && threadIdx.x < (nbytes & 15)) {
-        const int64_t j = (n16 << 4) + threadIdx.x;
-        dst[j] = src[j];
-    }
+    copy_span<BLOCK>(dst, src, nbytes);
 }
 
 hipError_t launch_copy_payload(void *dst, const void *src, int64_t nbytes, hipStream_t s)
@@ -1317,14 +1160,11 @@ hipError_t launch_copy_payload(void *dst, const void *src, int64_t nbytes, hipSt
     return hipGetLastError();
 }
 
-// Pull: copy a peer's snapshot (header + payload, IPC-mapped in another GPU's HBM) into the
-// local staging buffer.  The loads travel over the xGMI link to the owner; each lane keeps
-// four 16-byte loads in flight and the grid is capped (grid-stride) so the pull occupies a
-// bounded share of the CUs while the training step runs on the compute stream.
-__global__ __launch_bounds__(kBlock) void k_pull(u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, int64_t n16)
+// 16-byte words first, first + stride, ... below n16, four loads in flight per lane.
+__device__ __forceinline__ void copy16(u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, int64_t n16,
+                                       int64_t first, int64_t stride)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int64_t i = first;
     for (; i + 3 * stride < n16; i += 4 * stride) {
         u32x4 v0 = src[i], v1 = src[i + stride], v2 = src[i + 2 * stride], v3 = src[i + 3 * stride];
         dst[i] = v0;
@@ -1333,6 +1173,15 @@ __global__ __launch_bounds__(kBlock) void k_pull(u32x4 *__restrict__ dst, const 
         dst[i + 3 * stride] = v3;
     }
     for (; i < n16; i += stride) dst[i] = src[i];
+}
+
+// Pull: copy a peer's snapshot (header + payload, IPC-mapped in another GPU's HBM) into the
+// local staging buffer.  The loads travel over the xGMI link to the owner; each lane keeps
+// four 16-byte loads in flight and the grid is capped (grid-stride) so the pull occupies a
+// bounded share of the CUs while the training step runs on the compute stream.
+__global__ __launch_bounds__(kBlock) void k_pull(u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, int64_t n16)
+{
+    copy16(dst, src, n16, (int64_t)blockIdx.x * kBlock + threadIdx.x, (int64_t)gridDim.x * kBlock);
 }
 
 // Invalidates every XCD's L2 lines of other agents' memory (system-scope acquire from 256
@@ -1367,18 +1216,10 @@ hipError_t launch_pull(void *dst, const void *src, int64_t nbytes, int max_block
 // from the start even when the grid exceeds what is resident at once.
 __global__ void k_release_system();
 
-__device__ __forceinline__ void copy16(u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, int64_t n16)
+// A relay copy: this workgroup's share (blockIdx.y of gridDim.y) of n16 words.
+__device__ __forceinline__ void relay_copy(u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, int64_t n16)
 {
-    const int64_t stride = (int64_t)gridDim.y * kBlock;
-    int64_t i = (int64_t)blockIdx.y * kBlock + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {
-        u32x4 v0 = src[i], v1 = src[i + stride], v2 = src[i + 2 * stride], v3 = src[i + 3 * stride];
-        dst[i] = v0;
-        dst[i + stride] = v1;
-        dst[i + 2 * stride] = v2;
-        dst[i + 3 * stride] = v3;
-    }
-    for (; i < n16; i += stride) dst[i] = src[i];
+    copy16(dst, src, n16, (int64_t)blockIdx.y * kBlock + threadIdx.x, (int64_t)gridDim.y * kBlock);
 }
 
 __device__ __forceinline__ int64_t stripe_len(int s, int64_t stripe, int64_t payload)
@@ -1398,7 +1239,7 @@ __global__ __launch_bounds__(kBlock) void k_relay_phase1(RelayArgs a)
     const int64_t len = stripe_len(a.rank, a.stripe, a.payload);
     const char *src = a.slots[j] + a.slot_off + DPWA_SLOT_PAYLOAD_OFFSET + (int64_t)a.rank * a.stripe;
     char *dst = a.relay_mine + (int64_t)j * a.stripe;
-    copy16((u32x4 *)dst, (const u32x4 *)src, len >> 4);
+    relay_copy((u32x4 *)dst, (const u32x4 *)src, len >> 4);
 }
 
 __global__ __launch_bounds__(kBlock) void k_relay_phase2(RelayArgs a)
@@ -1413,7 +1254,7 @@ __global__ __launch_bounds__(kBlock) void k_relay_phase2(RelayArgs a)
     const char *src = s == j        ? a.slots[j] + a.slot_off + DPWA_SLOT_PAYLOAD_OFFSET + (int64_t)s * a.stripe
                       : s == a.rank ? a.relay_mine + (int64_t)j * a.stripe
                                     : a.relays[s] + (int64_t)j * a.stripe;
-    copy16((u32x4 *)(a.staging + DPWA_SLOT_PAYLOAD_OFFSET + (int64_t)s * a.stripe), (const u32x4 *)src, len >> 4);
+    relay_copy((u32x4 *)(a.staging + DPWA_SLOT_PAYLOAD_OFFSET + (int64_t)s * a.stripe), (const u32x4 *)src, len >> 4);
 }
 
 hipError_t launch_relay(int phase, const RelayArgs &a, int blocks_per_part, hipStream_t s)
@@ -1447,40 +1288,29 @@ hipError_t launch_release_system(hipStream_t s)
 // Workgroup size of the snapshot copy; DPWA_PUBLISH_BLOCK (64/128/256) forces another.
 static int publish_block()
 {
-    static const int forced = [] {
-        const char *e = getenv("DPWA_PUBLISH_BLOCK");
-        const int b = e ? atoi(e) : 0;
-        return (b == 64 || b == 128 || b == 256) ? b : 0;
-    }();
-    return forced ? forced : kStreamBlock;
+    static const int block =
+        env_knob("DPWA_PUBLISH_BLOCK", kStreamBlock, [](const char *e) { return one_of(atoi(e), {64, 128, 256}); });
+    return block;
 }
 
 hipError_t launch_publish(char *slot, const void *flat, int64_t nbytes, int64_t n, int32_t dtype, double *clock,
                           double loss, const double *loss_dev, bool loss_f32, uint64_t version, bool system_release,
                           hipStream_t s)
 {
-    const char *src = (const char *)flat;
-    if (aligned16(flat)) {
-        const int64_t n16 = nbytes >> 4;
-        const int b = publish_block();
-        const int64_t g = n16 / b + 1;
-        if (b == 64)
-            hipLaunchKernelGGL((k_publish<true, 64>), dim3((uint32_t)g), dim3(64), 0, s, slot, src, nbytes, n, dtype,
-                               clock, loss, loss_dev, (int32_t)loss_f32, version);
-        else if (b == 128)
-            hipLaunchKernelGGL((k_publish<true, 128>), dim3((uint32_t)g), dim3(128), 0, s, slot, src, nbytes, n,
-                               dtype, clock, loss, loss_dev, (int32_t)loss_f32, version);
-        else
-            hipLaunchKernelGGL((k_publish<true>), dim3((uint32_t)g), dim3(kBlock), 0, s, slot, src, nbytes, n, dtype,
-                               clock, loss, loss_dev, (int32_t)loss_f32, version);
-    } else {
-        int64_t g = blocks_for(nbytes);
-        if (g > 8192) g = 8192;
-        hipLaunchKernelGGL((k_publish<false>), dim3((uint32_t)g), dim3(kBlock), 0, s, slot, src, nbytes, n, dtype,
-                           clock, loss, loss_dev, (int32_t)loss_f32, version);
+    const auto run = [&](auto kernel, int64_t grid, int block) {
+        return launch(kernel, dim3((uint32_t)grid), dim3(block), s, nullptr, slot, flat, nbytes, n, dtype, clock, loss,
+                      loss_dev, loss_f32, version);
+    };
+    hipError_t err = aligned16(flat) ? Choice<kBlock, 64, 128>::with(publish_block(), [&](auto block) {
+        constexpr int BLOCK = decltype(block)::value;
+        return run(k_publish<true, BLOCK>, (nbytes >> 4) / BLOCK + 1, BLOCK);
+    })
+                                     : run(k_publish<false>, std::min<int64_t>(blocks_for(nbytes), 8192), kBlock);
+    if (system_release) {   // the last launch that failed is the error
+        const hipError_t r = launch_release_system(s);
+        if (r != hipSuccess) err = r;
     }
-    if (system_release) hipLaunchKernelGGL(k_release_system, dim3(256), dim3(64), 0, s);
-    return hipGetLastError();
+    return err;
 }
 
 // Header-only publish: the payload of `slot` was already written by a write-through
@@ -1599,16 +1429,7 @@ __global__ __launch_bounds__(kGuardBlock) void k_guard_publish(const char *__res
         const int64_t hi = k >= samples - 1 ? n16 : guard_base(k + 1, samples, n16);
         u32x4 *d = reinterpret_cast<u32x4 *>(payload);
         const u32x4 *src = reinterpret_cast<const u32x4 *>(flat);
-        int64_t i = lo + t;
-        for (; i + 3 * kGuardBlock < hi; i += 4 * kGuardBlock) {   // four loads in flight per lane
-            const u32x4 v0 = src[i], v1 = src[i + kGuardBlock], v2 = src[i + 2 * kGuardBlock],
-                        v3 = src[i + 3 * kGuardBlock];
-            d[i] = v0;
-            d[i + kGuardBlock] = v1;
-            d[i + 2 * kGuardBlock] = v2;
-            d[i + 3 * kGuardBlock] = v3;
-        }
-        for (; i < hi; i += kGuardBlock) d[i] = src[i];
+        copy16(d, src, hi, lo + t, kGuardBlock);
     }
 }
 
@@ -1767,11 +1588,7 @@ hipError_t launch_stream_mix(const StreamMixArgs &a, hipStream_t s, const Launch
     const uint32_t g = (uint32_t)(a.nbytes / (kStreamBlock * 16) + 1);
     void (*k)(StreamMixArgs) = a.nr == 1 ? (a.nw == 1 ? k_stream_mix<1, 1> : k_stream_mix<1, 2>)
                                          : (a.nw == 1 ? k_stream_mix<2, 1> : k_stream_mix<2, 2>);
-    if (timing)
-        hipExtLaunchKernelGGL(k, dim3(g), dim3(kStreamBlock), 0, s, timing->start, timing->stop, 0, a);
-    else
-        hipLaunchKernelGGL(k, dim3(g), dim3(kStreamBlock), 0, s, a);
-    return hipGetLastError();
+    return launch(k, dim3(g), dim3(kStreamBlock), s, timing, a);
 }
 
 // One 64-bit word into (host-mapped) memory after everything before it on the stream: a

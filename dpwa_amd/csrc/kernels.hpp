@@ -144,9 +144,6 @@ hipError_t launch_publish_header(char *slot, int64_t n, int32_t dtype, double *c
                                  const double *loss_dev, bool loss_f32, uint64_t version, bool system_release,
                                  hipStream_t s);
 
-// Reuse guard of a header-only publish: sampled words of `flat` against the snapshot `payload`
-// the last average wrote; on a difference the payload is copied from `flat` and *hits += 1
-// (*dirty: the verdict, device memory; both written by the device).
 // dpwa_stream_mix: the averaging kernels' access mix alone (measurement only).
 struct StreamMixArgs {
     const char *src[2];
@@ -156,6 +153,9 @@ struct StreamMixArgs {
 };
 hipError_t launch_stream_mix(const StreamMixArgs &a, hipStream_t s, const LaunchTiming *timing);
 
+// Reuse guard of a header-only publish: sampled words of `flat` against the snapshot `payload`
+// the last average wrote; on a difference the payload is copied from `flat` and *hits += 1
+// (*dirty: the verdict, device memory; both written by the device).
 hipError_t launch_guard_payload(char *payload, const void *flat, int64_t nbytes, int32_t *dirty, uint32_t *hits,
                                 int32_t gen, hipStream_t s);
 
