@@ -22,6 +22,7 @@ ABI_VERSION = 11
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4
 F32, BF16, F64, F16, MIXED = 0, 1, 2, 3, 4
 LAYOUT_MAX_SEGMENTS, LAYOUT_ALIGN = 3, 4096
+DISTANCE_ACC_STRIDE = 128    # bytes from one distance accumulator to the next in a workspace
 INTERP_CONSTANT, INTERP_CLOCK, INTERP_LOSS = 0, 1, 2
 STATUS_OK, STATUS_ZERO_DIVISION = 0, 1
 IPC_HANDLE_BYTES = 128
@@ -75,6 +76,12 @@ class Layout(ctypes.Structure):
     _fields_ = [("count", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seg", Segment * LAYOUT_MAX_SEGMENTS)]
 
 
+class Distance(ctypes.Structure):
+    """dpwa_distance: the 32-byte record of a round's distance to the peer."""
+    _fields_ = [("dist2", ctypes.c_double), ("norm2", ctypes.c_double), ("clock", ctypes.c_double),
+                ("n", ctypes.c_int64)]
+
+
 class Interp(ctypes.Structure):
     _fields_ = [("method", ctypes.c_int32), ("reserved", ctypes.c_int32), ("value", ctypes.c_double),
                 ("divergence_threshold", ctypes.c_double)]
@@ -109,6 +116,14 @@ SIGNATURES = {
     "dpwa_factor": [ctypes.POINTER(Interp), _vp, _vp, _dbl, _vp, _vp, _vp],
     "dpwa_average": [_i32, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp],
     "dpwa_average_mixed": [ctypes.POINTER(Layout), _vp, _vp, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_distance_workspace": [ctypes.POINTER(_i64)],
+    "dpwa_measure_distance": [_i32, _vp, _vp, _i64, _vp, _vp, _vp],
+    "dpwa_measure_distance_mixed": [ctypes.POINTER(Layout), _vp, _vp, _vp, _vp, _vp],
+    "dpwa_average_tracked": [_i32, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp],
+    "dpwa_distance_finish": [_vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "dpwa_learner_set_distance": [_vp, _int],
+    "dpwa_learner_distance": [_vp, ctypes.POINTER(_vp)],
     "dpwa_layout_digest": [ctypes.POINTER(Layout), _i64, ctypes.POINTER(ctypes.c_uint32)],
     "dpwa_learner_set_layout": [_vp, ctypes.POINTER(Layout)],
     "dpwa_node_set_layout": [_vp, ctypes.POINTER(Layout)],

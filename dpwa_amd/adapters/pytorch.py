@@ -71,10 +71,16 @@ class DpwaPyTorchAdapter:
     not use it."""
 
     def __init__(self, net, name, config_file, write_through=True, transport="device", reuse_guard=True,
-                 resident=False, **connection_kwargs):
+                 resident=False, track_distance=False, **connection_kwargs):
         """transport: "device" (peers are learners of this process or of the torch.distributed
         job, pulled from HBM/over xGMI) or "wire" (peers are reached over TCP at the YAML's
-        host/port with the reference's protocol -- e.g. reference CPU nodes; dpwa_amd/bridge.py)."""
+        host/port with the reference's protocol -- e.g. reference CPU nodes; dpwa_amd/bridge.py).
+
+        track_distance (extension, off by default): every round that averages also measures how far
+        the model was from the peer's snapshot it averaged with (``last_distance``; see
+        ``DpwaConnection``).  For a single-dtype model the averaging kernel does it with no extra
+        bytes in all three forms; a model that mixes dtypes pays one more read of both operands."""
+        connection_kwargs = dict(connection_kwargs, track_distance=track_distance)
         if resident and transport != "device":
             raise ValueError("resident parameters need the device transport")
         self._net = net
@@ -237,6 +243,13 @@ class DpwaPyTorchAdapter:
         hits = ctypes.c_uint32()
         _lib.call("dpwa_learner_window_hits", self._conn._learner.handle, ctypes.byref(hits))
         return hits.value
+
+    @property
+    def last_distance(self):
+        """The connection's ``last_distance`` (``PeerDistance``): None until a round has averaged
+        with ``track_distance=True``.  Its ``.distance`` / ``.norm`` / ``.relative`` / ``.clock``
+        read the device record and synchronise with the stream that averaged; ``.tensor()`` does not."""
+        return self._conn.last_distance
 
     @property
     def connection(self):

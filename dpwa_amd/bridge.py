@@ -256,8 +256,8 @@ class WireConnection(DpwaConnection):
     training step like the reference's TxThread; eager=False fetches at update_wait
     (deterministic lock-step when every node's update_send precedes every update_wait)."""
 
-    def __init__(self, name, config_file, codec=None, seed=None, eager=True, serve=True):
-        super().__init__(name, config_file, seed=seed, group=_WireGroup())
+    def __init__(self, name, config_file, codec=None, seed=None, eager=True, serve=True, track_distance=False):
+        super().__init__(name, config_file, seed=seed, group=_WireGroup(), track_distance=track_distance)
         self.codec = codec
         self.eager = eager
         self._wire_peers = [_Peer(p.host, p.port) for p in self.peers]
@@ -394,6 +394,7 @@ class WireConnection(DpwaConnection):
         else:
             self._learner.average(parameters, loss, stream)
         self._averaged_once = True
+        self._last_distance = self._distance
         return PeerSnapshot(self, k, 0), DeviceFactor(self._learner)
 
     def _loss(self, loss):

@@ -20,6 +20,10 @@
 //             so no workgroup ever reads a clock another one is writing) and dpwa_coef.
 //  * mixed:   the same pass over the segmented payload of a model that mixes float32, bfloat16
 //             and float16 parameters (k_lerp_mixed): each one-wave span rounds as its segment's type.
+//  * distance: opt-in -- the round's distance to the peer, sum (q - p)^2 and sum p^2 in fp64, formed
+//             by a tracked form of the fused average from the operands it holds anyway
+//             (k_lerp_tracked), or by a stand-alone pass (k_distance*), added across workgroups with
+//             the hardware fp64 add and finished by k_distance_finish.
 //  * factor:  the same fp64 math as a one-thread kernel for the split API.
 //  * publish: update_send's snapshot (dpwa.py:111-116, pytorch.py:49-53) -- clock += 1 on
 //             the device and one copy of the flat buffer into a snapshot slot behind its
@@ -462,16 +466,127 @@ struct StripeSrc {
     }
 };
 
+// ---------------------------------------------------------------- distance to the peer
+// The opt-in measurement of a round (include/dpwa_hip.h dpwa_distance): dist2 = sum (q - p)^2 and
+// norm2 = sum p^2 over the operands as they were before the average, every element widened
+// exactly to fp64 and every difference, product and sum in fp64 (contraction is off: a separate
+// multiply and add).  A lane sums its own elements in order, the wave sums its lanes with a
+// fixed xor butterfly of shuffles (no LDS memory), and lanes 0 and 1 add the pair into one of
+// kDistAccs accumulators with the hardware fp64 add, the accumulator chosen by the span's index
+// so that the workgroups in flight do not meet on one address.  Each accumulator has a 128-byte
+// row of its own (float atomics that all land in one row run an order of magnitude slower).
+// k_distance_finish sums the accumulators in a fixed order; the order in which workgroups
+// reached an accumulator is not fixed, so the record is the library's one output that is not
+// bit-exact from run to run (it is within (n - 1) 2^-53 relative, all terms being >= 0).
+constexpr int kDistAccs = 1024;
+constexpr int kDistAccStride = 128 / (int)sizeof(double);   // doubles from one accumulator to the next
+static_assert((size_t)kDistAccs * kDistAccStride * sizeof(double) == kDistanceWorkspaceBytes, "workspace size");
+
+__device__ __forceinline__ void dist_term(double q, double p, double &d2, double &n2)
+{
+    const double d = q - p;
+    d2 = d2 + d * d;
+    n2 = n2 + p * p;
+}
+
+__device__ __forceinline__ void dist_add_bf16x2(uint32_t q, uint32_t p, double &d2, double &n2)
+{
+    dist_term((double)bf_lo(q), (double)bf_lo(p), d2, n2);
+    dist_term((double)bf_hi(q), (double)bf_hi(p), d2, n2);
+}
+
+__device__ __forceinline__ void dist_add_f16x2(uint32_t q, uint32_t p, double &d2, double &n2)
+{
+    const f16x2v qh = __builtin_bit_cast(f16x2v, q), ph = __builtin_bit_cast(f16x2v, p);
+    dist_term((double)qh.x, (double)ph.x, d2, n2);
+    dist_term((double)qh.y, (double)ph.y, d2, n2);
+}
+
+// One lane's 16-byte item, its elements in order.
+__device__ __forceinline__ void dist_add(OpsF32, f32x4 q, f32x4 p, double &d2, double &n2)
+{
+    dist_term((double)q.x, (double)p.x, d2, n2);
+    dist_term((double)q.y, (double)p.y, d2, n2);
+    dist_term((double)q.z, (double)p.z, d2, n2);
+    dist_term((double)q.w, (double)p.w, d2, n2);
+}
+
+__device__ __forceinline__ void dist_add(OpsBF16, u32x4 q, u32x4 p, double &d2, double &n2)
+{
+    dist_add_bf16x2(q.x, p.x, d2, n2);
+    dist_add_bf16x2(q.y, p.y, d2, n2);
+    dist_add_bf16x2(q.z, p.z, d2, n2);
+    dist_add_bf16x2(q.w, p.w, d2, n2);
+}
+
+__device__ __forceinline__ void dist_add(OpsF16, u32x4 q, u32x4 p, double &d2, double &n2)
+{
+    dist_add_f16x2(q.x, p.x, d2, n2);
+    dist_add_f16x2(q.y, p.y, d2, n2);
+    dist_add_f16x2(q.z, p.z, d2, n2);
+    dist_add_f16x2(q.w, p.w, d2, n2);
+}
+
+// One element (the ragged tail, the unaligned kernel).
+__device__ __forceinline__ void dist_add_s(OpsF32, float q, float p, double &d2, double &n2)
+{
+    dist_term((double)q, (double)p, d2, n2);
+}
+
+__device__ __forceinline__ void dist_add_s(OpsBF16, uint16_t q, uint16_t p, double &d2, double &n2)
+{
+    dist_term((double)bf_lo(q), (double)bf_lo(p), d2, n2);
+}
+
+__device__ __forceinline__ void dist_add_s(OpsF16, uint16_t q, uint16_t p, double &d2, double &n2)
+{
+    dist_term((double)__builtin_bit_cast(_Float16, q), (double)__builtin_bit_cast(_Float16, p), d2, n2);
+}
+
+// The sum over the wave's 64 lanes, the same in every lane: a xor butterfly, so the order of the
+// additions is fixed.
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// The wave's pair into accumulator `index` mod kDistAccs: one atomic instruction, lane 0 adding
+// dist2 and lane 1 norm2 (global_atomic_add_f64, no compare-and-swap loop; the accumulators are
+// ordinary device memory).
+__device__ __forceinline__ void dist_commit(double *acc, uint32_t index, double d2, double n2)
+{
+    d2 = wave_sum(d2);
+    n2 = wave_sum(n2);
+    const int lane = threadIdx.x & 63;
+    if (lane < 2) unsafeAtomicAdd(acc + (size_t)(index % kDistAccs) * kDistAccStride + lane, lane ? n2 : d2);
+}
+
+// What lerp_span does about the distance: nothing (every averaging kernel but k_lerp_tracked), or
+// the sums above into `acc`.
+struct NoTrack {
+    static constexpr bool ON = false;
+};
+struct DistTrack {
+    static constexpr bool ON = true;
+    double *acc;
+};
+
 // One 16-byte item per lane; items beyond n/PER (the ragged tail) go to block 0.
 // DUAL also stores the result into args.snap (write-through snapshot: the next publish of
 // these parameters then needs no copy).  OOP (with DUAL): the result is stored into args.snap
 // ONLY -- the resident form, whose parameters live in the learner's own snapshot slots and move
 // from the published slot to the next one at every average (2 reads + 1 write per element, the
 // averaging's own bytes; learner.cpp "resident").  BLOCK lanes per workgroup (kStreamBlock).
-template <class Ops, int MODE, bool DUAL, int BLOCK, int POLICY, class Src, bool OOP = false>
+// Track (DistTrack, one-wave workgroups only): a round that averages also adds its distance sums,
+// formed from the q and p this lane loaded anyway; a no-op round adds nothing.
+template <class Ops, int MODE, bool DUAL, int BLOCK, int POLICY, class Src, bool OOP = false, class Track = NoTrack>
 __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restrict__ param, const Src &src,
-                                          int64_t n, const LerpArgs &args, const Ops &ops = Ops{})
+                                          int64_t n, const LerpArgs &args, const Ops &ops = Ops{},
+                                          const Track &track = Track{})
 {
+    static_assert(!Track::ON || BLOCK == 64, "the tracked form runs one-wave workgroups");
     using V = typename Ops::V;
     using P = LerpPolicy<POLICY>;
     constexpr int SPAN = BLOCK * 16;
@@ -500,17 +615,22 @@ __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restr
     const V r = ops.lerp(a, b, q, p);
     if (!OOP) span_store<V, P::store>(rp, lane_off, r);
     if (DUAL) span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, r);
+    [[maybe_unused]] double d2 = 0.0, n2 = 0.0;
+    if constexpr (Track::ON) dist_add(ops, q, p, d2, n2);
     if constexpr (Ops::TAIL) {
         using S = typename Ops::S;
         S *ps = reinterpret_cast<S *>(param);
         const int64_t tail = n / Ops::PER * Ops::PER;
         if (blk == 0 && threadIdx.x < n - tail) {
             const int64_t j = tail + threadIdx.x;
-            const S t = Ops::lerp_s(a, b, *reinterpret_cast<const S *>(src.at(j * (int64_t)sizeof(S))), ps[j]);
+            const S qs = *reinterpret_cast<const S *>(src.at(j * (int64_t)sizeof(S))), pj = ps[j];
+            const S t = Ops::lerp_s(a, b, qs, pj);
             if (!OOP) ps[j] = t;
             if (DUAL) reinterpret_cast<S *>(args.snap)[j] = t;
+            if constexpr (Track::ON) dist_add_s(ops, qs, pj, d2, n2);
         }
     }
+    if constexpr (Track::ON) dist_commit(track.acc, blk, d2, n2);
 }
 
 template <class Ops, int MODE, bool DUAL, int BLOCK = kBlock, int POLICY = 0, bool OOP = false>
@@ -575,6 +695,119 @@ __global__ __launch_bounds__(kStreamBlock) void k_lerp_mixed(u32x4 *__restrict__
     const ContigSrc src{(const char *)peer};
     const OpsMixed ops{segs, src.span_of<kStreamBlock * 16>(blockIdx.x)};
     lerp_span<OpsMixed, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP>(blockIdx.x, param, src, total, args, ops);
+}
+
+// The tracked form of the single-learner fused average (k_lerp's span code with DistTrack, so the
+// averaged bits are k_lerp's): plain, write-through (DUAL) and resident (OOP), one-wave
+// workgroups, the product cache policy (POLICY = kProductPolicy).  `acc`: the distance accumulators.
+template <class Ops, bool DUAL, bool OOP, int POLICY>
+__global__ __launch_bounds__(kStreamBlock) void k_lerp_tracked(typename Ops::V *__restrict__ param,
+                                                               const typename Ops::V *__restrict__ peer, int64_t n,
+                                                               LerpArgs args, double *__restrict__ acc)
+{
+    lerp_span<Ops, COEF_FUSED, DUAL, kStreamBlock, POLICY, ContigSrc, OOP, DistTrack>(
+        blockIdx.x, param, ContigSrc{(const char *)peer}, n, args, Ops{}, DistTrack{acc});
+}
+
+// The stand-alone distance pass: the same sums with no store to either operand, for the averaging
+// forms that have no tracked kernel (it runs before their average, on the same stream) and for
+// dpwa_measure_distance.  The spans are the averaging kernel's; the loads take the default cache
+// policy, since the average that follows reads the same bytes again.
+template <class Ops>
+__global__ __launch_bounds__(kStreamBlock) void k_distance(const typename Ops::V *__restrict__ param,
+                                                           const typename Ops::V *__restrict__ peer, int64_t n,
+                                                           double *__restrict__ acc)
+{
+    using V = typename Ops::V;
+    using S = typename Ops::S;
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t vbytes = n / Ops::PER * 16;
+    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
+    const int lane_off = threadIdx.x * 16;
+    const V q = span_load<V, 0>(span_rsrc<SPAN>(peer, span_off, vbytes), lane_off);
+    const V p = span_load<V, 0>(span_rsrc<SPAN>(param, span_off, vbytes), lane_off);
+    double d2 = 0.0, n2 = 0.0;
+    dist_add(Ops{}, q, p, d2, n2);
+    const int64_t tail = n / Ops::PER * Ops::PER;
+    if (blockIdx.x == 0 && threadIdx.x < n - tail) {
+        const int64_t j = tail + threadIdx.x;
+        dist_add_s(Ops{}, reinterpret_cast<const S *>(peer)[j], reinterpret_cast<const S *>(param)[j], d2, n2);
+    }
+    dist_commit(acc, blockIdx.x, d2, n2);
+}
+
+// The same over a segmented payload: the span's type is its segment's (no ragged tail; padding
+// bytes are zeros on both sides and add nothing).
+__global__ __launch_bounds__(kStreamBlock) void k_distance_mixed(const u32x4 *__restrict__ param,
+                                                                 const u32x4 *__restrict__ peer, int64_t total,
+                                                                 SegTable segs, double *__restrict__ acc)
+{
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
+    const int lane_off = threadIdx.x * 16;
+    const u32x4 q = span_load<u32x4, 0>(span_rsrc<SPAN>(peer, span_off, total), lane_off);
+    const u32x4 p = span_load<u32x4, 0>(span_rsrc<SPAN>(param, span_off, total), lane_off);
+    const int32_t dtype = seg_dtype(segs, span_off);
+    double d2 = 0.0, n2 = 0.0;
+    if (dtype == DPWA_F32) dist_add(OpsF32{}, __builtin_bit_cast(f32x4, q), __builtin_bit_cast(f32x4, p), d2, n2);
+    else if (dtype == DPWA_BF16) dist_add(OpsBF16{}, q, p, d2, n2);
+    else dist_add(OpsF16{}, q, p, d2, n2);
+    dist_commit(acc, blockIdx.x, d2, n2);
+}
+
+// Element-wise form for operands that are not 16-byte aligned: a grid-stride loop, each wave
+// adding its pair into the accumulator of its index in the grid.
+template <class Ops>
+__global__ __launch_bounds__(kBlock) void k_distance_unaligned(const typename Ops::S *__restrict__ param,
+                                                               const typename Ops::S *__restrict__ peer, int64_t n,
+                                                               double *__restrict__ acc)
+{
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    double d2 = 0.0, n2 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+        dist_add_s(Ops{}, peer[i], param[i], d2, n2);
+    dist_commit(acc, blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), d2, n2);
+}
+
+// Finishing (one workgroup, after the pass on the same stream: the kernel boundary orders it
+// behind every add): one lane per accumulator, so every load is in flight at once; the sums are
+// taken in a fixed order -- the butterfly inside each wave, then the waves in order -- and the
+// accumulators are left zero for the next round.  The record is written only when the round
+// averaged (`coef` null, or its status OK); its clock is the one that round committed (0 without
+// a coef).  The accumulators are read and zeroed with agent-scope accesses: the adds that fill
+// them never pass through an L2.
+constexpr int kDistFinishBlock = kDistAccs;
+static_assert(kDistFinishBlock <= 1024 && kDistFinishBlock % 64 == 0, "one lane per accumulator");
+
+__global__ __launch_bounds__(kDistFinishBlock) void k_distance_finish(double *__restrict__ acc,
+                                                                      dpwa_distance *__restrict__ out,
+                                                                      const dpwa_coef *__restrict__ coef, int64_t n)
+{
+    __shared__ double s_d2[kDistFinishBlock / 64], s_n2[kDistFinishBlock / 64];
+    double *a = acc + (size_t)threadIdx.x * kDistAccStride;
+    double d2 = __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    double n2 = __hip_atomic_load(a + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a + 1, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    d2 = wave_sum(d2);
+    n2 = wave_sum(n2);
+    if ((threadIdx.x & 63) == 0) {
+        s_d2[threadIdx.x >> 6] = d2;
+        s_n2[threadIdx.x >> 6] = n2;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0 || (coef && coef->status != DPWA_STATUS_OK)) return;
+    d2 = s_d2[0];
+    n2 = s_n2[0];
+#pragma unroll
+    for (int w = 1; w < kDistFinishBlock / 64; ++w) {
+        d2 = d2 + s_d2[w];
+        n2 = n2 + s_n2[w];
+    }
+    out->dist2 = d2;
+    out->norm2 = n2;
+    out->clock = coef ? coef->new_clock : 0.0;
+    out->n = n;
 }
 
 // The relay's fused second phase: the fused average reads the peer's snapshot stripe by stripe
@@ -953,6 +1186,67 @@ hipError_t launch_average_mixed(const dpwa_layout &layout, void *param, const vo
     if (oop) return launch_mixed<COEF_FUSED, true, true>(layout, param, peer, args, s, timing);
     if (snap) return launch_mixed<COEF_FUSED, true, false>(layout, param, peer, args, s, timing);
     return launch_mixed<COEF_FUSED, false, false>(layout, param, peer, args, s, timing);
+}
+
+// ---------------------------------------------------------------- distance launches
+hipError_t launch_average_tracked(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa,
+                                  void *snap, bool oop, double *acc, hipStream_t s, const LaunchTiming *timing)
+{
+    if (n < 0 || !acc || (oop && !snap && n > 0) || !aligned16(param) || !aligned16(peer) || !aligned16(snap))
+        return hipErrorInvalidValue;
+    LerpArgs args{};
+    args.fused = fa;
+    args.snap = snap;
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        using V = typename Ops::V;
+        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+        const auto run = [&](void (*kernel)(V *, const V *, int64_t, LerpArgs, double *)) {
+            return launch(kernel, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, timing, param,
+                          peer, n, args, acc);
+        };
+        constexpr int P = kProductPolicy;
+        return oop ? run(k_lerp_tracked<Ops, true, true, P>)
+                   : snap ? run(k_lerp_tracked<Ops, true, false, P>) : run(k_lerp_tracked<Ops, false, false, P>);
+    });
+}
+
+hipError_t launch_distance(int32_t dtype, const void *param, const void *peer, int64_t n, double *acc, hipStream_t s)
+{
+    if (n < 0 || !acc) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        if (!aligned16(param) || !aligned16(peer))
+            return launch(k_distance_unaligned<Ops>, dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)), dim3(kBlock),
+                          s, nullptr, param, peer, n, acc);
+        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+        return launch(k_distance<Ops>, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, nullptr,
+                      param, peer, n, acc);
+    });
+}
+
+hipError_t launch_distance_mixed(const dpwa_layout &layout, const void *param, const void *peer, double *acc,
+                                 hipStream_t s)
+{
+    if (layout_problem(layout, -1) || !param || !peer || !acc || !aligned16(param) || !aligned16(peer))
+        return hipErrorInvalidValue;
+    SegTable t;
+    for (int i = 0; i < DPWA_LAYOUT_MAX_SEGMENTS; ++i) {
+        t.begin[i] = i < layout.count ? layout.seg[i].byte_offset : INT64_MAX;
+        t.dtype[i] = i < layout.count ? layout.seg[i].dtype : layout.seg[0].dtype;
+    }
+    const int64_t total = layout_bytes(layout);
+    const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
+    if (g > 0x7fffffffLL) return hipErrorInvalidValue;
+    return launch(k_distance_mixed, dim3((uint32_t)g), dim3(kStreamBlock), s, nullptr, param, peer, total, t, acc);
+}
+
+hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
+                                  const LaunchTiming *timing)
+{
+    if (!acc || !out) return hipErrorInvalidValue;
+    return launch(k_distance_finish, dim3(1), dim3(kDistFinishBlock), s, timing, acc, out, coef, n);
 }
 
 // Some buffer is read by two entries (as parameters or as the peer snapshot).

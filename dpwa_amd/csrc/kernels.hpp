@@ -73,6 +73,24 @@ hipError_t launch_lerp_mixed(const dpwa_layout &layout, void *param, const void 
 hipError_t launch_average_mixed(const dpwa_layout &layout, void *param, const void *peer, const FusedArgs &fa,
                                 void *snap, hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
 
+// The distance to the peer (dpwa_distance, include/dpwa_hip.h; kernels.hip "distance to the peer").
+// `acc`: kDistanceWorkspaceBytes of device memory, zero before the first use; every finish leaves
+// it zero again.
+//   average_tracked   launch_average with the sums added by the same kernel (k_lerp_tracked):
+//                     16-B aligned operands and a single dtype only, else hipErrorInvalidValue
+//   distance(_mixed)  the stand-alone pass over (param, peer payload); any element alignment
+//   distance_finish   sums the accumulators into *out when the round averaged (`coef` null, or its
+//                     status OK; the record's clock is coef->new_clock, 0 without a coef)
+constexpr int64_t kDistanceWorkspaceBytes = 128 << 10;
+hipError_t launch_average_tracked(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa,
+                                  void *snap, bool oop, double *acc, hipStream_t s,
+                                  const LaunchTiming *timing = nullptr);
+hipError_t launch_distance(int32_t dtype, const void *param, const void *peer, int64_t n, double *acc, hipStream_t s);
+hipError_t launch_distance_mixed(const dpwa_layout &layout, const void *param, const void *peer, double *acc,
+                                 hipStream_t s);
+hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
+                                  const LaunchTiming *timing = nullptr);
+
 // Several fused averages (co-resident learners) in one dispatch: entry i's workgroups follow
 // entry i-1's.  Every pointer 16-B aligned; `dual` = every entry writes through (snap non-null).
 constexpr int kMaxAvgBatch = 8;

@@ -464,6 +464,10 @@ struct dpwa_learner {
     // learners (local) that read our slot k and must be waited for before rewriting it
     std::mutex readers_mu;
     std::vector<dpwa_learner *> readers[2];
+    // distance tracking (dpwa_learner_set_distance): the accumulators and, behind them, the record;
+    // allocated when first switched on, kept until destroy
+    bool track = false;
+    char *dist_mem = nullptr;
     int32_t *host_status = nullptr;     // pinned mirror of coef.status for non-blocking polls
     int32_t *host_status_dev = nullptr; // its device-side address
 };
@@ -472,6 +476,9 @@ static char *slot_payload(const dpwa_learner *l, int k)
 {
     return l->slots + (size_t)k * l->slot_stride + kPayloadOff;
 }
+
+static double *dist_acc(const dpwa_learner *l) { return (double *)l->dist_mem; }
+static dpwa_distance *dist_record(const dpwa_learner *l) { return (dpwa_distance *)(l->dist_mem + kDistanceWorkspaceBytes); }
 
 static int64_t now_ns()
 {
@@ -623,6 +630,102 @@ int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_
     return DPWA_OK;
 }
 
+static_assert(sizeof(dpwa_distance) == 32, "dpwa_distance must be 32 bytes");
+static_assert(kDistanceWorkspaceBytes % DPWA_DISTANCE_ACC_STRIDE == 0 && kDistanceWorkspaceBytes <= (1 << 20),
+              "distance workspace");
+
+int dpwa_distance_workspace(int64_t *bytes)
+{
+    if (!bytes) return set_error(DPWA_ERR_ARG, "dpwa_distance_workspace: NULL argument");
+    *bytes = kDistanceWorkspaceBytes;
+    return DPWA_OK;
+}
+
+// The workspace and the record of a stateless distance entry: non-null, 16-B / 8-B aligned.
+static bool distance_buffers_ok(const void *workspace, const dpwa_distance *out_dev)
+{
+    return workspace && out_dev && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)out_dev & 7) == 0;
+}
+
+int dpwa_measure_distance(int32_t dtype, const void *param, const void *peer_payload, int64_t n, void *workspace,
+                          dpwa_distance *out_dev, dpwa_stream_t stream)
+{
+    if (n < 0 || (n > 0 && (!param || !peer_payload)) || !distance_buffers_ok(workspace, out_dev))
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: bad arguments (NULL or misaligned pointer, n < 0)");
+    if (dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: a DPWA_MIXED payload needs its layout "
+                                       "(dpwa_measure_distance_mixed)");
+    if (dtype != DPWA_F32 && dtype != DPWA_BF16 && dtype != DPWA_F16)
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: unknown dtype %d", dtype);
+    const size_t es = dtype_size(dtype);
+    if (((uintptr_t)param | (uintptr_t)peer_payload) & (es - 1))
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: an operand is not aligned to its element size");
+    HIP_TRY(launch_distance(dtype, param, peer_payload, n, (double *)workspace, (hipStream_t)stream));
+    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, nullptr, n, (hipStream_t)stream));
+    return DPWA_OK;
+}
+
+int dpwa_measure_distance_mixed(const dpwa_layout *layout, const void *param, const void *peer_payload,
+                                void *workspace, dpwa_distance *out_dev, dpwa_stream_t stream)
+{
+    if (!layout || !param || !peer_payload || !distance_buffers_ok(workspace, out_dev))
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: bad arguments (NULL or misaligned pointer)");
+    if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: %s", why);
+    if (((uintptr_t)param | (uintptr_t)peer_payload) & 15)
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: a segmented payload is 16-byte aligned");
+    int64_t n = 0;
+    for (int i = 0; i < layout->count; ++i) n += layout->seg[i].byte_length / (int64_t)dtype_size(layout->seg[i].dtype);
+    HIP_TRY(launch_distance_mixed(*layout, param, peer_payload, (double *)workspace, (hipStream_t)stream));
+    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, nullptr, n, (hipStream_t)stream));
+    return DPWA_OK;
+}
+
+int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int64_t n, const dpwa_interp *cfg,
+                         double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, void *workspace,
+                         dpwa_distance *out_dev, dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (!cfg || !clock_dev || !coef_dev || !peer_slot || n < 0 || (n > 0 && !param) || (!start_event) != (!stop_event) ||
+        !distance_buffers_ok(workspace, out_dev))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: bad arguments (NULL or misaligned pointer, n < 0)");
+    if (dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: segmented (DPWA_MIXED) payloads have no tracked kernel "
+                                       "(dpwa_measure_distance_mixed, then dpwa_average_mixed)");
+    if (dtype != DPWA_F32 && dtype != DPWA_BF16 && dtype != DPWA_F16)
+        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: unknown dtype %d", dtype);
+    if (cfg->method < 0 || cfg->method > 2)
+        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: unknown method %d", cfg->method);
+    FusedArgs fa{};
+    fa.cfg = *cfg;
+    fa.clock_in = clock_dev;
+    fa.clock_out = clock_dev + 1;
+    fa.hdr = (const dpwa_header *)peer_slot;
+    fa.loss_h = loss;
+    fa.coef_out = coef_dev;
+    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
+    hipStream_t s = (hipStream_t)stream;
+    const char *peer = (const char *)peer_slot + kPayloadOff;
+    if ((((uintptr_t)param | (uintptr_t)peer | (uintptr_t)snap_payload) & 15) == 0) {
+        HIP_TRY(launch_average_tracked(dtype, param, peer, n, fa, snap_payload, false, (double *)workspace, s,
+                                       start_event ? &t : nullptr));
+    } else {   // the stand-alone pass, then dpwa_average's own (unaligned) kernel
+        HIP_TRY(launch_distance(dtype, param, peer, n, (double *)workspace, s));
+        HIP_TRY(launch_average(dtype, param, peer, n, fa, snap_payload, s, start_event ? &t : nullptr));
+    }
+    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, s));
+    return DPWA_OK;
+}
+
+int dpwa_distance_finish(void *workspace, dpwa_distance *out_dev, const dpwa_coef *coef_dev, int64_t n,
+                         dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (n < 0 || (!start_event) != (!stop_event) || !distance_buffers_ok(workspace, out_dev))
+        return set_error(DPWA_ERR_ARG, "dpwa_distance_finish: bad arguments (NULL or misaligned pointer, n < 0)");
+    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
+    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, (hipStream_t)stream,
+                                   start_event ? &t : nullptr));
+    return DPWA_OK;
+}
+
 int dpwa_stream_mix(void *const *dst, int nw, const void *const *src, int nr, int64_t nbytes, dpwa_stream_t stream,
                     void *start_event, void *stop_event)
 {
@@ -746,6 +849,7 @@ int dpwa_learner_destroy(dpwa_learner *l)
     devmem_free(l->relay_mem);
     if (l->read_stream) (void)hipStreamDestroy(l->read_stream);
     if (l->host_status) (void)hipHostFree(l->host_status);
+    if (l->dist_mem) (void)hipFree(l->dist_mem);
     devmem_free(l->slot_mem);
     if (l->staging) (void)hipFree(l->staging);
     if (l->ctl) (void)hipFree(l->ctl);
@@ -1309,6 +1413,8 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
 
 static int relay_materialize(dpwa_learner *l);
 static hipError_t staging_read(dpwa_learner *l, hipStream_t s);
+static int distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s);
+static int distance_after(dpwa_learner *l, hipStream_t s);
 
 static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev)
 {
@@ -1374,12 +1480,17 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_lerp: a resident learner averages with dpwa_learner_average");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    if (l->dtype == DPWA_MIXED) {   // (its layout is known: the factor was computed)
-        if ((uintptr_t)flat & 15) return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
+    if (l->dtype == DPWA_MIXED && ((uintptr_t)flat & 15))   // (its layout is known: the factor was computed)
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
+    if (l->track)
+        if (int rc = distance_before(l, flat, l->src + kPayloadOff, s)) return rc;
+    if (l->dtype == DPWA_MIXED) {
         HIP_TRY(launch_lerp_mixed(l->layout, flat, l->src + kPayloadOff, &l->ctl->coef, s));
     } else {
         HIP_TRY(launch_lerp(l->dtype, flat, l->src + kPayloadOff, l->n, &l->ctl->coef, 0.f, 0.f, s));
     }
+    if (l->track)
+        if (int rc = distance_after(l, s)) return rc;
     HIP_TRY(staging_read(l, s));
     l->wt_valid = false;
     l->consume_stream = s;
@@ -1483,8 +1594,39 @@ static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
     return DPWA_OK;
 }
 
+// Distance tracking around an average that has no tracked kernel: the stand-alone pass over the
+// operands before the average on `s` (the in-place forms overwrite what it reads), the finishing
+// step after it (it reads the coefficients that average committed).
+static int distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s)
+{
+    if (l->dtype == DPWA_MIXED) HIP_TRY(launch_distance_mixed(l->layout, flat, peer, dist_acc(l), s));
+    else HIP_TRY(launch_distance(l->dtype, flat, peer, l->n, dist_acc(l), s));
+    return DPWA_OK;
+}
+
+static int distance_after(dpwa_learner *l, hipStream_t s)
+{
+    int64_t n = l->n;
+    if (l->dtype == DPWA_MIXED) {   // the element slots of its segments
+        n = 0;
+        for (int i = 0; i < l->layout.count; ++i)
+            n += l->layout.seg[i].byte_length / (int64_t)dtype_size(l->layout.seg[i].dtype);
+    }
+    HIP_TRY(launch_distance_finish(dist_acc(l), dist_record(l), &l->ctl->coef, n, s));
+    return DPWA_OK;
+}
+
 static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
+    if (l->track) {   // never p.relay: relay_phase2 refuses to defer for a tracking learner
+        const bool fused = !p.mixed && ((((uintptr_t)p.flat | (uintptr_t)p.peer | (uintptr_t)p.snap) & 15) == 0);
+        if (fused) {
+            HIP_TRY(launch_average_tracked(l->dtype, p.flat, p.peer, l->n, p.fa, p.snap, p.oop, dist_acc(l), s,
+                                           take_timing(l)));
+            return distance_after(l, s);
+        }
+        if (int rc = distance_before(l, p.flat, p.peer, s)) return rc;
+    }
     if (p.mixed) {   // never p.relay: relay_phase2 refuses to defer for a segmented payload
         HIP_TRY(launch_average_mixed(l->layout, p.flat, p.peer, p.fa, p.snap, s, take_timing(l), p.oop));
     } else if (p.relay) {
@@ -1494,7 +1636,7 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
         const LaunchTiming *timing = ((uintptr_t)p.flat & 15) == 0 ? take_timing(l) : nullptr;
         HIP_TRY(launch_average(l->dtype, p.flat, p.peer, l->n, p.fa, p.snap, s, timing, p.oop));
     }
-    return DPWA_OK;
+    return l->track ? distance_after(l, s) : DPWA_OK;
 }
 
 static int average_impl(dpwa_learner *l, void *flat, double loss, const double *loss_dev, hipStream_t s,
@@ -1534,7 +1676,13 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
         }
         AvgBatch b{};
         const LaunchTiming *timing = take_timing(la);
+        dpwa_learner *tracking[kMaxAvgBatch];   // the dispatch stays as it is: their passes go around it
+        int tracking_entry[kMaxAvgBatch], n_tracking = 0;
         auto add = [&](dpwa_learner *l, const AvgPlan &p) {
+            if (l->track) {
+                tracking[n_tracking] = l;
+                tracking_entry[n_tracking++] = b.count;
+            }
             AvgEntry &e = b.e[b.count++];
             e.param = p.flat;
             e.peer = p.peer;
@@ -1552,7 +1700,13 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
             add(ls[ic], plans[ic]);
             done[c] = 1;
         }
+        for (int t = 0; t < n_tracking; ++t) {
+            const AvgEntry &e = b.e[tracking_entry[t]];
+            if (int rc = distance_before(tracking[t], e.param, (const char *)e.peer, s)) return rc;
+        }
         HIP_TRY(launch_average_batch(la->dtype, pa.write_through, b, s, timing, pa.oop));
+        for (int t = 0; t < n_tracking; ++t)
+            if (int rc = distance_after(tracking[t], s)) return rc;
     }
     return DPWA_OK;
 }
@@ -1656,6 +1810,44 @@ int dpwa_average_many_resident(int32_t dtype, const dpwa_average_desc *descs, in
 {
     return average_many_impl("dpwa_average_many_resident", dtype, descs, count, cfg, stream, start_event, stop_event,
                              true);
+}
+
+int dpwa_learner_set_distance(dpwa_learner *l, int on)
+{
+    if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_distance: NULL learner");
+    if (!on) {
+        l->track = false;
+        return DPWA_OK;
+    }
+    if (l->relay_deferred)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_set_distance: a fused relay second phase is pending "
+                                         "(dpwa_learner_relay_phase2 with fuse != 0), which reads no contiguous peer "
+                                         "snapshot to measure against");
+    if (!l->dist_mem) {   // once, here: never inside a round
+        DeviceGuard dg(l->device);
+        const size_t bytes = (size_t)kDistanceWorkspaceBytes + sizeof(dpwa_distance);
+        char *mem = nullptr;
+        HIP_TRY(hipMalloc(&mem, bytes));
+        hipError_t e = hipMemset(mem, 0, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void)hipFree(mem);
+            return set_error(DPWA_ERR_HIP, "dpwa_learner_set_distance: %s", hipGetErrorString(e));
+        }
+        l->dist_mem = mem;
+    }
+    l->track = true;
+    return DPWA_OK;
+}
+
+int dpwa_learner_distance(dpwa_learner *l, const dpwa_distance **dev)
+{
+    if (!l || !dev) return set_error(DPWA_ERR_ARG, "dpwa_learner_distance: NULL argument");
+    if (!l->dist_mem)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_distance: distance tracking was never switched on "
+                                         "(dpwa_learner_set_distance)");
+    *dev = dist_record(l);
+    return DPWA_OK;
 }
 
 int dpwa_learner_set_header_publish(dpwa_learner *l, int always)
@@ -1998,6 +2190,10 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
     if (fuse && l->dtype == DPWA_MIXED)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_phase2: the fused second phase is not built for segmented "
                                        "(DPWA_MIXED) payloads; gather (fuse = 0)");
+    if (fuse && l->track)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
+                                         "snapshot, so a learner that tracks the distance (dpwa_learner_set_distance) "
+                                         "cannot use it; gather (fuse = 0)");
     RelayArgs a;
     int rc = relay_args(l, picks_dev, version, a);
     if (rc) return rc;

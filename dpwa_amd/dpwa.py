@@ -192,15 +192,105 @@ class DeviceFactor:
         return "DeviceFactor(%r)" % float(self)
 
 
+class PeerDistance:
+    """How far the learner's parameters were from the snapshot they were last averaged with
+    (``DpwaConnection(..., track_distance=True)``; dpwa_distance in include/dpwa_hip.h): over the
+    elements p of the parameters and q of the snapshot, both as they were BEFORE the average,
+    ``dist2 = sum (q - p)^2`` and ``norm2 = sum p^2`` in float64, written by the round's averaging
+    on the device next to the clock that round committed.
+
+    ``tensor()`` is a float64 device view of ``[dist2, norm2, clock]`` -- no copy, no host sync; it
+    always shows the newest round that averaged (read it in order with the stream that averaged).
+    ``distance`` (sqrt(dist2)), ``norm`` (sqrt(norm2)), ``relative`` (sqrt(dist2 / norm2)) and
+    ``clock`` are Python floats read from that record, so each of them synchronises with the
+    stream that averaged: a loop that logs every k rounds pays one small read every k rounds.
+
+    The sums are added across workgroups in no fixed order, so -- unlike everything else this
+    library computes -- they are not bit-exact from run to run, only to (n - 1) * 2**-53 relative."""
+
+    def __init__(self, learner):
+        self._learner = learner
+        self._t = None
+        self._raw = None
+
+    def _ptr(self):
+        learner = self._learner
+        if learner._h is None:
+            raise RuntimeError("the connection this distance belongs to is closed")
+        p = ctypes.c_void_p()
+        _lib.call("dpwa_learner_distance", learner.handle, ctypes.byref(p))
+        return p.value
+
+    def tensor(self):
+        if self._t is None:
+            from .devview import device_tensor
+            # (device_tensor describes bytes; the record is 8-byte aligned, so they view as float64)
+            self._t = device_tensor(self._ptr(), 24, torch.uint8, self._learner.device).view(torch.float64)
+        return self._t
+
+    def read(self):
+        """The whole record as a ``_lib.Distance`` (dist2, norm2, clock, n); synchronises."""
+        if self._raw is None:
+            from .devview import device_tensor
+            self._raw = device_tensor(self._ptr(), ctypes.sizeof(_lib.Distance), torch.uint8, self._learner.device)
+        elif self._learner._h is None:
+            raise RuntimeError("the connection this distance belongs to is closed")
+        rec = _lib.Distance()
+        torch.frombuffer(rec, dtype=torch.uint8).copy_(self._raw)
+        return rec
+
+    @property
+    def distance(self):
+        return float(self.read().dist2) ** 0.5
+
+    @property
+    def norm(self):
+        return float(self.read().norm2) ** 0.5
+
+    @property
+    def relative(self):
+        rec = self.read()
+        if rec.norm2 == 0.0:
+            return 0.0 if rec.dist2 == 0.0 else float("inf")
+        return (rec.dist2 / rec.norm2) ** 0.5
+
+    @property
+    def clock(self):
+        return float(self.read().clock)
+
+    def __repr__(self):
+        rec = self.read()
+        return "PeerDistance(dist2=%r, norm2=%r, clock=%r, n=%d)" % (rec.dist2, rec.norm2, rec.clock, rec.n)
+
+
+TRACKED_RELAY_AVG = ("pull='relay-avg' is not available with track_distance=True: the relay's fused second phase "
+                     "reads the peer's snapshot stripe by stripe and leaves no contiguous snapshot to measure the "
+                     "distance against; use 'relay' (the same relay, gathered first), 'kernel' or 'copy', or leave "
+                     "track_distance off")
+
+
 class DpwaConnection:
-    def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None):
+    def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None, track_distance=False):
         """layout (extension): ``FlatParameters.layout`` when the flat buffer given to update_send
         is the segmented ``torch.uint8`` buffer of a model that mixes dtypes (dpwa_amd/flat.py);
-        every peer must hold the same layout."""
+        every peer must hold the same layout.
+
+        track_distance (extension, off by default): every round that averages also measures how far
+        the parameters were from the snapshot they were averaged with (``last_distance``,
+        :class:`PeerDistance`).  The fused average of a single-dtype model does it inside the
+        averaging kernel, from the operands it holds anyway; a mixed-dtype model, an unaligned
+        buffer, ``update_wait()`` + ``average()`` and ``update_wait_average_many`` run a separate
+        pass before the average and pay 2*n*s more bytes read.  Not available with
+        ``pull='relay-avg'``.  It is a constructor argument only (the YAML schema is the
+        reference's)."""
         self.name = name
         self._layout = tuple(layout) if layout is not None else None
+        self._track_distance = bool(track_distance)
+        self._last_distance = None
         if self._layout is not None and pull is not None and pull.partition(":")[0] == "relay-avg":
             raise ValueError(MIXED_RELAY_AVG)
+        if self._track_distance and pull is not None and pull.partition(":")[0] == "relay-avg":
+            raise ValueError(TRACKED_RELAY_AVG)
         self.config = DpwaConfiguration(config_file)
         self.nodes = self.config.get_nodes()
         self.fetch_probability = self.config.get_fetch_probability()
@@ -251,6 +341,7 @@ class DpwaConnection:
         _lib.call("dpwa_node_handles", self._node, None, ctypes.byref(sched))
         self._sched = Scheduler(len(self.peers), handle=sched.value)
         self._learner = None
+        self._distance = None             # the learner's PeerDistance, once bound with tracking on
         self._pending_clock = None        # load_state_dict before the learner exists
         self._resident = False      # make_resident was called
         self._sent = None           # resident: (parameters tensor, its version) at update_send
@@ -367,6 +458,8 @@ class DpwaConnection:
             self._fail("dpwa_node_update_wait_average", rc)
         self.fetching = False
         self._sent = None
+        if self._out.value >= 0:
+            self._last_distance = self._distance
         return self._result()
 
     # ---------------------------------------------------------------- extensions
@@ -458,6 +551,7 @@ class DpwaConnection:
             for j, i in enumerate(bound):
                 if peers[j] >= 0:
                     c = conns[i]
+                    c._last_distance = c._distance
                     out[i] = (PeerSnapshot(c, peers[j], c._learner.version), DeviceFactor(c._learner))
         return out
 
@@ -475,6 +569,16 @@ class DpwaConnection:
         rc = self._f_lerp(self._node, learner._ptr(parameters), s)
         if rc:
             self._fail("dpwa_node_lerp", rc)
+        self._last_distance = self._distance
+
+    @property
+    def last_distance(self):
+        """The :class:`PeerDistance` of the newest round that averaged with ``track_distance=True``;
+        None until one has (tracking off, no update_send yet, rounds gated off or without a peer).
+        ``update_wait()`` alone leaves it as it was -- the caller's own arithmetic is not measured;
+        ``average()`` after it measures.  A round whose interpolation divides by zero averages
+        nothing and keeps the previous round's numbers."""
+        return self._last_distance
 
     def synchronize(self):
         """Waits for the device and raises a deferred ZeroDivisionError, if any."""
@@ -594,6 +698,11 @@ class DpwaConnection:
         if self._pending_clock is not None:           # load_state_dict before the first round
             self._learner.write_clock(self._pending_clock)
             self._pending_clock = None
+        if self._track_distance:                      # allocates the record here, never inside a round
+            if self._pull.partition(":")[0] == "relay-avg":
+                raise ValueError(TRACKED_RELAY_AVG)
+            _lib.call("dpwa_learner_set_distance", self._learner.handle, 1)
+            self._distance = PeerDistance(self._learner)
         if self._pull.partition(":")[0] in RELAY_PULLS:
             if not hasattr(self._group, "relay_blocks"):
                 raise ValueError("the relay pull needs a DistGroup (one learner per rank)")
@@ -615,6 +724,8 @@ class DpwaConnection:
                              "got %r" % mode)
         if kind == "relay-avg" and self._layout is not None:
             raise ValueError(MIXED_RELAY_AVG)
+        if kind == "relay-avg" and self._track_distance:
+            raise ValueError(TRACKED_RELAY_AVG)
         self._pull = mode
         learner = self._learner
         if learner is None:

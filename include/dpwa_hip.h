@@ -30,7 +30,10 @@ extern "C" {
 /* 11: DPWA_F16 -- float16 parameters through every averaging form, dpwa_lerp_f16{,_host}.
  * Still 11, by additions only (every ABI-11 caller runs unchanged): DPWA_MIXED -- segmented payloads
  * (dpwa_layout): dpwa_average_mixed, dpwa_layout_digest, dpwa_learner_set_layout,
- * dpwa_node_set_layout; the IPC handle carries the layout digest in bytes that were zero. */
+ * dpwa_node_set_layout; the IPC handle carries the layout digest in bytes that were zero.
+ * Still 11, by additions only: the distance to the peer (dpwa_distance) -- dpwa_distance_workspace,
+ * dpwa_measure_distance, dpwa_measure_distance_mixed, dpwa_average_tracked, dpwa_distance_finish,
+ * dpwa_learner_set_distance, dpwa_learner_distance. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -189,6 +192,55 @@ int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_
                        double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, dpwa_stream_t stream,
                        void *start_event, void *stop_event);
 
+/* The distance to the peer (extension, opt-in; no reference interface): how far the parameters p
+ * were from the snapshot q they were averaged with, both read BEFORE the average, over the n elements:
+ *   dist2 = sum (double(q_i) - double(p_i))^2      norm2 = sum double(p_i)^2
+ * every element widened exactly to fp64, every difference, product and sum in fp64; subnormals count,
+ * a NaN anywhere gives NaN, no finite input overflows; padding bytes of a DPWA_MIXED layout are zeros
+ * and add 0.  `clock` is the clock the round committed (which round the sums belong to; 0 from the
+ * stateless dpwa_measure_distance); `n` the elements summed over (a DPWA_MIXED payload: the element
+ * slots of its segments, padding included).  A round that does not average (no fetch, or the
+ * ZeroDivision no-op) leaves the record untouched.  The sums are added across workgroups with hardware
+ * fp64 atomic adds, whose order is not fixed: the record is this library's one output that is NOT
+ * bit-exact from run to run -- it is reproducible to (n - 1) * 2^-53 relative (every term is >= 0).
+ *
+ * workspace: dpwa_distance_workspace() bytes of ordinary device memory (hipMalloc), 16-B aligned, zero
+ * before the first use; every entry below leaves it zero again, so one workspace serves any number of
+ * rounds of one stream (not two streams at once).  Its size does not depend on n: it holds
+ * bytes / DPWA_DISTANCE_ACC_STRIDE accumulators, and the 1-KiB span s of the operands adds into
+ * accumulator s modulo that count.
+ *   dpwa_measure_distance        the stand-alone pass: reads n elements of `param` and of `peer_payload`
+ *                                (any element alignment), stores nothing to either, writes *out_dev.
+ *   dpwa_measure_distance_mixed  the same for a DPWA_MIXED payload (16-B aligned buffers of the layout's bytes).
+ *   dpwa_average_tracked         dpwa_average whose kernel also forms the sums from the operands it holds
+ *                                in registers anyway (no extra bytes): the averaged parameters, the
+ *                                snapshot, the clock and *coef_dev are exactly dpwa_average's.  16-B
+ *                                aligned operands run the tracked kernel; others the stand-alone pass
+ *                                followed by dpwa_average's kernel.  The events time the averaging kernel.
+ *   dpwa_distance_finish         the finishing step alone (what the entries above end with): sums the
+ *                                accumulators into *out_dev and zeroes them; coef_dev non-NULL: the record
+ *                                is written only when its status is DPWA_STATUS_OK, with its new_clock.
+ *                                Events as dpwa_average (measurement).
+ * DPWA_ERR_ARG (no device touched) for NULL pointers, n < 0, an unknown dtype, DPWA_MIXED without its
+ * layout, an invalid layout or a misaligned workspace / record. */
+#define DPWA_DISTANCE_ACC_STRIDE 128
+typedef struct dpwa_distance {
+    double dist2;
+    double norm2;
+    double clock;
+    int64_t n;
+} dpwa_distance;
+int dpwa_distance_workspace(int64_t *bytes);
+int dpwa_measure_distance(int32_t dtype, const void *param, const void *peer_payload, int64_t n, void *workspace,
+                          dpwa_distance *out_dev, dpwa_stream_t stream);
+int dpwa_measure_distance_mixed(const dpwa_layout *layout, const void *param, const void *peer_payload,
+                                void *workspace, dpwa_distance *out_dev, dpwa_stream_t stream);
+int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int64_t n, const dpwa_interp *cfg,
+                         double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, void *workspace,
+                         dpwa_distance *out_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
+int dpwa_distance_finish(void *workspace, dpwa_distance *out_dev, const dpwa_coef *coef_dev, int64_t n,
+                         dpwa_stream_t stream, void *start_event, void *stop_event);
+
 /* dpwa_average over several independent (param, peer slot) pairs in ONE dispatch -- the averages
  * of co-resident learners of one round (pytorch.py:66-68 once per learner).  Each descriptor is
  * one dpwa_average call: its own clock_dev (reads [0], writes [1]), coefficient block and loss;
@@ -340,6 +392,25 @@ int dpwa_learner_average_through(dpwa_learner *l, void *flat, double loss, const
 int dpwa_learner_average_many(dpwa_learner *const *learners, void *const *flats, const double *loss,
                               const double *const *loss_dev, const int *write_through, int count,
                               dpwa_stream_t stream);
+/* Distance tracking (dpwa_distance above; off by default, and off every launch is the untracked one).
+ * set_distance(on != 0) allocates the workspace and the record once, here -- never inside a round --
+ * and from then on every round of this learner that averages writes the record:
+ *   single dtype, 16-B aligned, contiguous peer snapshot     the tracked kernel (no extra bytes), in the
+ *     (average / average_through / resident)                 plain, write-through and resident forms
+ *   DPWA_MIXED; unaligned parameters; the split              the stand-alone pass enqueued on the same
+ *     factor -> lerp form; an average inside                 stream BEFORE the unchanged average (the
+ *     dpwa_learner_average_many                              in-place forms overwrite what it reads):
+ *                                                            2*n*s more bytes read per round
+ *   the relay's fused second phase                           refused: dpwa_learner_relay_phase2 with
+ *                                                            fuse != 0 on a tracking learner is
+ *                                                            DPWA_ERR_STATE, and so is set_distance(on)
+ *                                                            while a fused second phase is pending
+ * A round that does not average leaves the record as it was.  dpwa_learner_distance: the record's
+ * device address (borrowed, valid until dpwa_learner_destroy; DPWA_ERR_STATE before the first
+ * set_distance(on)); read it in order with the stream that averaged. */
+int dpwa_learner_set_distance(dpwa_learner *l, int on);
+int dpwa_learner_distance(dpwa_learner *l, const dpwa_distance **dev);
+
 /* always != 0: a write-through average never writes the next publish's header ahead; that
  * publish then writes it with the loss given to it (a snapshot served over the wire bridge
  * carries the reference's {'clock', 'loss'} state, conn.py:110). */
