@@ -15,6 +15,9 @@ host test's conditions on the list (the NaN cap, the mutants) hold for what the 
 is an int (``sample(dtype, n, seed)``) or, for resident learners that average each other's
 parameters, a pair ``(a, b)``: the parameters of ``sample(dtype, n, a)`` meeting those of
 ``sample(dtype, n, b)``.
+
+The "pull" form is tests/test_gpu_moves.py's: a snapshot pulled by the copy kernel or the copy
+engine at the sizes of ``moves_ref.pull_sizes`` and then averaged with the constant factor 0.3.
 """
 import functools
 
@@ -22,7 +25,7 @@ import numpy as np
 
 from oracle import lerp as olerp
 from oracle import policy as opolicy
-from tests import f16_ref
+from tests import f16_ref, moves_ref
 from tests.mixed_ref import CODE, HARD, NUMPY, SIZE, TORCH, tensor_bits  # noqa: F401  (re-exported)
 from tests.test_gpu_f16 import FUSED
 
@@ -167,10 +170,24 @@ def worker_sizes(dtype, wide=False):
 
 
 PLAIN_FACTORS = (0.3, 0.0, 1.0, 1.5)
+PULL_FACTOR = 0.3
 UNALIGNED_N = 1003
 UNALIGNED_OFFSETS = [(1, 0), (0, 3), (2, 2), (7, 5)]          # (parameters, peer / snapshot), in elements
 UNALIGNED_CASE = FUSED[1]                                      # clock interpolation, 3 and 7
 ZERO_DIVISION = ("clock", None, 0.0, 0.0, 0.0, 1.0, 1.0)       # interpolation.py:22-24 with both clocks 0
+
+
+def pull_elements(dtype):
+    """Elements of the payloads of moves_ref.pull_sizes, over every cap of the pull's grid."""
+    return sorted({b // SIZE[dtype] for cap in moves_ref.PULL_BLOCKS for b in moves_ref.pull_sizes(cap)})
+
+
+def ragged_publish_elements(dtype):
+    """tests/forms_worker.py run_publish: the element counts nearest (on both sides) to the payload
+    byte counts of moves_ref.PUBLISH_BYTES that leave tail bytes behind the last 16-byte word."""
+    s = SIZE[dtype]
+    counts = {m for b in moves_ref.PUBLISH_BYTES for m in (b // s, -(-b // s)) if m > 0}
+    return sorted(m for m in counts if (m * s) & 15)
 
 
 def fused_factor(case):
@@ -254,6 +271,8 @@ def _tuples_at(dtype, n, base, forms):
                 res = resident_factor(name, j)
                 if res is not None:
                     out.append((dtype, n, (base + a, base + b), res[0]))
+    if "pull" in forms:
+        out.append((dtype, n, base, PULL_FACTOR))
     return out
 
 
@@ -268,11 +287,13 @@ def forms_at(dtype, n):
         forms.add("many")
     if n in resident_sizes(dtype):
         forms.add("resident")
+    if n in pull_elements(dtype):
+        forms.add("pull")
     return forms
 
 
 def all_sizes(dtype):
-    return sorted(set(resident_sizes(dtype) + worker_sizes(dtype, wide=True) + [UNALIGNED_N]))
+    return sorted(set(resident_sizes(dtype) + worker_sizes(dtype, wide=True) + [UNALIGNED_N] + pull_elements(dtype)))
 
 
 # sample seeds per (dtype, n); entry or learner i of a dispatch uses the seed plus i.  1 unless the

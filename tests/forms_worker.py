@@ -281,7 +281,7 @@ def run_resident(dtype, name, n):
 def run_publish(dtype, n):
     """One Learner.publish of a ragged payload (bytes & 15 != 0), read back with read_snapshot."""
     assert (n * SIZE[dtype]) & 15
-    bits = ref.operands(dtype, n, ref.seed_of(dtype, n))[0]
+    bits = ref.operands(dtype, n, ref.SEEDS.get((dtype, n), 1))[0]
     flat = source(dtype, bits)
     lr = Learner(DEV, n, TORCH[dtype], _lib.Interp(_lib.INTERP_CONSTANT, 0, 0.5, 0.0))
     try:
@@ -318,7 +318,8 @@ def main():
             for n in ref.worker_sizes(dtype):
                 run_resident(dtype, name, n)
         if os.environ.get("DPWA_PUBLISH_BLOCK"):
-            run_publish(dtype, ref.worker_sizes(dtype)[1])
+            for n in [ref.worker_sizes(dtype)[1]] + ref.ragged_publish_elements(dtype):
+                run_publish(dtype, n)
     print("forms_worker: ok")
 
 

@@ -24,6 +24,7 @@ VARIANTS = [
     ("DPWA_BATCH_SHARE", "0"),
     ("DPWA_BATCH_ORDER", "contiguous"),
     ("DPWA_BATCH_ORDER", "interleaved"),
+    ("DPWA_PUBLISH_BLOCK", "128"),
     ("DPWA_PUBLISH_BLOCK", "256"),
 ]
 CHILD_TIMEOUT_S = 120                    # a cap against a hang, not an expectation
