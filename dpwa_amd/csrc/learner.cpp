@@ -27,6 +27,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "order.hpp"
 
 namespace {
 
@@ -91,6 +92,53 @@ struct DevMem {
     size_t chunk = 0;
     std::vector<hipMemGenericAllocationHandle_t> handles;   // VMM chunks; empty: hipMalloc
     bool vmm() const { return !handles.empty(); }
+
+    DevMem() = default;
+    DevMem(DevMem &&o) noexcept { *this = std::move(o); }
+    DevMem &operator=(DevMem &&o) noexcept   // `o` leaves with what this held, and frees it
+    {
+        std::swap(ptr, o.ptr);
+        std::swap(bytes, o.bytes);
+        std::swap(chunk, o.chunk);
+        handles.swap(o.handles);
+        return *this;
+    }
+    ~DevMem()
+    {
+        if (!ptr) return;
+        if (vmm()) {
+            (void)hipMemUnmap(ptr, bytes);
+            for (auto h : handles) (void)hipMemRelease(h);
+            (void)hipMemAddressFree(ptr, bytes);
+        } else {
+            (void)hipFree(ptr);
+        }
+    }
+};
+
+// Owners of the plain HIP objects a learner holds, like order.hpp's of the events.
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {   // non-blocking
+    hipError_t create() { return hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+    hipError_t create(int priority) { return hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority); }
+};
+struct DevBuf : Owned<void *, hipFree> {
+    hipError_t alloc(size_t bytes) { return hipMalloc(&h, bytes); }
+    char *ptr() const { return (char *)h; }
+};
+
+// One pinned 32-bit word, zero at first, that the device writes through `dev` and the host polls
+// through host() without waiting for anything.
+template <class T> struct HostWord : Owned<void *, hipHostFree> {
+    static_assert(sizeof(T) == 4, "a 32-bit word");
+    T *dev = nullptr;
+    T *host() const { return (T *)h; }
+    hipError_t alloc()
+    {
+        hipError_t e = hipHostMalloc(&h, sizeof(T), hipHostMallocMapped);
+        if (e != hipSuccess) return e;
+        *host() = 0;
+        return hipHostGetDevicePointer((void **)&dev, h, 0);
+    }
 };
 
 hipMemAllocationProp vmm_prop(int device)
@@ -114,19 +162,6 @@ hipError_t vmm_grant(const DevMem &m, int device)
     return hipMemSetAccess(m.ptr, m.bytes, &a, 1);
 }
 
-void devmem_free(DevMem &m)
-{
-    if (!m.ptr) return;
-    if (m.vmm()) {
-        (void)hipMemUnmap(m.ptr, m.bytes);
-        for (auto h : m.handles) (void)hipMemRelease(h);
-        (void)hipMemAddressFree(m.ptr, m.bytes);
-    } else {
-        (void)hipFree(m.ptr);
-    }
-    m = DevMem();
-}
-
 // Maps `n` chunks (VMM handles in h[]) contiguously into a fresh reservation, readable and
 // writable from `device`; releases the handles on failure.
 hipError_t vmm_map(DevMem &m, std::vector<hipMemGenericAllocationHandle_t> &h, size_t chunk, int device)
@@ -140,20 +175,21 @@ hipError_t vmm_map(DevMem &m, std::vector<hipMemGenericAllocationHandle_t> &h, s
         for (; mapped < h.size(); ++mapped)
             if ((e = hipMemMap((char *)va + mapped * chunk, chunk, 0, h[mapped], 0)) != hipSuccess) break;
     }
-    m.ptr = (char *)va;
-    m.bytes = total;
-    m.chunk = chunk;
-    if (e == hipSuccess) {
+    if (e == hipSuccess) {   // fully mapped: `m` owns it, and gives it back if the grant fails
+        m.ptr = (char *)va;
+        m.bytes = total;
+        m.chunk = chunk;
         m.handles = h;
         if ((e = vmm_grant(m, device)) == hipSuccess) return hipSuccess;
+        m = DevMem();
+    } else {
+        if (va) {
+            if (mapped) (void)hipMemUnmap(va, mapped * chunk);
+            (void)hipMemAddressFree(va, total);
+        }
+        for (auto x : h) (void)hipMemRelease(x);
     }
-    if (va) {
-        if (mapped) (void)hipMemUnmap(va, mapped * chunk);
-        (void)hipMemAddressFree(va, total);
-    }
-    for (auto x : h) (void)hipMemRelease(x);
     h.clear();
-    m = DevMem();
     return e;
 }
 
@@ -298,7 +334,7 @@ static void close_endpoint(Endpoint &ep)
 {
     if (ep.kind != 2 || !ep.base) return;
     if (ep.imported.vmm())
-        devmem_free(ep.imported);
+        ep.imported = DevMem();
     else
         (void)hipIpcCloseMemHandle(ep.base);
     ep.base = nullptr;
@@ -322,24 +358,76 @@ constexpr size_t kRescueShare = 8;
 constexpr int64_t kMaxBacklogMs = 60000;
 constexpr int64_t kProbeWaitUs = 2000;
 constexpr size_t kRescueReserve = (size_t)1 << 30;
+namespace {
+
 struct RescueLane {
-    char *buf = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_landed = nullptr;     // its last pull landed
-    hipEvent_t ev_done = nullptr;       // the last reader of its buffer is done
-    bool used = false;                  // a pull was issued into it
-    bool read = false;                  // ev_done recorded
+    DevBuf buf;
+    Stream stream;
+    DoneEvent landed;                   // its last pull landed (recorded: a pull was issued into it)
+    DoneEvent done;                     // the last reader of its buffer is done
     uint64_t last_round = 0;            // fetch round of its last pull
 };
 
-void destroy_lane(RescueLane &r)
-{
-    if (r.buf) (void)hipFree(r.buf);
-    if (r.stream) (void)hipStreamDestroy(r.stream);
-    if (r.ev_landed) (void)hipEventDestroy(r.ev_landed);
-    if (r.ev_done) (void)hipEventDestroy(r.ev_done);
-    r = RescueLane();
-}
+struct Probe {   // fetch_state's clock (probe_since): a stream that only ever holds `ev`, a timing event
+    Stream stream;
+    Event ev;
+};
+
+// Window guard (resident, with reuse_guard): each publish checks the payload published last time
+// against the samples saved then and saves the new payload's (kernels.hip k_window_roll); written
+// windows are counted on the device and mirrored into a host-mapped word the next publishes read
+// without waiting.  Made at first use (window_alloc).
+struct WindowGuard {
+    DevBuf sample;                      // kWindowSampleBytes
+    HostWord<uint32_t> hits;            // windows found written (device-written)
+    StreamMark rolled;                  // the last roll: a roll on another stream runs after it
+    const char *src = nullptr;          // payload the samples were taken from (NULL: none)
+    int32_t gen = 0;
+    uint32_t reported = 0;
+};
+
+// Begin/end event pairs for timed launches (bench), handed out in order.
+struct TimingRing {
+    std::vector<LaunchTiming> pairs;
+    int used = 0;
+
+    TimingRing() = default;
+    TimingRing(const TimingRing &) = delete;
+    ~TimingRing() { (void)reserve(0); }
+    // `capacity` fresh pairs in place of the old ones (the caller has synchronised the device)
+    hipError_t reserve(int capacity)
+    {
+        for (auto &t : pairs) {
+            if (t.start) (void)hipEventDestroy(t.start);
+            if (t.stop) (void)hipEventDestroy(t.stop);
+        }
+        pairs.assign((size_t)capacity, LaunchTiming{});
+        used = 0;
+        hipError_t e = hipSuccess;
+        for (auto &t : pairs)
+            if (e == hipSuccess && (e = hipEventCreate(&t.start)) == hipSuccess) e = hipEventCreate(&t.stop);
+        if (e != hipSuccess) (void)reserve(0);   // none rather than some
+        return e;
+    }
+    // the next unused pair, or NULL when all are taken
+    const LaunchTiming *take() { return used < (int)pairs.size() ? &pairs[used++] : nullptr; }
+    // microseconds of the pairs taken so far, at most `max` (waits for each to complete)
+    hipError_t read(float *us_out, int max, int *count) const
+    {
+        const int k = used < max ? used : max;
+        for (int i = 0; i < k; ++i) {
+            float ms = 0.f;
+            hipError_t e = hipEventSynchronize(pairs[i].stop);
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, pairs[i].start, pairs[i].stop);
+            if (e != hipSuccess) return e;
+            us_out[i] = ms * 1000.f;
+        }
+        *count = k;
+        return hipSuccess;
+    }
+};
+
+}  // namespace
 
 struct dpwa_learner {
     int device = 0;
@@ -352,33 +440,27 @@ struct dpwa_learner {
     dpwa_interp cfg{};
     size_t payload_bytes = 0;
     size_t slot_stride = 0;
-    char *slots = nullptr;          // 2 slots (= slot_mem.ptr)
-    DevMem slot_mem;
-    char *staging = nullptr;        // 1 slot
-    Ctl *ctl = nullptr;
+    // Every HIP object below has an owner that frees it: `delete` tears a learner down (after
+    // dpwa_learner_destroy's device sync nothing is in flight, so the members go in any order).
+    DevMem slot_mem;                // 2 slots
+    DevBuf staging;                 // 1 slot
+    Ctl *ctl = nullptr;             // (= ctl_mem.ptr())
+    DevBuf ctl_mem;
     uint64_t version = 0;
     int cur = 0;                        // index of the live clock in ctl->clock (mod 4)
     bool exported = false;
-    hipStream_t side = nullptr;
-    // Cross-stream ordering is recorded lazily: the stream of every publish / consumption is
-    // remembered and an event is recorded (on that stream, at the moment a dependent
-    // operation is enqueued) only when the dependent operation runs on a different stream.
-    // In the common single-stream loop no event is recorded at all.
-    hipEvent_t ev_published[2] = {nullptr, nullptr};
-    hipStream_t publish_stream[2] = {nullptr, nullptr};
-    bool published[2] = {false, false};
-    hipEvent_t ev_issue = nullptr;      // fetch may start (recorded on the caller's stream)
-    hipEvent_t ev_fetched = nullptr;    // fetch landed (recorded on the side stream)
-    hipEvent_t ev_consumed = nullptr;   // this learner finished reading its fetch source
-    hipStream_t consume_stream = nullptr;
-    bool consumed_once = false;
+    Stream side;
+    // who waits for whom across streams (order.hpp)
+    StreamMark published[2];            // slot k's publish (noted under pub_mu)
+    Event ev_issue;                     // fetch may start (recorded on the caller's stream); timed
+    DoneEvent fetched;                  // fetch landed (recorded on the stream that moved it)
+    StreamMark consumed;                // this learner finished reading its fetch source
     // Fetches of published snapshots (DPWA_FETCH_PUBLISHED: the gossip board) alternate between
     // two staging buffers and are not ordered after the caller's stream: each waits only for
-    // the average that last read its buffer (ev_stage_done), so a pull starts at update_send
+    // the average that last read its buffer (stage_done), so a pull starts at update_send
     // instead of after the caller's queued work, and a peer's read mark is released sooner.
-    char *staging_alt = nullptr;        // second staging buffer, allocated at the first such fetch
-    hipEvent_t ev_stage_done[2] = {nullptr, nullptr};
-    bool stage_read[2] = {false, false};
+    DevBuf staging_alt;                 // second staging buffer, allocated at the first such fetch
+    DoneEvent stage_done[2];
     // rescue lanes (RescueLane), allocated at first use: a lane whose pull has not landed stays
     // taken and the next re-selected pull takes another, as TxThread keeps re-selecting
     RescueLane rescue[kMaxRescueLanes];
@@ -389,18 +471,18 @@ struct dpwa_learner {
     // the fetch in flight waits for ev_issue (the caller's stream at update_send): its deadline runs
     // from when that point is reached, not from the host's enqueue (fetch_state)
     bool issue_evented = false;
-    hipStream_t probe_stream = nullptr; // only ever holds ev_probe (fetch_state)
-    hipEvent_t ev_probe = nullptr;
-    hipStream_t fetch_stream = nullptr; // stream the fetch in flight moves its bytes on
+    Probe probe;                        // made at the first probe (probe_since)
+    hipStream_t fetch_stream = nullptr; // stream the fetch in flight moves its bytes on (not owned)
     int stage_next = 0;
     int src_stage = -1;                 // buffer l->src points into: staging 0 / 1, rescue lane 2 + j; -1: none
-    hipEvent_t ev_factor = nullptr;     // last factor computation done
-    // write-through snapshot: the last average also wrote its result into the slot of the
-    // next publish (for the flat buffer `wt_flat`, on stream `wt_stream`)
+    DoneEvent factor_done;              // last factor computation done
     int pull_mode = DPWA_PULL_COPY_ENGINE;   // how cross-device fetches move bytes
     int pull_blocks = 512;
     bool loss_f32 = false;              // device loss pointers point at a float32
-    bool wt_valid = false;
+    // write-through snapshot: the last average also wrote its result into the slot of the
+    // next publish (for the flat buffer `wt_flat`; noted while that holds: set_written_through)
+    StreamMark written_through;
+    const void *wt_flat = nullptr;
     bool wt_header = false;             // the write-through average also wrote the next header
     bool header_on_publish = false;     // never write the next header ahead (served to wire peers)
     bool reuse_guard = false;           // check a header-only publish's parameters on the device
@@ -408,40 +490,22 @@ struct dpwa_learner {
     // move to the other slot at every average (or relocate)
     bool resident = false;
     int res_slot = 0;
-    // window guard (resident, with reuse_guard): each publish checks the payload published last
-    // time against the samples saved then and saves the new payload's (kernels.hip k_window_roll);
-    // written windows are counted on the device and mirrored into a host-mapped word the next
-    // publishes read without waiting
-    char *window_sample = nullptr;      // kWindowSampleBytes, allocated at first use
-    uint32_t *window_host = nullptr;    // mapped pinned: windows found written (device-written)
-    uint32_t *window_host_dev = nullptr;
-    const char *window_src = nullptr;   // payload the samples were taken from (NULL: none)
-    hipStream_t window_stream = nullptr;    // stream of the last roll
-    hipEvent_t ev_window = nullptr;     // orders a roll after the last one on another stream
-    int32_t window_gen = 0;
-    uint32_t window_reported = 0;
-    const void *wt_flat = nullptr;
-    hipStream_t wt_stream = nullptr;
-    hipEvent_t ev_wt = nullptr;
+    WindowGuard window;
     // timing of the averaging launches (bench): kernel begin/end events, filled in order
-    std::vector<LaunchTiming> timing;
-    int timing_used = 0;
+    TimingRing avg_times;
     bool timing_armed = false;   // time the next averaging launch (one-shot)
     // timing of copying fetches (bench at N > 1: the pull over xGMI), filled in order
-    std::vector<LaunchTiming> fetch_timing;
-    int fetch_timing_used = 0;
+    TimingRing fetch_times;
     // relay transport (multi-link lock-step pulls), see kernels.hip
     bool relay_on = false;
     int relay_world = 0, relay_rank = 0;
     int64_t relay_stripe = 0;
-    char *relay_buf = nullptr;               // world x stripe, IPC-exported (= relay_mem.ptr)
-    DevMem relay_mem;
+    DevMem relay_mem;                        // world x stripe, IPC-exported
     std::vector<const char *> relay_slots;   // per rank: slot 0 base (own or IPC-mapped)
     std::vector<const char *> relay_bufs;    // per rank: relay buffer (own or IPC-mapped)
-    std::vector<char *> relay_opened;        // IPC mappings to close
-    std::vector<DevMem> relay_imported;      // fd-imported relay buffers to unmap
-    hipEvent_t ev_relay = nullptr;           // all relay work of the last round
-    bool relay_pending = false;
+    std::vector<char *> relay_opened;        // IPC mappings to close (dpwa_learner_destroy)
+    std::vector<DevMem> relay_imported;      // fd-imported relay buffers
+    DoneEvent relay_done;                    // all relay work of the last round
     // phase 2 deferred into the average (dpwa_learner_relay_phase2 with fuse != 0): the stripes
     // are read where phase 1 left them by the next fused average, or gathered into staging
     // first if the fetch is consumed any other way (relay_materialize)
@@ -451,8 +515,8 @@ struct dpwa_learner {
     // host readers of published slots (wire bridge) run on other threads; their stream is created
     // at the first read, under pub_mu
     std::mutex pub_mu;
-    hipStream_t read_stream = nullptr;
-    hipEvent_t ev_read = nullptr;
+    Stream read_stream;
+    Event ev_read;
     // fetch state
     const char *src = nullptr;          // header of the snapshot to average with
     bool src_copied = false;
@@ -467,18 +531,17 @@ struct dpwa_learner {
     // distance tracking (dpwa_learner_set_distance): the accumulators and, behind them, the record;
     // allocated when first switched on, kept until destroy
     bool track = false;
-    char *dist_mem = nullptr;
-    int32_t *host_status = nullptr;     // pinned mirror of coef.status for non-blocking polls
-    int32_t *host_status_dev = nullptr; // its device-side address
+    DevBuf dist_mem;
+    HostWord<int32_t> status;           // pinned mirror of coef.status for non-blocking polls
 };
 
 static char *slot_payload(const dpwa_learner *l, int k)
 {
-    return l->slots + (size_t)k * l->slot_stride + kPayloadOff;
+    return l->slot_mem.ptr + (size_t)k * l->slot_stride + kPayloadOff;
 }
 
-static double *dist_acc(const dpwa_learner *l) { return (double *)l->dist_mem; }
-static dpwa_distance *dist_record(const dpwa_learner *l) { return (dpwa_distance *)(l->dist_mem + kDistanceWorkspaceBytes); }
+static double *dist_acc(const dpwa_learner *l) { return (double *)l->dist_mem.ptr(); }
+static dpwa_distance *dist_record(const dpwa_learner *l) { return (dpwa_distance *)(l->dist_mem.ptr() + kDistanceWorkspaceBytes); }
 
 static int64_t now_ns()
 {
@@ -492,6 +555,44 @@ static bool is_live(dpwa_learner *l)
     return g_live.count(l) != 0;
 }
 
+// ---------------------------------------------------------------- stateless entry points
+// What they share; `fn` names the entry in messages.  The six lerp wrappers' body:
+static int lerp_entry(const char *fn, int32_t dtype, void *param, const void *peer, int64_t n,
+                      const dpwa_coef *coef_dev, const double *factor, dpwa_stream_t stream)
+{
+    if (n < 0 || (n > 0 && (!param || !peer || (!factor && !coef_dev)))) return set_error(DPWA_ERR_ARG, "%s: bad arguments", fn);
+    const float f = factor ? (float)*factor : 0.f, g = factor ? (float)(1.0 - *factor) : 0.f;
+    HIP_TRY(launch_lerp(dtype, param, peer, n, factor ? nullptr : coef_dev, f, g, (hipStream_t)stream));
+    return DPWA_OK;
+}
+
+// The caller's begin/end events as a launch's timing argument: NULL when none were given.
+struct CallerTiming {
+    LaunchTiming t;
+    CallerTiming(void *start_event, void *stop_event) : t{(hipEvent_t)start_event, (hipEvent_t)stop_event} {}
+    operator const LaunchTiming *() const { return t.start ? &t : nullptr; }
+};
+
+static int check_method(const dpwa_interp *cfg, const char *fn)
+{
+    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "%s: unknown method %d", fn, cfg->method);
+    return DPWA_OK;
+}
+
+// Factor from the header of `peer_slot`, clock read at clock_dev and written behind it.
+static FusedArgs stateless_args(const dpwa_interp *cfg, double *clock_dev, const void *peer_slot, double loss,
+                                dpwa_coef *coef_dev)
+{
+    FusedArgs fa{};
+    fa.cfg = *cfg;
+    fa.clock_in = clock_dev;
+    fa.clock_out = clock_dev + 1;
+    fa.hdr = (const dpwa_header *)peer_slot;
+    fa.loss_h = loss;
+    fa.coef_out = coef_dev;
+    return fa;
+}
+
 extern "C" {
 
 const char *dpwa_last_error(void) { return g_last_error.c_str(); }
@@ -500,61 +601,44 @@ int dpwa_abi_version(void) { return DPWA_ABI_VERSION; }
 
 int dpwa_lerp_f32(float *param, const float *peer, int64_t n, const dpwa_coef *coef_dev, dpwa_stream_t stream)
 {
-    if (n < 0 || (n > 0 && (!param || !peer || !coef_dev))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_f32: bad arguments");
-    HIP_TRY(launch_lerp(DPWA_F32, param, peer, n, coef_dev, 0.f, 0.f, (hipStream_t)stream));
-    return DPWA_OK;
+    return lerp_entry("dpwa_lerp_f32", DPWA_F32, param, peer, n, coef_dev, nullptr, stream);
 }
 
 int dpwa_lerp_bf16(uint16_t *param, const uint16_t *peer, int64_t n, const dpwa_coef *coef_dev,
                    dpwa_stream_t stream)
 {
-    if (n < 0 || (n > 0 && (!param || !peer || !coef_dev))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_bf16: bad arguments");
-    HIP_TRY(launch_lerp(DPWA_BF16, param, peer, n, coef_dev, 0.f, 0.f, (hipStream_t)stream));
-    return DPWA_OK;
-}
-
-int dpwa_lerp_f32_host(float *param, const float *peer, int64_t n, double factor, dpwa_stream_t stream)
-{
-    if (n < 0 || (n > 0 && (!param || !peer))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_f32_host: bad arguments");
-    HIP_TRY(launch_lerp(DPWA_F32, param, peer, n, nullptr, (float)factor, (float)(1.0 - factor), (hipStream_t)stream));
-    return DPWA_OK;
-}
-
-int dpwa_lerp_bf16_host(uint16_t *param, const uint16_t *peer, int64_t n, double factor, dpwa_stream_t stream)
-{
-    if (n < 0 || (n > 0 && (!param || !peer))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_bf16_host: bad arguments");
-    HIP_TRY(launch_lerp(DPWA_BF16, param, peer, n, nullptr, (float)factor, (float)(1.0 - factor), (hipStream_t)stream));
-    return DPWA_OK;
+    return lerp_entry("dpwa_lerp_bf16", DPWA_BF16, param, peer, n, coef_dev, nullptr, stream);
 }
 
 int dpwa_lerp_f16(uint16_t *param, const uint16_t *peer, int64_t n, const dpwa_coef *coef_dev,
                   dpwa_stream_t stream)
 {
-    if (n < 0 || (n > 0 && (!param || !peer || !coef_dev))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_f16: bad arguments");
-    HIP_TRY(launch_lerp(DPWA_F16, param, peer, n, coef_dev, 0.f, 0.f, (hipStream_t)stream));
-    return DPWA_OK;
+    return lerp_entry("dpwa_lerp_f16", DPWA_F16, param, peer, n, coef_dev, nullptr, stream);
+}
+
+int dpwa_lerp_f32_host(float *param, const float *peer, int64_t n, double factor, dpwa_stream_t stream)
+{
+    return lerp_entry("dpwa_lerp_f32_host", DPWA_F32, param, peer, n, nullptr, &factor, stream);
+}
+
+int dpwa_lerp_bf16_host(uint16_t *param, const uint16_t *peer, int64_t n, double factor, dpwa_stream_t stream)
+{
+    return lerp_entry("dpwa_lerp_bf16_host", DPWA_BF16, param, peer, n, nullptr, &factor, stream);
 }
 
 int dpwa_lerp_f16_host(uint16_t *param, const uint16_t *peer, int64_t n, double factor, dpwa_stream_t stream)
 {
-    if (n < 0 || (n > 0 && (!param || !peer))) return set_error(DPWA_ERR_ARG, "dpwa_lerp_f16_host: bad arguments");
-    HIP_TRY(launch_lerp(DPWA_F16, param, peer, n, nullptr, (float)factor, (float)(1.0 - factor), (hipStream_t)stream));
-    return DPWA_OK;
+    return lerp_entry("dpwa_lerp_f16_host", DPWA_F16, param, peer, n, nullptr, &factor, stream);
 }
 
 int dpwa_factor(const dpwa_interp *cfg, double *clock_dev, const dpwa_header *peer_header_dev, double loss,
                 const double *loss_dev, dpwa_coef *coef_dev, dpwa_stream_t stream)
 {
     if (!cfg || !clock_dev || !peer_header_dev || !coef_dev) return set_error(DPWA_ERR_ARG, "dpwa_factor: NULL argument");
-    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "dpwa_factor: unknown method %d", cfg->method);
-    FusedArgs fa{};
-    fa.cfg = *cfg;
-    fa.clock_in = clock_dev;
-    fa.clock_out = clock_dev;
-    fa.hdr = peer_header_dev;
-    fa.loss_h = loss;
+    if (int rc = check_method(cfg, "dpwa_factor")) return rc;
+    FusedArgs fa = stateless_args(cfg, clock_dev, peer_header_dev, loss, coef_dev);
+    fa.clock_out = clock_dev;   // the clock moves in place
     fa.loss_d = loss_dev;
-    fa.coef_out = coef_dev;
     HIP_TRY(launch_factor(fa, (hipStream_t)stream));
     return DPWA_OK;
 }
@@ -568,17 +652,10 @@ int dpwa_average(int32_t dtype, void *param, const void *peer_slot, int64_t n, c
         return set_error(DPWA_ERR_ARG, "dpwa_average: bad arguments");
     if (dtype == DPWA_MIXED)
         return set_error(DPWA_ERR_ARG, "dpwa_average: a DPWA_MIXED payload needs its layout (dpwa_average_mixed)");
-    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "dpwa_average: unknown method %d", cfg->method);
-    FusedArgs fa{};
-    fa.cfg = *cfg;
-    fa.clock_in = clock_dev;
-    fa.clock_out = clock_dev + 1;
-    fa.hdr = (const dpwa_header *)peer_slot;
-    fa.loss_h = loss;
-    fa.coef_out = coef_dev;
-    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
+    if (int rc = check_method(cfg, "dpwa_average")) return rc;
+    const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
     HIP_TRY(launch_average(dtype, param, (const char *)peer_slot + kPayloadOff, n, fa, snap_payload, (hipStream_t)stream,
-                           start_event ? &t : nullptr));
+                           CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -616,17 +693,10 @@ int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_
     if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: %s", why);
     if (((uintptr_t)param | (uintptr_t)peer_slot | (uintptr_t)snap_payload) & 15)
         return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: a segmented payload is 16-byte aligned");
-    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: unknown method %d", cfg->method);
-    FusedArgs fa{};
-    fa.cfg = *cfg;
-    fa.clock_in = clock_dev;
-    fa.clock_out = clock_dev + 1;
-    fa.hdr = (const dpwa_header *)peer_slot;
-    fa.loss_h = loss;
-    fa.coef_out = coef_dev;
-    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
+    if (int rc = check_method(cfg, "dpwa_average_mixed")) return rc;
+    const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
     HIP_TRY(launch_average_mixed(*layout, param, (const char *)peer_slot + kPayloadOff, fa, snap_payload,
-                                 (hipStream_t)stream, start_event ? &t : nullptr));
+                                 (hipStream_t)stream, CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -692,24 +762,16 @@ int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int6
                                        "(dpwa_measure_distance_mixed, then dpwa_average_mixed)");
     if (dtype != DPWA_F32 && dtype != DPWA_BF16 && dtype != DPWA_F16)
         return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: unknown dtype %d", dtype);
-    if (cfg->method < 0 || cfg->method > 2)
-        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: unknown method %d", cfg->method);
-    FusedArgs fa{};
-    fa.cfg = *cfg;
-    fa.clock_in = clock_dev;
-    fa.clock_out = clock_dev + 1;
-    fa.hdr = (const dpwa_header *)peer_slot;
-    fa.loss_h = loss;
-    fa.coef_out = coef_dev;
-    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
+    if (int rc = check_method(cfg, "dpwa_average_tracked")) return rc;
+    const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
+    const CallerTiming timing(start_event, stop_event);
     hipStream_t s = (hipStream_t)stream;
     const char *peer = (const char *)peer_slot + kPayloadOff;
     if ((((uintptr_t)param | (uintptr_t)peer | (uintptr_t)snap_payload) & 15) == 0) {
-        HIP_TRY(launch_average_tracked(dtype, param, peer, n, fa, snap_payload, false, (double *)workspace, s,
-                                       start_event ? &t : nullptr));
+        HIP_TRY(launch_average_tracked(dtype, param, peer, n, fa, snap_payload, false, (double *)workspace, s, timing));
     } else {   // the stand-alone pass, then dpwa_average's own (unaligned) kernel
         HIP_TRY(launch_distance(dtype, param, peer, n, (double *)workspace, s));
-        HIP_TRY(launch_average(dtype, param, peer, n, fa, snap_payload, s, start_event ? &t : nullptr));
+        HIP_TRY(launch_average(dtype, param, peer, n, fa, snap_payload, s, timing));
     }
     HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, s));
     return DPWA_OK;
@@ -720,9 +782,8 @@ int dpwa_distance_finish(void *workspace, dpwa_distance *out_dev, const dpwa_coe
 {
     if (n < 0 || (!start_event) != (!stop_event) || !distance_buffers_ok(workspace, out_dev))
         return set_error(DPWA_ERR_ARG, "dpwa_distance_finish: bad arguments (NULL or misaligned pointer, n < 0)");
-    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
     HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, (hipStream_t)stream,
-                                   start_event ? &t : nullptr));
+                                   CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -742,8 +803,7 @@ int dpwa_stream_mix(void *const *dst, int nw, const void *const *src, int nr, in
     a.nbytes = nbytes;
     a.nr = nr;
     a.nw = nw;
-    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
-    HIP_TRY(launch_stream_mix(a, (hipStream_t)stream, start_event ? &t : nullptr));
+    HIP_TRY(launch_stream_mix(a, (hipStream_t)stream, CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -763,34 +823,22 @@ int dpwa_learner_create(dpwa_learner **out, int device, int64_t n, int32_t dtype
     l->cfg = *cfg;
     l->payload_bytes = (size_t)n * dtype_size(dtype);
     l->slot_stride = kPayloadOff + round_up(l->payload_bytes, kPayloadOff);
+    // what a learner holds from its creation on (the rest is made at first use); the first failure ends it
     hipError_t e = hipSuccess;
-    do {
-        if ((e = devmem_alloc(l->slot_mem, 2 * l->slot_stride, device)) != hipSuccess) break;
-        l->slots = l->slot_mem.ptr;
-        if ((e = hipMalloc(&l->staging, l->slot_stride)) != hipSuccess) break;
-        if ((e = hipMalloc(&l->ctl, sizeof(Ctl))) != hipSuccess) break;
-        if ((e = hipMemset(l->slots, 0, kPayloadOff)) != hipSuccess) break;
-        if ((e = hipMemset(l->slots + l->slot_stride, 0, kPayloadOff)) != hipSuccess) break;
-        if ((e = hipMemset(l->staging, 0, kPayloadOff)) != hipSuccess) break;
-        if ((e = hipMemset(l->ctl, 0, sizeof(Ctl))) != hipSuccess) break;
-        if ((e = hipStreamCreateWithFlags(&l->side, hipStreamNonBlocking)) != hipSuccess) break;
-        for (auto &ev : l->ev_published)
-            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) break;
-        if (e != hipSuccess) break;
-        if ((e = hipEventCreate(&l->ev_issue)) != hipSuccess) break;     // timed: the fetch deadline
-        if ((e = hipEventCreateWithFlags(&l->ev_fetched, hipEventDisableTiming)) != hipSuccess) break;
-        if ((e = hipEventCreateWithFlags(&l->ev_consumed, hipEventDisableTiming)) != hipSuccess) break;
-        for (auto &ev : l->ev_stage_done)
-            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) break;
-        if (e != hipSuccess) break;
-        if ((e = hipEventCreateWithFlags(&l->ev_factor, hipEventDisableTiming)) != hipSuccess) break;
-        if ((e = hipEventCreateWithFlags(&l->ev_wt, hipEventDisableTiming)) != hipSuccess) break;
-        if ((e = hipHostMalloc((void **)&l->host_status, sizeof(int32_t), hipHostMallocMapped)) != hipSuccess) break;
-        *l->host_status = 0;
-        if ((e = hipHostGetDevicePointer((void **)&l->host_status_dev, l->host_status, 0)) != hipSuccess) break;
-        if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-    } while (0);
-    if (e != hipSuccess) {
+    auto ok = [&e](hipError_t r) { return (e = r) == hipSuccess; };
+    if (ok(devmem_alloc(l->slot_mem, 2 * l->slot_stride, device)) && ok(l->staging.alloc(l->slot_stride)) &&
+        ok(l->ctl_mem.alloc(sizeof(Ctl)))) {
+        l->ctl = (Ctl *)l->ctl_mem.ptr();
+        if (ok(hipMemset(l->slot_mem.ptr, 0, kPayloadOff)) && ok(hipMemset(l->slot_mem.ptr + l->slot_stride, 0, kPayloadOff)) &&
+            ok(hipMemset(l->staging.ptr(), 0, kPayloadOff)) && ok(hipMemset(l->ctl, 0, sizeof(Ctl))) &&
+            ok(l->side.create()) && ok(l->published[0].init()) && ok(l->published[1].init()) &&
+            ok(l->ev_issue.init(hipEventDefault)) &&   // timed: the fetch deadline
+            ok(l->fetched.init()) && ok(l->consumed.init()) && ok(l->stage_done[0].init()) &&
+            ok(l->stage_done[1].init()) && ok(l->factor_done.init()) && ok(l->written_through.init()) &&
+            ok(l->status.alloc()))
+            ok(hipDeviceSynchronize());
+    }
+    if (e != hipSuccess) {   // the owners give back whatever was made
         int rc = set_error(DPWA_ERR_HIP, "dpwa_learner_create: %s (slot %zu bytes)", hipGetErrorString(e), l->slot_stride);
         dpwa_learner_destroy(l);
         return rc;
@@ -817,43 +865,8 @@ int dpwa_learner_destroy(dpwa_learner *l)
     DeviceGuard dg(l->device);
     (void)hipDeviceSynchronize();
     for (auto &kv : l->peers) close_endpoint(kv.second);
-    if (l->side) (void)hipStreamDestroy(l->side);
-    for (auto ev : l->ev_published)
-        if (ev) (void)hipEventDestroy(ev);
-    if (l->ev_issue) (void)hipEventDestroy(l->ev_issue);
-    if (l->ev_probe) (void)hipEventDestroy(l->ev_probe);
-    if (l->probe_stream) (void)hipStreamDestroy(l->probe_stream);
-    if (l->ev_fetched) (void)hipEventDestroy(l->ev_fetched);
-    if (l->ev_consumed) (void)hipEventDestroy(l->ev_consumed);
-    for (auto ev : l->ev_stage_done)
-        if (ev) (void)hipEventDestroy(ev);
-    if (l->staging_alt) (void)hipFree(l->staging_alt);
-    for (auto &r : l->rescue) destroy_lane(r);
-    if (l->ev_factor) (void)hipEventDestroy(l->ev_factor);
-    if (l->ev_wt) (void)hipEventDestroy(l->ev_wt);
-    if (l->ev_read) (void)hipEventDestroy(l->ev_read);
-    if (l->ev_relay) (void)hipEventDestroy(l->ev_relay);
-    if (l->ev_window) (void)hipEventDestroy(l->ev_window);
-    if (l->window_sample) (void)hipFree(l->window_sample);
-    if (l->window_host) (void)hipHostFree(l->window_host);
-    for (auto &t : l->timing) {
-        (void)hipEventDestroy(t.start);
-        (void)hipEventDestroy(t.stop);
-    }
-    for (auto &t : l->fetch_timing) {
-        (void)hipEventDestroy(t.start);
-        (void)hipEventDestroy(t.stop);
-    }
     for (char *p : l->relay_opened) (void)hipIpcCloseMemHandle(p);
-    for (auto &m : l->relay_imported) devmem_free(m);
-    devmem_free(l->relay_mem);
-    if (l->read_stream) (void)hipStreamDestroy(l->read_stream);
-    if (l->host_status) (void)hipHostFree(l->host_status);
-    if (l->dist_mem) (void)hipFree(l->dist_mem);
-    devmem_free(l->slot_mem);
-    if (l->staging) (void)hipFree(l->staging);
-    if (l->ctl) (void)hipFree(l->ctl);
-    delete l;
+    delete l;   // every member frees what it owns, on l's device (dg)
     return DPWA_OK;
 }
 
@@ -867,10 +880,9 @@ static int wait_slot_readers(dpwa_learner *l, int k, hipStream_t s)
             return set_error(DPWA_ERR_STATE,
                              "a peer still has an unconsumed fetch of the snapshot slot about to be rewritten "
                              "(publish at most once per round)");
-        if (r->consumed_once && r->consume_stream != s) {
+        if (r->consumed.crosses(s)) {
             DeviceGuard rg(r->device);
-            HIP_TRY(hipEventRecord(r->ev_consumed, r->consume_stream));
-            HIP_TRY(hipStreamWaitEvent(s, r->ev_consumed, 0));
+            HIP_TRY(r->consumed.order(s));
         }
     }
     l->readers[k].clear();
@@ -878,6 +890,14 @@ static int wait_slot_readers(dpwa_learner *l, int k, hipStream_t s)
 }
 
 static int relocate_impl(dpwa_learner *l, hipStream_t s);
+
+// `flat` is in the next publish's slot, written there on `s` (`header`: with its header and clock)
+static void set_written_through(dpwa_learner *l, const void *flat, bool header, hipStream_t s)
+{
+    l->written_through.note(s);
+    l->wt_flat = flat;
+    l->wt_header = header;
+}
 
 // ---------------------------------------------------------------- window guard (resident)
 // Between update_send and update_wait resident parameters ARE the snapshot peers read (the
@@ -893,28 +913,13 @@ static int relocate_impl(dpwa_learner *l, hipStream_t s);
 // change none of the sampled words are not seen.
 static int window_alloc(dpwa_learner *l)
 {
-    if (l->window_sample) return DPWA_OK;
-    char *sample = nullptr;
-    uint32_t *host = nullptr, *host_dev = nullptr;
-    hipEvent_t ev = nullptr;
-    hipError_t e = hipMalloc(&sample, kWindowSampleBytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&host, sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        *host = 0;
-        e = hipHostGetDevicePointer((void **)&host_dev, host, 0);
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        if (sample) (void)hipFree(sample);
-        if (host) (void)hipHostFree(host);
-        if (ev) (void)hipEventDestroy(ev);
-        return set_error(DPWA_ERR_HIP, "window guard: %s", hipGetErrorString(e));
-    }
-    l->window_sample = sample;
-    l->window_host = host;
-    l->window_host_dev = host_dev;
-    l->ev_window = ev;
-    l->window_reported = 0;
+    if (l->window.sample.ptr()) return DPWA_OK;
+    WindowGuard w;   // built aside: a failure leaves the learner without one, and nothing to free
+    hipError_t e = w.sample.alloc(kWindowSampleBytes);
+    if (e == hipSuccess) e = w.hits.alloc();
+    if (e == hipSuccess) e = w.rolled.init();
+    if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "window guard: %s", hipGetErrorString(e));
+    l->window = std::move(w);
     return DPWA_OK;
 }
 
@@ -923,27 +928,23 @@ static int window_alloc(dpwa_learner *l)
 // runs after that roll when the roll went to another stream.
 static int wait_window_roll(dpwa_learner *l, hipStream_t s)
 {
-    if (!l->resident || !l->window_stream || l->window_stream == s) return DPWA_OK;
-    HIP_TRY(hipEventRecord(l->ev_window, l->window_stream));
-    HIP_TRY(hipStreamWaitEvent(s, l->ev_window, 0));
+    // a null handle counts as "no roll yet": the default stream is indistinguishable from "never"
+    if (l->resident && l->window.rolled.stream()) HIP_TRY(l->window.rolled.order(s));
     return DPWA_OK;
 }
 
 // One roll on `s`: check the last window (if any), then sample `cur` (if not NULL).
 static int window_roll(dpwa_learner *l, const char *cur, hipStream_t s)
 {
-    int rc = window_alloc(l);
-    if (rc) return rc;
-    if (l->window_stream && l->window_stream != s) {
-        HIP_TRY(hipEventRecord(l->ev_window, l->window_stream));
-        HIP_TRY(hipStreamWaitEvent(s, l->ev_window, 0));
-    }
-    HIP_TRY(launch_window_roll(l->window_src, cur, (int64_t)l->payload_bytes, l->window_sample, &l->ctl->window_dirty,
-                               &l->ctl->window_hits, l->window_host_dev, l->window_gen, (int32_t)(l->version + 1), s));
-    l->window_stream = s;
+    if (int rc = window_alloc(l)) return rc;
+    if (int rc = wait_window_roll(l, s)) return rc;   // (only a resident learner rolls)
+    WindowGuard &w = l->window;
+    HIP_TRY(launch_window_roll(w.src, cur, (int64_t)l->payload_bytes, w.sample.ptr(), &l->ctl->window_dirty,
+                               &l->ctl->window_hits, w.hits.dev, w.gen, (int32_t)(l->version + 1), s));
+    w.rolled.note(s);
     if (cur) {
-        l->window_src = cur;
-        l->window_gen = (int32_t)(l->version + 1);
+        w.src = cur;
+        w.gen = (int32_t)(l->version + 1);
     }
     return DPWA_OK;
 }
@@ -951,11 +952,12 @@ static int window_roll(dpwa_learner *l, const char *cur, hipStream_t s)
 // Reports written windows counted since the last report; never waits for a check.
 static int window_report(dpwa_learner *l)
 {
-    if (!l->window_host) return DPWA_OK;
-    const uint32_t seen = __atomic_load_n(l->window_host, __ATOMIC_ACQUIRE);
-    if (seen == l->window_reported) return DPWA_OK;
-    const uint32_t newly = seen - l->window_reported;
-    l->window_reported = seen;
+    WindowGuard &w = l->window;
+    if (!w.hits.host()) return DPWA_OK;
+    const uint32_t seen = __atomic_load_n(w.hits.host(), __ATOMIC_ACQUIRE);
+    if (seen == w.reported) return DPWA_OK;
+    const uint32_t newly = seen - w.reported;
+    w.reported = seen;
     return set_error(DPWA_ERR_STATE,
                      "resident parameters were written between update_send and update_wait (%u more window(s); "
                      "through param.data, which moves no version counter): peers may have averaged with a partly "
@@ -969,66 +971,52 @@ static int publish_impl(dpwa_learner *l, const void *flat, double loss, const do
     TraceRange tr(reuse ? "dpwa.learner_publish.reuse" : "dpwa.learner_publish");
     l->timing_armed = false;   // armed for the last round's average, which did not happen
     if (l->resident && l->reuse_guard) {   // the window guard's buffers, before anything is queued
-        int rc = window_alloc(l);
-        if (rc) return rc;
+        if (int rc = window_alloc(l)) return rc;
     }
     const int k = (int)(l->version % 2);   // slot of publish number version+1
-    char *slot = l->slots + (size_t)k * l->slot_stride;
+    char *slot = l->slot_mem.ptr + (size_t)k * l->slot_stride;
     if (l->resident) {
-        int rc = window_report(l);
-        if (rc) return rc;
+        if (int rc = window_report(l)) return rc;
         // the parameters are the payload already: publish the header of the slot they are in
         // (after a publish with no average since, they first move on by one copy)
         if (flat != slot_payload(l, l->res_slot))
             return set_error(DPWA_ERR_ARG, "resident learner: publish the parameters where they are "
                                            "(dpwa_learner_resident_params)");
-        rc = relocate_impl(l, s);
-        if (rc) return rc;
+        if (int rc = relocate_impl(l, s)) return rc;
         flat = slot_payload(l, l->res_slot);
         reuse = true;
     }
-    const bool header_only = reuse && l->wt_valid && l->wt_flat == flat;
-    if (header_only && l->wt_header) {
-        // payload, header and clock of this publish were written by the last average: nothing
-        // moves (IPC-exported slots still get their system-scope write-back).  Work on `s`
-        // after this publish (the next factor reads the clock the average wrote) is ordered
-        // after the average.
-        if (l->wt_stream != s) {
-            HIP_TRY(hipEventRecord(l->ev_wt, l->wt_stream));
-            HIP_TRY(hipStreamWaitEvent(s, l->ev_wt, 0));
-        }
+    const bool header_only = reuse && l->written_through.noted() && l->wt_flat == flat;
+    if (header_only) {
+        // the payload was written by the last average (readers of slot k were waited for then);
+        // work on `s` after this publish (the next factor reads the clock the average wrote) is
+        // ordered after the average
+        HIP_TRY(l->written_through.order(s));
         if (l->reuse_guard && !l->resident)
             HIP_TRY(launch_guard_payload(slot + kPayloadOff, flat, (int64_t)l->payload_bytes, &l->ctl->guard_dirty,
                                          &l->ctl->guard_hits, (int32_t)(l->version + 1), s));
-        if (l->exported) HIP_TRY(launch_release_system(s));
-        l->cur = (l->cur + 1) & 3;
-    } else if (header_only) {
-        // the payload was written by the last average (readers of slot k were waited for then)
-        if (l->wt_stream != s) {
-            HIP_TRY(hipEventRecord(l->ev_wt, l->wt_stream));
-            HIP_TRY(hipStreamWaitEvent(s, l->ev_wt, 0));
+        if (l->wt_header) {
+            // header and clock of this publish were written by the last average too: nothing
+            // moves (IPC-exported slots still get their system-scope write-back)
+            if (l->exported) HIP_TRY(launch_release_system(s));
+            l->cur = (l->cur + 1) & 3;
+        } else {
+            HIP_TRY(launch_publish_header(slot, l->n, l->dtype, &l->ctl->clock[l->cur], loss, loss_dev, l->loss_f32,
+                                          l->version + 1, l->exported, s));
         }
-        if (l->reuse_guard && !l->resident)
-            HIP_TRY(launch_guard_payload(slot + kPayloadOff, flat, (int64_t)l->payload_bytes, &l->ctl->guard_dirty,
-                                         &l->ctl->guard_hits, (int32_t)(l->version + 1), s));
-        HIP_TRY(launch_publish_header(slot, l->n, l->dtype, &l->ctl->clock[l->cur], loss, loss_dev, l->loss_f32,
-                                      l->version + 1, l->exported, s));
     } else {
         if (l->resident) return set_error(DPWA_ERR_STATE, "resident learner: parameters not in the next slot");
-        int rc = wait_slot_readers(l, k, s);
-        if (rc) return rc;
+        if (int rc = wait_slot_readers(l, k, s)) return rc;
         HIP_TRY(launch_publish(slot, flat, (int64_t)l->payload_bytes, l->n, l->dtype, &l->ctl->clock[l->cur], loss,
                                loss_dev, l->loss_f32, l->version + 1, l->exported, s));
     }
-    l->wt_valid = false;
+    l->written_through.clear();
     l->wt_header = false;
     if (l->resident && l->reuse_guard) {   // the last window's check; this window's samples
-        int rc = window_roll(l, (const char *)flat, s);
-        if (rc) return rc;
+        if (int rc = window_roll(l, (const char *)flat, s)) return rc;
     }
     std::lock_guard<std::mutex> g(l->pub_mu);
-    l->publish_stream[k] = s;
-    l->published[k] = true;
+    l->published[k].note(s);
     l->version++;
     return DPWA_OK;
 }
@@ -1113,12 +1101,12 @@ int dpwa_learner_attach_local(dpwa_learner *l, int peer_id, dpwa_learner *peer)
     Endpoint ep;
     ep.kind = 1;
     ep.local = peer;
-    ep.base = peer->slots;
+    ep.base = peer->slot_mem.ptr;
     ep.device = peer->device;
     ep.slot_stride = (int64_t)peer->slot_stride;
     ep.n = peer->n;
     ep.dtype = peer->dtype;
-    l->peers[peer_id] = ep;
+    l->peers[peer_id] = std::move(ep);
     return DPWA_OK;
 }
 
@@ -1143,7 +1131,7 @@ int dpwa_learner_ipc_handle(dpwa_learner *l, void *handle_out, int64_t handle_le
         return set_error(DPWA_ERR_ARG, "dpwa_learner_ipc_handle: need %zu bytes", sizeof(IpcBlob));
     DeviceGuard dg(l->device);
     IpcBlob b = make_blob(l, l->slot_mem, (int64_t)l->slot_stride);
-    if (!b.vmm) HIP_TRY(hipIpcGetMemHandle(&b.handle, l->slots));   // else: fds, dpwa_learner_export_fds
+    if (!b.vmm) HIP_TRY(hipIpcGetMemHandle(&b.handle, l->slot_mem.ptr));   // else: fds, dpwa_learner_export_fds
     memset(handle_out, 0, (size_t)handle_len);
     memcpy(handle_out, &b, sizeof(b));
     l->exported = true;   // from now on publishes release at system scope
@@ -1225,8 +1213,7 @@ static int free_lane(dpwa_learner *l, int *lane)
 {
     *lane = -1;
     for (int j = 0; j < l->rescue_lanes; ++j) {
-        RescueLane &r = l->rescue[j];
-        const hipError_t e = r.used ? hipEventQuery(r.ev_landed) : hipSuccess;
+        const hipError_t e = l->rescue[j].landed.query();
         if (e == hipSuccess) {
             *lane = j;
             return DPWA_OK;
@@ -1253,21 +1240,17 @@ static int rescue_lane(dpwa_learner *l, int *lane)
     }
     RescueLane r;
     int least = 0, greatest = 0;
-    hipError_t e;
-    do {
-        if ((e = hipMalloc(&r.buf, l->slot_stride)) != hipSuccess) break;
-        if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) break;
-        if ((e = hipStreamCreateWithPriority(&r.stream, hipStreamNonBlocking, greatest)) != hipSuccess) break;
-        if ((e = hipEventCreateWithFlags(&r.ev_landed, hipEventDisableTiming)) != hipSuccess) break;
-        e = hipEventCreateWithFlags(&r.ev_done, hipEventDisableTiming);
-    } while (0);
-    if (e != hipSuccess) {
-        destroy_lane(r);
+    hipError_t e = r.buf.alloc(l->slot_stride);
+    if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (e == hipSuccess) e = r.stream.create(greatest);
+    if (e == hipSuccess) e = r.landed.init();
+    if (e == hipSuccess) e = r.done.init();
+    if (e != hipSuccess) {                // `r` gives back what it made
         (void)hipGetLastError();          // clear the sticky error: the round goes on without a new lane
         l->rescue_cap = l->rescue_lanes;
         return DPWA_OK;
     }
-    l->rescue[l->rescue_lanes] = r;
+    l->rescue[l->rescue_lanes] = std::move(r);
     *lane = l->rescue_lanes++;
     return DPWA_OK;
 }
@@ -1281,12 +1264,46 @@ static void trim_lanes(dpwa_learner *l)
         const int j = l->rescue_lanes - 1;
         RescueLane &r = l->rescue[j];
         if (l->fetch_rounds - r.last_round < kLaneIdleRounds || l->src_stage == 2 + j) return;
-        if (r.used && hipEventQuery(r.ev_landed) != hipSuccess) break;
-        if (r.read && hipEventQuery(r.ev_done) != hipSuccess) break;
-        destroy_lane(r);
+        if (r.landed.query() != hipSuccess || r.done.query() != hipSuccess) break;
+        r = RescueLane();
         l->rescue_lanes--;
     }
     (void)hipGetLastError();   // a not-ready query leaves no error behind
+}
+
+// `to` runs on from the point `s` has reached; fetch_state reads ev_issue's time of reaching it
+static hipError_t issue_after(dpwa_learner *l, hipStream_t s, hipStream_t to)
+{
+    const hipError_t e = hipEventRecord(l->ev_issue.h, s);
+    return e == hipSuccess ? hipStreamWaitEvent(to, l->ev_issue.h, 0) : e;
+}
+
+// One snapshot from `peer_slot` into the slot-sized `dst` on `stream`, by the copy engine or the
+// pull kernel (dpwa_learner_set_pull); `timed` takes the next fetch-timing pair, if one is left.
+static int pull_into(dpwa_learner *l, char *dst, const char *peer_slot, bool cross_device, hipStream_t stream,
+                     bool timed)
+{
+    const size_t nbytes = kPayloadOff + round_up(l->payload_bytes, 16);
+    const LaunchTiming *ft = timed ? l->fetch_times.take() : nullptr;
+    if (ft) HIP_TRY(hipEventRecord(ft->start, stream));
+    if (l->pull_mode == DPWA_PULL_KERNEL)
+        HIP_TRY(launch_pull(dst, peer_slot, (int64_t)nbytes, l->pull_blocks, cross_device, stream));
+    else
+        HIP_TRY(hipMemcpyAsync(dst, peer_slot, nbytes, hipMemcpyDefault, stream));
+    if (ft) HIP_TRY(hipEventRecord(ft->stop, stream));
+    return DPWA_OK;
+}
+
+// The fetch in flight reads the snapshot at `src`: in buffer `stage` (src_stage), a copy that
+// `fetched` covers or not, of local peer `owner`'s slot `slot` (NULL, -1: not a local peer's).
+static void set_source(dpwa_learner *l, const char *src, int stage, bool copied, dpwa_learner *owner, int slot)
+{
+    l->src = src;
+    l->src_copied = copied;
+    l->src_stage = stage;
+    l->src_owner = owner;
+    l->src_slot = slot;
+    l->have_fetch = true;
 }
 
 int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int flags, dpwa_stream_t stream)
@@ -1305,18 +1322,20 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
     if (ep.kind == 1) {
         // RAW: the peer's publish of that slot must be complete before anyone reads it.
         dpwa_learner *pl = ep.local;
-        if (!pl->published[k]) return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: peer %d slot %d never published", peer_id, k);
-        if (pl->publish_stream[k] != s) {
+        if (!pl->published[k].noted()) return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: peer %d slot %d never published", peer_id, k);
+        if (pl->published[k].crosses(s)) {
             DeviceGuard pg(pl->device);
-            HIP_TRY(hipEventRecord(pl->ev_published[k], pl->publish_stream[k]));
-            HIP_TRY(hipStreamWaitEvent(s, pl->ev_published[k], 0));
+            HIP_TRY(pl->published[k].order(s));
         }
         std::lock_guard<std::mutex> g(ep.local->readers_mu);
         auto &rv = ep.local->readers[k];
         if (std::find(rv.begin(), rv.end(), l) == rv.end()) rv.push_back(l);
     }
+    dpwa_learner *const owner = ep.kind == 1 ? ep.local : nullptr;
+    const bool cross_device = ep.kind == 2 || ep.device != l->device;
+    hipStream_t side = l->side.h;
     l->fetch_issue_ns = now_ns();
-    l->fetch_stream = l->side;
+    l->fetch_stream = side;
     l->issue_evented = false;
     if (!(flags & DPWA_FETCH_RESCUE)) {
         l->fetch_rounds++;
@@ -1327,92 +1346,52 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
         // after the publish of the snapshot (above, local peers) and after the last reader of the
         // lane's buffer
         int j = -1;
-        const int rc = rescue_lane(l, &j);
-        if (rc) return rc;
+        if (int rc = rescue_lane(l, &j)) return rc;
         if (j < 0)
             return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: all %d rescue lanes are still pulling",
                              l->rescue_lanes);
         RescueLane &r = l->rescue[j];
         if (!(flags & DPWA_FETCH_PUBLISHED)) {
-            HIP_TRY(hipEventRecord(l->ev_issue, s));
-            HIP_TRY(hipStreamWaitEvent(r.stream, l->ev_issue, 0));
+            HIP_TRY(issue_after(l, s, r.stream.h));
             l->issue_evented = true;
         }
-        if (r.read) HIP_TRY(hipStreamWaitEvent(r.stream, r.ev_done, 0));
-        const size_t nbytes = kPayloadOff + round_up(l->payload_bytes, 16);
-        if (l->pull_mode == DPWA_PULL_KERNEL)
-            HIP_TRY(launch_pull(r.buf, peer_slot, (int64_t)nbytes, l->pull_blocks,
-                                ep.kind == 2 || ep.device != l->device, r.stream));
-        else
-            HIP_TRY(hipMemcpyAsync(r.buf, peer_slot, nbytes, hipMemcpyDefault, r.stream));
-        HIP_TRY(hipEventRecord(r.ev_landed, r.stream));
-        HIP_TRY(hipEventRecord(l->ev_fetched, r.stream));
-        r.used = true;
+        HIP_TRY(r.done.wait(r.stream.h));
+        if (int rc = pull_into(l, r.buf.ptr(), peer_slot, cross_device, r.stream.h, false)) return rc;
+        HIP_TRY(r.landed.record(r.stream.h));
+        HIP_TRY(l->fetched.record(r.stream.h));
         r.last_round = l->fetch_rounds;
-        l->fetch_stream = r.stream;
-        l->src = r.buf;
-        l->src_copied = true;
-        l->src_stage = 2 + j;
+        l->fetch_stream = r.stream.h;
+        set_source(l, r.buf.ptr(), 2 + j, true, owner, k);
     } else if (zero_copy && ep.kind == 1 && ep.device == l->device) {
-        l->src = peer_slot;             // read in place; stream order covers the rest
-        l->src_copied = false;
-        l->src_stage = -1;
+        set_source(l, peer_slot, -1, false, owner, k);   // read in place; stream order covers the rest
     } else if ((flags & DPWA_FETCH_PUBLISHED) && ep.kind == 2) {
-        if (!l->staging_alt) {
-            HIP_TRY(hipMalloc(&l->staging_alt, l->slot_stride));
-            HIP_TRY(hipMemsetAsync(l->staging_alt, 0, kPayloadOff, l->side));
+        if (!l->staging_alt.ptr()) {
+            HIP_TRY(l->staging_alt.alloc(l->slot_stride));
+            HIP_TRY(hipMemsetAsync(l->staging_alt.ptr(), 0, kPayloadOff, side));
         }
         const int b = l->stage_next;
         l->stage_next ^= 1;
-        char *dst = b == 0 ? l->staging : l->staging_alt;
+        char *dst = b == 0 ? l->staging.ptr() : l->staging_alt.ptr();
         // WAR: the average that last read this buffer; nothing else on the caller's stream
-        if (l->stage_read[b]) HIP_TRY(hipStreamWaitEvent(l->side, l->ev_stage_done[b], 0));
-        const size_t nbytes = kPayloadOff + round_up(l->payload_bytes, 16);
-        const LaunchTiming *ft = l->fetch_timing_used < (int)l->fetch_timing.size()
-                                     ? &l->fetch_timing[l->fetch_timing_used++] : nullptr;
-        if (ft) HIP_TRY(hipEventRecord(ft->start, l->side));
-        if (l->pull_mode == DPWA_PULL_KERNEL)
-            HIP_TRY(launch_pull(dst, peer_slot, (int64_t)nbytes, l->pull_blocks, true, l->side));
-        else
-            HIP_TRY(hipMemcpyAsync(dst, peer_slot, nbytes, hipMemcpyDefault, l->side));
-        if (ft) HIP_TRY(hipEventRecord(ft->stop, l->side));
-        HIP_TRY(hipEventRecord(l->ev_fetched, l->side));
-        l->src = dst;
-        l->src_copied = true;
-        l->src_stage = b;
+        HIP_TRY(l->stage_done[b].wait(side));
+        if (int rc = pull_into(l, dst, peer_slot, true, side, true)) return rc;
+        HIP_TRY(l->fetched.record(side));
+        set_source(l, dst, b, true, owner, k);
     } else {
-        if (l->stage_read[0]) HIP_TRY(hipStreamWaitEvent(l->side, l->ev_stage_done[0], 0));
-        HIP_TRY(hipEventRecord(l->ev_issue, s));
-        HIP_TRY(hipStreamWaitEvent(l->side, l->ev_issue, 0));
+        HIP_TRY(l->stage_done[0].wait(side));
+        HIP_TRY(issue_after(l, s, side));
         l->issue_evented = true;
-        // WAR on our own staging buffer: the previous average must have consumed it.
-        if (l->consumed_once && l->consume_stream != s) {
-            HIP_TRY(hipEventRecord(l->ev_consumed, l->consume_stream));
-            HIP_TRY(hipStreamWaitEvent(l->side, l->ev_consumed, 0));
-        }
-        const size_t nbytes = kPayloadOff + round_up(l->payload_bytes, 16);
-        const LaunchTiming *ft = l->fetch_timing_used < (int)l->fetch_timing.size()
-                                     ? &l->fetch_timing[l->fetch_timing_used++] : nullptr;
-        if (ft) HIP_TRY(hipEventRecord(ft->start, l->side));
-        if (l->pull_mode == DPWA_PULL_KERNEL)
-            HIP_TRY(launch_pull(l->staging, peer_slot, (int64_t)nbytes, l->pull_blocks,
-                                ep.kind == 2 || ep.device != l->device, l->side));
-        else
-            HIP_TRY(hipMemcpyAsync(l->staging, peer_slot, nbytes, hipMemcpyDefault, l->side));
-        if (ft) HIP_TRY(hipEventRecord(ft->stop, l->side));
-        HIP_TRY(hipEventRecord(l->ev_fetched, l->side));
-        l->src = l->staging;
-        l->src_copied = true;
-        l->src_stage = 0;
+        // WAR on our own staging buffer: the previous average must have consumed it (the side
+        // stream waits, and now follows `s`, which covers a consumption on itself)
+        HIP_TRY(l->consumed.order(side, s));
+        if (int rc = pull_into(l, l->staging.ptr(), peer_slot, cross_device, side, true)) return rc;
+        HIP_TRY(l->fetched.record(side));
+        set_source(l, l->staging.ptr(), 0, true, owner, k);
     }
-    l->src_owner = ep.kind == 1 ? ep.local : nullptr;
-    l->src_slot = k;
-    l->have_fetch = true;
     return DPWA_OK;
 }
 
 static int relay_materialize(dpwa_learner *l);
-static hipError_t staging_read(dpwa_learner *l, hipStream_t s);
 static int distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s);
 static int distance_after(dpwa_learner *l, hipStream_t s);
 
@@ -1427,8 +1406,19 @@ static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev
     fa.loss_d = loss_dev;
     fa.loss_f32 = l->loss_f32 ? 1 : 0;
     fa.coef_out = &l->ctl->coef;
-    fa.status_mirror = l->host_status_dev;
+    fa.status_mirror = l->status.dev;
     return fa;
+}
+
+// Everything enqueued on `s` so far has read the fetch source: a staging buffer or lane may be
+// refilled once `s` gets here (recorded now: refills run elsewhere); so may the source itself.
+static hipError_t note_consumed(dpwa_learner *l, hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+    if (l->src_stage >= 0 && l->src_copied)
+        e = l->src_stage >= 2 ? l->rescue[l->src_stage - 2].done.record(s) : l->stage_done[l->src_stage].record(s);
+    if (e == hipSuccess) l->consumed.note(s);
+    return e;
 }
 
 int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dpwa_stream_t stream)
@@ -1439,30 +1429,14 @@ int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dp
     if (int rc = need_layout(l, "dpwa_learner_factor")) return rc;
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    int rc = relay_materialize(l);
-    if (rc) return rc;
-    if (l->src_copied) HIP_TRY(hipStreamWaitEvent(s, l->ev_fetched, 0));   // TxThread.fetch_wait
+    if (int rc = relay_materialize(l)) return rc;
+    if (l->src_copied) HIP_TRY(l->fetched.wait(s));   // TxThread.fetch_wait
     HIP_TRY(launch_factor(fused_args(l, loss, loss_dev), s));
-    HIP_TRY(hipEventRecord(l->ev_factor, s));
-    HIP_TRY(staging_read(l, s));   // a later pull into this staging buffer waits for the header read
-    l->consume_stream = s;   // the header has been read on s
-    l->consumed_once = true;
+    HIP_TRY(l->factor_done.record(s));
+    HIP_TRY(note_consumed(l, s));   // the header has been read on s: a later pull into this buffer waits for it
     l->cur = (l->cur + 1) & 3;
     l->have_factor = true;
     return DPWA_OK;
-}
-
-// The fetched snapshot in staging buffer src_stage has been read by everything enqueued on s.
-static hipError_t staging_read(dpwa_learner *l, hipStream_t s)
-{
-    if (l->src_stage < 0 || !l->src_copied) return hipSuccess;
-    if (l->src_stage >= 2) {
-        RescueLane &r = l->rescue[l->src_stage - 2];
-        r.read = true;
-        return hipEventRecord(r.ev_done, s);
-    }
-    l->stage_read[l->src_stage] = true;
-    return hipEventRecord(l->ev_stage_done[l->src_stage], s);
 }
 
 static void finish_fetch(dpwa_learner *l)
@@ -1491,10 +1465,8 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     }
     if (l->track)
         if (int rc = distance_after(l, s)) return rc;
-    HIP_TRY(staging_read(l, s));
-    l->wt_valid = false;
-    l->consume_stream = s;
-    l->consumed_once = true;
+    HIP_TRY(note_consumed(l, s));
+    l->written_through.clear();
     finish_fetch(l);
     return DPWA_OK;
 }
@@ -1535,9 +1507,8 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
     p.fa = fused_args(l, loss, loss_dev);
     if (write_through) {
         const int k = (int)(l->version % 2);   // slot of the next publish
-        int rc = wait_slot_readers(l, k, s);
-        if (rc) return rc;
-        if ((rc = wait_window_roll(l, s))) return rc;
+        if (int rc = wait_slot_readers(l, k, s)) return rc;
+        if (int rc = wait_window_roll(l, s)) return rc;
         p.snap = slot_payload(l, k);
         p.snap_slot = k;
         if (l->cfg.method != DPWA_INTERP_LOSS && !l->header_on_publish) {   // peers never read this header's loss
@@ -1552,12 +1523,11 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
         // the relay's phase 2 fused into the average: stripes read where phase 1 left them
         const RelayArgs &a = l->relay_saved;
         p.fa.hdr = (const dpwa_header *)(a.slots[l->relay_saved_pick] + a.slot_off);
-        HIP_TRY(hipStreamWaitEvent(s, l->ev_fetched, 0));
+        HIP_TRY(l->fetched.wait(s));
         p.relay = true;
     } else {
-        int rc = relay_materialize(l);
-        if (rc) return rc;
-        if (l->src_copied) HIP_TRY(hipStreamWaitEvent(s, l->ev_fetched, 0));   // TxThread.fetch_wait
+        if (int rc = relay_materialize(l)) return rc;
+        if (l->src_copied) HIP_TRY(l->fetched.wait(s));   // TxThread.fetch_wait
         p.peer = l->src + kPayloadOff;
     }
     return DPWA_OK;
@@ -1565,31 +1535,23 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
 
 static const LaunchTiming *take_timing(dpwa_learner *l)
 {
-    if (l->timing_armed && l->timing_used < (int)l->timing.size()) return &l->timing[l->timing_used++];
-    return nullptr;
+    return l->timing_armed ? l->avg_times.take() : nullptr;
 }
 
 static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
     if (p.relay) {
-        HIP_TRY(hipEventRecord(l->ev_relay, s));   // the next round's barrier waits for these reads
-        l->relay_pending = true;
+        HIP_TRY(l->relay_done.record(s));   // the next round's barrier waits for these reads
         l->relay_deferred = false;
+        l->consumed.note(s);   // the stripes were read where phase 1 left them: no staging buffer
     } else {
-        HIP_TRY(staging_read(l, s));
+        HIP_TRY(note_consumed(l, s));
     }
     l->timing_armed = false;
-    l->consume_stream = s;
-    l->consumed_once = true;
     l->cur = (l->cur + 1) & 3;
-    l->wt_valid = p.write_through;
-    l->wt_header = p.fa.next_header != nullptr;
-    l->wt_flat = p.flat;
-    l->wt_stream = s;
-    if (p.oop) {   // the parameters moved into the next publish's slot
-        l->res_slot = p.snap_slot;
-        l->wt_flat = p.snap;
-    }
+    if (p.oop) l->res_slot = p.snap_slot;   // the parameters moved into the next publish's slot
+    set_written_through(l, p.oop ? p.snap : p.flat, p.fa.next_header != nullptr, s);
+    if (!p.write_through) l->written_through.clear();
     finish_fetch(l);
     return DPWA_OK;
 }
@@ -1644,9 +1606,8 @@ static int average_impl(dpwa_learner *l, void *flat, double loss, const double *
 {
     TraceRange tr("dpwa.average");
     AvgPlan p;
-    int rc = average_prepare(l, flat, loss, loss_dev, s, write_through, p);
-    if (rc) return rc;
-    if ((rc = average_launch(l, p, s))) return rc;
+    if (int rc = average_prepare(l, flat, loss, loss_dev, s, write_through, p)) return rc;
+    if (int rc = average_launch(l, p, s)) return rc;
     return average_commit(l, p, s);
 }
 
@@ -1766,7 +1727,7 @@ static int average_many_impl(const char *fn, int32_t dtype, const dpwa_average_d
     if (count < 1 || count > kMaxAvgBatch || !descs || !cfg || dtype_size(dtype) == 0 || (!start_event) != (!stop_event))
         return set_error(DPWA_ERR_ARG, "%s: bad arguments (1..%d descriptors)", fn, kMaxAvgBatch);
     if (dtype == DPWA_MIXED) return set_error(DPWA_ERR_ARG, "%s: segmented (DPWA_MIXED) payloads are not batched", fn);
-    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "%s: unknown method %d", fn, cfg->method);
+    if (int rc = check_method(cfg, fn)) return rc;
     AvgBatch b{};
     bool dual = oop;   // an empty entry may pass no buffers at all
     for (int i = 0; i < count; ++i) dual = dual || descs[i].snap_payload != nullptr;
@@ -1781,21 +1742,15 @@ static int average_many_impl(const char *fn, int32_t dtype, const dpwa_average_d
         e.peer = (const char *)d.peer_slot + kPayloadOff;
         e.snap = d.snap_payload;
         e.n = d.n;
-        e.fa.cfg = *cfg;
-        e.fa.clock_in = d.clock_dev;
-        e.fa.clock_out = d.clock_dev + 1;
-        e.fa.hdr = (const dpwa_header *)d.peer_slot;
-        e.fa.loss_h = d.loss;
-        e.fa.coef_out = d.coef_dev;
+        e.fa = stateless_args(cfg, d.clock_dev, d.peer_slot, d.loss, d.coef_dev);
     }
-    LaunchTiming t{(hipEvent_t)start_event, (hipEvent_t)stop_event};
+    const CallerTiming timing(start_event, stop_event);
     if (oop && count == 1) {   // one resident average: the single kernel, as a resident learner runs it
         const AvgEntry &e = b.e[0];
-        HIP_TRY(launch_average(dtype, e.param, e.peer, e.n, e.fa, e.snap, (hipStream_t)stream,
-                               start_event ? &t : nullptr, true));
+        HIP_TRY(launch_average(dtype, e.param, e.peer, e.n, e.fa, e.snap, (hipStream_t)stream, timing, true));
         return DPWA_OK;
     }
-    HIP_TRY(launch_average_batch(dtype, dual, b, (hipStream_t)stream, start_event ? &t : nullptr, oop));
+    HIP_TRY(launch_average_batch(dtype, dual, b, (hipStream_t)stream, timing, oop));
     return DPWA_OK;
 }
 
@@ -1823,18 +1778,15 @@ int dpwa_learner_set_distance(dpwa_learner *l, int on)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_set_distance: a fused relay second phase is pending "
                                          "(dpwa_learner_relay_phase2 with fuse != 0), which reads no contiguous peer "
                                          "snapshot to measure against");
-    if (!l->dist_mem) {   // once, here: never inside a round
+    if (!l->dist_mem.ptr()) {   // once, here: never inside a round
         DeviceGuard dg(l->device);
         const size_t bytes = (size_t)kDistanceWorkspaceBytes + sizeof(dpwa_distance);
-        char *mem = nullptr;
-        HIP_TRY(hipMalloc(&mem, bytes));
-        hipError_t e = hipMemset(mem, 0, bytes);
+        DevBuf mem;
+        HIP_TRY(mem.alloc(bytes));
+        hipError_t e = hipMemset(mem.ptr(), 0, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            (void)hipFree(mem);
-            return set_error(DPWA_ERR_HIP, "dpwa_learner_set_distance: %s", hipGetErrorString(e));
-        }
-        l->dist_mem = mem;
+        if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "dpwa_learner_set_distance: %s", hipGetErrorString(e));
+        l->dist_mem = std::move(mem);
     }
     l->track = true;
     return DPWA_OK;
@@ -1843,7 +1795,7 @@ int dpwa_learner_set_distance(dpwa_learner *l, int on)
 int dpwa_learner_distance(dpwa_learner *l, const dpwa_distance **dev)
 {
     if (!l || !dev) return set_error(DPWA_ERR_ARG, "dpwa_learner_distance: NULL argument");
-    if (!l->dist_mem)
+    if (!l->dist_mem.ptr())
         return set_error(DPWA_ERR_STATE, "dpwa_learner_distance: distance tracking was never switched on "
                                          "(dpwa_learner_set_distance)");
     *dev = dist_record(l);
@@ -1861,7 +1813,7 @@ int dpwa_learner_set_reuse_guard(dpwa_learner *l, int on)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_reuse_guard: NULL learner");
     l->reuse_guard = on != 0;
-    l->window_src = nullptr;   // a resident learner's window guard starts afresh at the next publish
+    l->window.src = nullptr;   // a resident learner's window guard starts afresh at the next publish
     return DPWA_OK;
 }
 
@@ -1871,15 +1823,11 @@ static int relocate_impl(dpwa_learner *l, hipStream_t s)
 {
     const int k = (int)(l->version % 2);
     if (!l->resident || l->res_slot == k) return DPWA_OK;
-    int rc = wait_slot_readers(l, k, s);
-    if (rc) return rc;
-    if ((rc = wait_window_roll(l, s))) return rc;
+    if (int rc = wait_slot_readers(l, k, s)) return rc;
+    if (int rc = wait_window_roll(l, s)) return rc;
     HIP_TRY(launch_copy_payload(slot_payload(l, k), slot_payload(l, l->res_slot), (int64_t)l->payload_bytes, s));
     l->res_slot = k;
-    l->wt_valid = true;
-    l->wt_header = false;     // the publish writes the header (the clock did not move)
-    l->wt_flat = slot_payload(l, k);
-    l->wt_stream = s;
+    set_written_through(l, slot_payload(l, k), false, s);   // the publish writes the header (the clock did not move)
     return DPWA_OK;
 }
 
@@ -1891,17 +1839,13 @@ int dpwa_learner_set_resident(dpwa_learner *l, const void *init, dpwa_stream_t s
         return set_error(DPWA_ERR_STATE, "dpwa_learner_set_resident: only before the first publish");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    int rc = wait_slot_readers(l, 0, s);
-    if (rc) return rc;
+    if (int rc = wait_slot_readers(l, 0, s)) return rc;
     char *dst = slot_payload(l, 0);
     if (l->payload_bytes && dst != init)
         HIP_TRY(hipMemcpyAsync(dst, init, l->payload_bytes, hipMemcpyDeviceToDevice, s));
     l->resident = true;
     l->res_slot = 0;
-    l->wt_valid = true;
-    l->wt_header = false;
-    l->wt_flat = dst;
-    l->wt_stream = s;
+    set_written_through(l, dst, false, s);
     return DPWA_OK;
 }
 
@@ -1926,15 +1870,15 @@ int dpwa_learner_window_hits(dpwa_learner *l, uint32_t *hits)
     if (!l || !hits) return set_error(DPWA_ERR_ARG, "dpwa_learner_window_hits: NULL argument");
     DeviceGuard dg(l->device);
     *hits = 0;
-    if (!l->window_sample) return DPWA_OK;
-    if (l->window_src) {   // check the window open now (or closed, not yet checked); keep its samples
-        hipStream_t s = l->window_stream;
-        HIP_TRY(launch_window_roll(l->window_src, nullptr, (int64_t)l->payload_bytes, l->window_sample,
-                                   &l->ctl->window_dirty, &l->ctl->window_hits, l->window_host_dev, l->window_gen, 0,
-                                   s));
+    WindowGuard &w = l->window;
+    if (!w.sample.ptr()) return DPWA_OK;
+    if (w.src) {   // check the window open now (or closed, not yet checked); keep its samples
+        hipStream_t s = w.rolled.stream();
+        HIP_TRY(launch_window_roll(w.src, nullptr, (int64_t)l->payload_bytes, w.sample.ptr(), &l->ctl->window_dirty,
+                                   &l->ctl->window_hits, w.hits.dev, w.gen, 0, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    *hits = __atomic_load_n(l->window_host, __ATOMIC_ACQUIRE);
+    *hits = __atomic_load_n(w.hits.host(), __ATOMIC_ACQUIRE);
     return DPWA_OK;
 }
 
@@ -1965,21 +1909,22 @@ int dpwa_learner_read_snapshot(dpwa_learner *l, void *header_out, void *payload_
                 return DPWA_OK;   // nothing published: the reference replies without state
             }
             k = (int)((v - 1) % 2);
-            if (!l->read_stream) {   // created at the first host read: no stream (and no hardware
-                                     // queue share) for learners nobody reads over the wire
-                HIP_TRY(hipEventCreateWithFlags(&l->ev_read, hipEventDisableTiming));
-                HIP_TRY(hipStreamCreateWithFlags(&l->read_stream, hipStreamNonBlocking));
+            if (!l->read_stream.h) {   // created at the first host read: no stream (and no hardware
+                                       // queue share) for learners nobody reads over the wire
+                HIP_TRY(l->ev_read.init());
+                HIP_TRY(l->read_stream.create());
             }
             // order after the publish (and everything before it) on the publisher's stream
-            HIP_TRY(hipEventRecord(l->ev_read, l->publish_stream[k]));
+            HIP_TRY(hipEventRecord(l->ev_read.h, l->published[k].stream()));
         }
-        HIP_TRY(hipStreamWaitEvent(l->read_stream, l->ev_read, 0));
-        const char *slot = l->slots + (size_t)k * l->slot_stride;
-        HIP_TRY(hipMemcpyAsync(header_out, slot, kHeader, hipMemcpyDeviceToHost, l->read_stream));
+        hipStream_t rs = l->read_stream.h;
+        HIP_TRY(hipStreamWaitEvent(rs, l->ev_read.h, 0));
+        const char *slot = l->slot_mem.ptr + (size_t)k * l->slot_stride;
+        HIP_TRY(hipMemcpyAsync(header_out, slot, kHeader, hipMemcpyDeviceToHost, rs));
         if (payload_bytes)
             HIP_TRY(hipMemcpyAsync(payload_out, slot + kPayloadOff, (size_t)payload_bytes, hipMemcpyDeviceToHost,
-                                   l->read_stream));
-        HIP_TRY(hipStreamSynchronize(l->read_stream));
+                                   rs));
+        HIP_TRY(hipStreamSynchronize(rs));
         // a slot is rewritten two publishes later: if that happened meanwhile, read again
         std::lock_guard<std::mutex> g(l->pub_mu);
         if (l->version < v + 2 && ((const dpwa_header *)header_out)->version == v) {
@@ -1999,9 +1944,10 @@ int dpwa_learner_fetch_host(dpwa_learner *l, const void *header, const void *pay
     DeviceGuard dg(l->device);
     (void)stream;
     // The copy waits only for the last reader of the staging buffer (every consumer of a fetch
-    // records ev_stage_done), not for all the work queued on the caller's stream: it starts
+    // records stage_done), not for all the work queued on the caller's stream: it starts
     // at once, beside a training step already enqueued.
-    if (l->stage_read[0]) HIP_TRY(hipStreamWaitEvent(l->side, l->ev_stage_done[0], 0));
+    hipStream_t side = l->side.h;
+    HIP_TRY(l->stage_done[0].wait(side));
     // Pageable host sources: the calls return once the host bytes have been taken.  A
     // page-locked source is copied asynchronously, so the copy is waited for: either way the
     // caller may reuse its buffer when this returns.
@@ -2009,17 +1955,12 @@ int dpwa_learner_fetch_host(dpwa_learner *l, const void *header, const void *pay
     const bool pinned = payload_bytes > 0 && hipPointerGetAttributes(&attr, payload) == hipSuccess &&
                         attr.type == hipMemoryTypeHost;
     (void)hipGetLastError();   // a pageable pointer is "invalid" to hipPointerGetAttributes
-    HIP_TRY(hipMemcpyAsync(l->staging, header, kHeader, hipMemcpyHostToDevice, l->side));
+    HIP_TRY(hipMemcpyAsync(l->staging.ptr(), header, kHeader, hipMemcpyHostToDevice, side));
     if (payload_bytes)
-        HIP_TRY(hipMemcpyAsync(l->staging + kPayloadOff, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, l->side));
-    HIP_TRY(hipEventRecord(l->ev_fetched, l->side));
-    if (pinned) HIP_TRY(hipEventSynchronize(l->ev_fetched));
-    l->src = l->staging;
-    l->src_copied = true;
-    l->src_stage = 0;
-    l->src_owner = nullptr;
-    l->src_slot = -1;
-    l->have_fetch = true;
+        HIP_TRY(hipMemcpyAsync(l->staging.ptr() + kPayloadOff, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, side));
+    HIP_TRY(l->fetched.record(side));
+    if (pinned) HIP_TRY(hipEventSynchronize(l->fetched.event()));
+    set_source(l, l->staging.ptr(), 0, true, nullptr, -1);
     l->have_factor = false;
     return DPWA_OK;
 }
@@ -2033,14 +1974,13 @@ int dpwa_learner_relay_enable(dpwa_learner *l, int world, int rank)
     const int64_t payload16 = (int64_t)round_up(l->payload_bytes, 16);
     l->relay_stripe = (int64_t)round_up((size_t)((payload16 + world - 1) / world), kPayloadOff);
     HIP_TRY(devmem_alloc(l->relay_mem, (size_t)l->relay_stripe * world, l->device));
-    l->relay_buf = l->relay_mem.ptr;
-    HIP_TRY(hipEventCreateWithFlags(&l->ev_relay, hipEventDisableTiming));
+    HIP_TRY(l->relay_done.init());
     l->relay_world = world;
     l->relay_rank = rank;
     l->relay_slots.assign((size_t)world, nullptr);
     l->relay_bufs.assign((size_t)world, nullptr);
-    l->relay_slots[rank] = l->slots;
-    l->relay_bufs[rank] = l->relay_buf;
+    l->relay_slots[rank] = l->slot_mem.ptr;
+    l->relay_bufs[rank] = l->relay_mem.ptr;
     l->relay_on = true;
     return DPWA_OK;
 }
@@ -2051,7 +1991,7 @@ int dpwa_learner_relay_handle(dpwa_learner *l, void *handle_out, int64_t handle_
         return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_handle: relay not enabled or short buffer");
     DeviceGuard dg(l->device);
     IpcBlob b = make_blob(l, l->relay_mem, l->relay_stripe);
-    if (!b.vmm) HIP_TRY(hipIpcGetMemHandle(&b.handle, l->relay_buf));
+    if (!b.vmm) HIP_TRY(hipIpcGetMemHandle(&b.handle, l->relay_mem.ptr));
     memset(handle_out, 0, (size_t)handle_len);
     memcpy(handle_out, &b, sizeof(b));
     l->exported = true;
@@ -2118,8 +2058,8 @@ static int relay_args(dpwa_learner *l, const int32_t *picks_dev, uint64_t versio
         a.slots[r] = l->relay_slots[r];
         a.relays[r] = l->relay_bufs[r];
     }
-    a.relay_mine = l->relay_buf;
-    a.staging = l->staging;
+    a.relay_mine = l->relay_mem.ptr;
+    a.staging = l->staging.ptr();
     a.picks = picks_dev;
     a.slot_off = (int64_t)((version - 1) % 2) * (int64_t)l->slot_stride;
     a.stripe = l->relay_stripe;
@@ -2132,9 +2072,9 @@ static int relay_args(dpwa_learner *l, const int32_t *picks_dev, uint64_t versio
 int dpwa_learner_relay_wait(dpwa_learner *l, dpwa_stream_t stream)
 {
     if (!l || !l->relay_on) return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_wait: relay not enabled");
-    if (l->relay_pending) {
+    if (l->relay_done.recorded()) {
         DeviceGuard dg(l->device);
-        HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, l->ev_relay, 0));
+        HIP_TRY(l->relay_done.wait((hipStream_t)stream));
     }
     return DPWA_OK;
 }
@@ -2145,30 +2085,27 @@ int dpwa_learner_relay_phase1(dpwa_learner *l, const int32_t *picks_dev, uint64_
     if (!l || !l->relay_on || !picks_dev || blocks < 1)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_phase1: bad arguments");
     RelayArgs a;
-    int rc = relay_args(l, picks_dev, version, a);
-    if (rc) return rc;
+    if (int rc = relay_args(l, picks_dev, version, a)) return rc;
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipEventRecord(l->ev_issue, s));
-    HIP_TRY(hipStreamWaitEvent(l->side, l->ev_issue, 0));
-    HIP_TRY(launch_relay(1, a, blocks, l->side));
-    HIP_TRY(hipEventRecord(l->ev_relay, l->side));
-    l->relay_pending = true;
+    HIP_TRY(issue_after(l, s, l->side.h));
+    HIP_TRY(launch_relay(1, a, blocks, l->side.h));
+    HIP_TRY(l->relay_done.record(l->side.h));
     return DPWA_OK;
 }
 
 // Phase 2 on the side stream: my_pick's stripes gathered into staging.
 static int relay_phase2_now(dpwa_learner *l, const RelayArgs &a, int my_pick, int blocks)
 {
-    if (my_pick >= 0 && l->consumed_once && l->consume_stream) {   // WAR on staging
-        HIP_TRY(hipEventRecord(l->ev_consumed, l->consume_stream));
-        HIP_TRY(hipStreamWaitEvent(l->side, l->ev_consumed, 0));
+    hipStream_t side = l->side.h;
+    if (my_pick >= 0) {   // WAR on staging
+        // covered_by = nullptr: a consumption on the default stream is indistinguishable from "never"
+        HIP_TRY(l->consumed.order(side, nullptr));
+        HIP_TRY(l->stage_done[0].wait(side));
     }
-    if (my_pick >= 0 && l->stage_read[0]) HIP_TRY(hipStreamWaitEvent(l->side, l->ev_stage_done[0], 0));
-    HIP_TRY(launch_relay(2, a, blocks, l->side));
-    HIP_TRY(hipEventRecord(l->ev_relay, l->side));
-    l->relay_pending = true;
-    if (my_pick >= 0) HIP_TRY(hipEventRecord(l->ev_fetched, l->side));
+    HIP_TRY(launch_relay(2, a, blocks, side));
+    HIP_TRY(l->relay_done.record(side));
+    if (my_pick >= 0) HIP_TRY(l->fetched.record(side));
     return DPWA_OK;
 }
 
@@ -2201,7 +2138,7 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
     l->relay_deferred = false;
     if (fuse && my_pick >= 0) {
         // everything the fused average needs is on the side stream now (phase 1, the barrier)
-        HIP_TRY(hipEventRecord(l->ev_fetched, l->side));
+        HIP_TRY(l->fetched.record(l->side.h));
         l->relay_saved = a;
         l->relay_saved_pick = my_pick;
         l->relay_saved_blocks = blocks;
@@ -2210,12 +2147,7 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
         if ((rc = relay_phase2_now(l, a, my_pick, blocks))) return rc;
     }
     if (my_pick >= 0) {
-        l->src = l->staging;
-        l->src_copied = true;
-        l->src_stage = 0;
-        l->src_owner = nullptr;
-        l->src_slot = -1;
-        l->have_fetch = true;
+        set_source(l, l->staging.ptr(), 0, true, nullptr, -1);
         l->have_factor = false;
     }
     return DPWA_OK;
@@ -2226,19 +2158,8 @@ int dpwa_learner_time_averages(dpwa_learner *l, int capacity)
     if (!l || capacity < 0) return set_error(DPWA_ERR_ARG, "dpwa_learner_time_averages: bad arguments");
     DeviceGuard dg(l->device);
     HIP_TRY(hipDeviceSynchronize());
-    for (auto &t : l->timing) {
-        (void)hipEventDestroy(t.start);
-        (void)hipEventDestroy(t.stop);
-    }
-    l->timing.clear();
-    l->timing_used = 0;
     l->timing_armed = false;
-    for (int i = 0; i < capacity; ++i) {
-        LaunchTiming t{};
-        HIP_TRY(hipEventCreate(&t.start));
-        HIP_TRY(hipEventCreate(&t.stop));
-        l->timing.push_back(t);
-    }
+    HIP_TRY(l->avg_times.reserve(capacity));
     return DPWA_OK;
 }
 
@@ -2253,15 +2174,8 @@ int dpwa_learner_read_average_times(dpwa_learner *l, float *us_out, int max, int
 {
     if (!l || !count || (max > 0 && !us_out)) return set_error(DPWA_ERR_ARG, "dpwa_learner_read_average_times: bad arguments");
     DeviceGuard dg(l->device);
-    const int k = l->timing_used < max ? l->timing_used : max;
-    for (int i = 0; i < k; ++i) {
-        HIP_TRY(hipEventSynchronize(l->timing[i].stop));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, l->timing[i].start, l->timing[i].stop));
-        us_out[i] = ms * 1000.f;
-    }
-    *count = k;
-    l->timing_used = 0;
+    HIP_TRY(l->avg_times.read(us_out, max, count));
+    l->avg_times.used = 0;   // the pairs are handed out again (a fetch's are not)
     return DPWA_OK;
 }
 
@@ -2270,18 +2184,7 @@ int dpwa_learner_time_fetches(dpwa_learner *l, int capacity)
     if (!l || capacity < 0) return set_error(DPWA_ERR_ARG, "dpwa_learner_time_fetches: bad arguments");
     DeviceGuard dg(l->device);
     HIP_TRY(hipDeviceSynchronize());
-    for (auto &t : l->fetch_timing) {
-        (void)hipEventDestroy(t.start);
-        (void)hipEventDestroy(t.stop);
-    }
-    l->fetch_timing.clear();
-    l->fetch_timing_used = 0;
-    for (int i = 0; i < capacity; ++i) {
-        LaunchTiming t{};
-        HIP_TRY(hipEventCreate(&t.start));
-        HIP_TRY(hipEventCreate(&t.stop));
-        l->fetch_timing.push_back(t);
-    }
+    HIP_TRY(l->fetch_times.reserve(capacity));
     return DPWA_OK;
 }
 
@@ -2289,21 +2192,14 @@ int dpwa_learner_read_fetch_times(dpwa_learner *l, float *us_out, int max, int *
 {
     if (!l || !count || (max > 0 && !us_out)) return set_error(DPWA_ERR_ARG, "dpwa_learner_read_fetch_times: bad arguments");
     DeviceGuard dg(l->device);
-    const int k = l->fetch_timing_used < max ? l->fetch_timing_used : max;
-    for (int i = 0; i < k; ++i) {
-        HIP_TRY(hipEventSynchronize(l->fetch_timing[i].stop));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, l->fetch_timing[i].start, l->fetch_timing[i].stop));
-        us_out[i] = ms * 1000.f;
-    }
-    *count = k;
+    HIP_TRY(l->fetch_times.read(us_out, max, count));
     return DPWA_OK;
 }
 
 int dpwa_learner_side_stream(dpwa_learner *l, dpwa_stream_t *stream)
 {
     if (!l || !stream) return set_error(DPWA_ERR_ARG, "dpwa_learner_side_stream: NULL argument");
-    *stream = l->side;
+    *stream = l->side.h;
     return DPWA_OK;
 }
 
@@ -2312,9 +2208,8 @@ int dpwa_learner_wait_fetch(dpwa_learner *l, dpwa_stream_t stream)
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_wait_fetch: NULL learner");
     if (l->have_fetch && l->src_copied) {
         DeviceGuard dg(l->device);
-        int rc = relay_materialize(l);
-        if (rc) return rc;
-        HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, l->ev_fetched, 0));
+        if (int rc = relay_materialize(l)) return rc;
+        HIP_TRY(l->fetched.wait((hipStream_t)stream));
     }
     return DPWA_OK;
 }
@@ -2350,14 +2245,11 @@ int dpwa_learner_copy_fetched(dpwa_learner *l, void *dst_dev, dpwa_stream_t stre
     if (!l->have_fetch || !l->src) return set_error(DPWA_ERR_STATE, "dpwa_learner_copy_fetched: no fetch in flight");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    int rc = relay_materialize(l);
-    if (rc) return rc;
-    if (l->src_copied) HIP_TRY(hipStreamWaitEvent(s, l->ev_fetched, 0));
+    if (int rc = relay_materialize(l)) return rc;
+    if (l->src_copied) HIP_TRY(l->fetched.wait(s));
     if (l->payload_bytes)
         HIP_TRY(hipMemcpyAsync(dst_dev, l->src + kPayloadOff, l->payload_bytes, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(staging_read(l, s));   // a later pull into this staging buffer waits for this copy
-    l->consume_stream = s;   // the staging buffer / peer slot is read on s
-    l->consumed_once = true;
+    HIP_TRY(note_consumed(l, s));   // a later pull into this staging buffer waits for this copy
     return DPWA_OK;
 }
 
@@ -2370,24 +2262,23 @@ int dpwa_learner_copy_fetched(dpwa_learner *l, void *dst_dev, dpwa_stream_t stre
 // queue another lane already uses).
 static int probe_since(dpwa_learner *l, hipEvent_t since, float *ms)
 {
-    if (!l->probe_stream) {
-        hipStream_t ps = nullptr;
-        hipEvent_t pe = nullptr;
-        hipError_t e = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
-        if (e == hipSuccess && (e = hipEventCreate(&pe)) != hipSuccess) (void)hipStreamDestroy(ps);
+    if (!l->probe.stream.h) {
+        Probe p;
+        hipError_t e = p.stream.create();
+        if (e == hipSuccess) e = p.ev.init(hipEventDefault);
         if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "probe stream: %s", hipGetErrorString(e));
-        l->probe_stream = ps;
-        l->ev_probe = pe;
+        l->probe = std::move(p);
     }
-    HIP_TRY(hipEventRecord(l->ev_probe, l->probe_stream));
+    const hipEvent_t ev_probe = l->probe.ev.h;
+    HIP_TRY(hipEventRecord(ev_probe, l->probe.stream.h));
     const int64_t t0 = now_ns();
     for (;;) {
-        const hipError_t q = hipEventQuery(l->ev_probe);
+        const hipError_t q = hipEventQuery(ev_probe);
         if (q == hipSuccess) break;
         if (q != hipErrorNotReady) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(q));
         if (now_ns() - t0 > kProbeWaitUs * 1000) return set_error(DPWA_ERR_STATE, "probe held up");
     }
-    HIP_TRY(hipEventElapsedTime(ms, since, l->ev_probe));
+    HIP_TRY(hipEventElapsedTime(ms, since, ev_probe));
     return DPWA_OK;
 }
 
@@ -2397,7 +2288,7 @@ int dpwa_learner_fetch_state(dpwa_learner *l, int64_t timeout_ms, int *state)
     *state = DPWA_FETCH_LANDED;
     if (!l->have_fetch || !l->src_copied || l->relay_deferred) return DPWA_OK;
     DeviceGuard dg(l->device);
-    const hipError_t e = hipEventQuery(l->ev_fetched);
+    const hipError_t e = l->fetched.query();
     if (e == hipSuccess) return DPWA_OK;
     if (e != hipErrorNotReady) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
     *state = DPWA_FETCH_IN_FLIGHT;
@@ -2410,11 +2301,11 @@ int dpwa_learner_fetch_state(dpwa_learner *l, int64_t timeout_ms, int *state)
     const int64_t waited_ns = now_ns() - l->fetch_issue_ns;
     if (waited_ns < timeout_ms * 1000000LL) return DPWA_OK;
     if (l->issue_evented && waited_ns < (timeout_ms + kMaxBacklogMs) * 1000000LL) {
-        const hipError_t q = hipEventQuery(l->ev_issue);
+        const hipError_t q = hipEventQuery(l->ev_issue.h);
         if (q == hipErrorNotReady) return DPWA_OK;        // the request has not gone out yet
         if (q != hipSuccess) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(q));
         float ms = 0.f;
-        if (probe_since(l, l->ev_issue, &ms) == DPWA_OK && ms >= 0.f) {
+        if (probe_since(l, l->ev_issue.h, &ms) == DPWA_OK && ms >= 0.f) {
             *state = ms >= (float)timeout_ms ? DPWA_FETCH_TIMED_OUT : DPWA_FETCH_IN_FLIGHT;
             return DPWA_OK;
         }
@@ -2453,7 +2344,7 @@ int dpwa_learner_set_rescue_cap(dpwa_learner *l, int cap)
 int dpwa_learner_fetch_stream(dpwa_learner *l, dpwa_stream_t *stream)
 {
     if (!l || !stream) return set_error(DPWA_ERR_ARG, "dpwa_learner_fetch_stream: NULL argument");
-    *stream = l->fetch_stream ? l->fetch_stream : l->side;
+    *stream = l->fetch_stream ? l->fetch_stream : l->side.h;
     return DPWA_OK;
 }
 
@@ -2471,15 +2362,15 @@ int dpwa_learner_pointers(dpwa_learner *l, double **clock_dev, dpwa_coef **coef_
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_pointers: NULL learner");
     if (clock_dev) *clock_dev = &l->ctl->clock[l->cur];
     if (coef_dev) *coef_dev = &l->ctl->coef;
-    if (staging_header_dev) *staging_header_dev = (dpwa_header *)l->staging;
-    if (staging_payload_dev) *staging_payload_dev = l->staging + kPayloadOff;
+    if (staging_header_dev) *staging_header_dev = (dpwa_header *)l->staging.ptr();
+    if (staging_payload_dev) *staging_payload_dev = l->staging.ptr() + kPayloadOff;
     return DPWA_OK;
 }
 
 int dpwa_learner_status_word(dpwa_learner *l, int32_t **status_word)
 {
     if (!l || !status_word) return set_error(DPWA_ERR_ARG, "dpwa_learner_status_word: NULL argument");
-    *status_word = l->host_status;
+    *status_word = l->status.host();
     return DPWA_OK;
 }
 
@@ -2515,11 +2406,11 @@ int dpwa_learner_poll_status(dpwa_learner *l, int *done, int32_t *status)
 {
     if (!l || !done || !status) return set_error(DPWA_ERR_ARG, "dpwa_learner_poll_status: NULL argument");
     DeviceGuard dg(l->device);
-    hipError_t e = hipEventQuery(l->ev_factor);
+    hipError_t e = l->factor_done.query();
     if (e != hipSuccess && e != hipErrorNotReady) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
     *done = e == hipSuccess ? 1 : 0;
     // Sticky word: the factor kernel writes only non-OK statuses; reading clears it.
-    volatile int32_t *w = l->host_status;
+    volatile int32_t *w = l->status.host();
     *status = *w;
     if (*status != DPWA_STATUS_OK) *w = DPWA_STATUS_OK;
     return DPWA_OK;

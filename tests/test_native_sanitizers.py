@@ -60,6 +60,29 @@ def test_gossip_board_under_asan_ubsan(tmp_path):
     assert "board stress ok" in r.stdout
 
 
+def test_stream_ordering_types_under_asan_ubsan(tmp_path):
+    """order.hpp's StreamMark and DoneEvent -- every cross-stream wait of a learner goes through
+    them -- against recording stand-ins of the five HIP calls they make
+    (tests/native/order_check.cpp, which links no HIP runtime): a mark never noted or noted on
+    the same stream makes no call; another stream gives one record on the noted stream and then
+    one wait on the waiter; `covered_by` is what is compared; a wait before any record makes no
+    call; a failed record is returned and not waited for; every event is destroyed once, moves
+    included."""
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    cxx = os.path.join(rocm, "lib", "llvm", "bin", "clang++")
+    if not os.path.exists(cxx):
+        pytest.skip("no ROCm clang++")
+    exe = str(tmp_path / "order_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", *SAN, "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+           os.path.join(ROOT, "tests/native/order_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "order check ok" in r.stdout
+
+
 def _tsan_build(tmp_path):
     gxx = shutil.which("g++")
     if gxx is None:
