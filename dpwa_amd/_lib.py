@@ -82,6 +82,22 @@ class Distance(ctypes.Structure):
                 ("n", ctypes.c_int64)]
 
 
+class ParamRange(ctypes.Structure):
+    """dpwa_param_range: where one parameter tensor lies in the payload."""
+    _fields_ = [("byte_offset", ctypes.c_int64), ("byte_length", ctypes.c_int64), ("dtype", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class ParamSizes(ctypes.Structure):
+    """dpwa_param_sizes: the buffers of the per-parameter distance."""
+    _fields_ = [("table_bytes", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64),
+                ("record_bytes", ctypes.c_int64), ("max_rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+PARAM_ALIGN = 256            # DPWA_PARAM_ALIGN
+PARAM_HEAD_BYTES = 16        # dpwa_param_distance_head {double clock; int64 count}; 16-byte pairs follow
+
+
 class Interp(ctypes.Structure):
     _fields_ = [("method", ctypes.c_int32), ("reserved", ctypes.c_int32), ("value", ctypes.c_double),
                 ("divergence_threshold", ctypes.c_double)]
@@ -122,6 +138,14 @@ SIGNATURES = {
     "dpwa_average_tracked": [_i32, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp],
     "dpwa_distance_finish": [_vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "dpwa_param_ranges_check": [ctypes.POINTER(ParamRange), _i64, _i32, _i64, ctypes.POINTER(Layout)],
+    "dpwa_param_distance_sizes": [ctypes.POINTER(ParamRange), _i64, ctypes.POINTER(ParamSizes)],
+    "dpwa_param_distance_table": [ctypes.POINTER(ParamRange), _i64, _vp],
+    "dpwa_measure_param_distance": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_param_distance_finish": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_learner_set_param_distance": [_vp, ctypes.POINTER(ParamRange), _i64, _int],
+    "dpwa_learner_param_distance": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64)],
+    "dpwa_learner_param_distance_rounds": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     "dpwa_learner_set_distance": [_vp, _int],
     "dpwa_learner_distance": [_vp, ctypes.POINTER(_vp)],
     "dpwa_layout_digest": [ctypes.POINTER(Layout), _i64, ctypes.POINTER(ctypes.c_uint32)],

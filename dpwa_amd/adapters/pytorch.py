@@ -71,7 +71,7 @@ class DpwaPyTorchAdapter:
     not use it."""
 
     def __init__(self, net, name, config_file, write_through=True, transport="device", reuse_guard=True,
-                 resident=False, track_distance=False, **connection_kwargs):
+                 resident=False, track_distance=False, distance_every=1, **connection_kwargs):
         """transport: "device" (peers are learners of this process or of the torch.distributed
         job, pulled from HBM/over xGMI) or "wire" (peers are reached over TCP at the YAML's
         host/port with the reference's protocol -- e.g. reference CPU nodes; dpwa_amd/bridge.py).
@@ -79,7 +79,12 @@ class DpwaPyTorchAdapter:
         track_distance (extension, off by default): every round that averages also measures how far
         the model was from the peer's snapshot it averaged with (``last_distance``; see
         ``DpwaConnection``).  For a single-dtype model the averaging kernel does it with no extra
-        bytes in all three forms; a model that mixes dtypes pays one more read of both operands."""
+        bytes in all three forms; a model that mixes dtypes pays one more read of both operands.
+
+        track_distance="per_parameter" (device transport): also the same two sums for every parameter
+        tensor, ``last_distance.parameters`` -> ``{name: ...}`` keyed by ``named_parameters()`` names
+        (``ParameterDistances``), measured on every ``distance_every``-th round that averages by a
+        separate pass that reads both operands once more."""
         connection_kwargs = dict(connection_kwargs, track_distance=track_distance)
         if resident and transport != "device":
             raise ValueError("resident parameters need the device transport")
@@ -91,6 +96,8 @@ class DpwaPyTorchAdapter:
             self._conn = WireConnection(name, config_file, codec=SnapshotCodec.from_flat(self._flat),
                                         **connection_kwargs)
         elif transport == "device":
+            if track_distance == "per_parameter":
+                connection_kwargs.update(parameter_ranges=self._flat.parameter_ranges(), distance_every=distance_every)
             self._conn = DpwaConnection(name, config_file, layout=self._flat.layout, **connection_kwargs)
         else:
             raise ValueError("transport must be 'device' or 'wire'")

@@ -24,6 +24,9 @@
 //             by a tracked form of the fused average from the operands it holds anyway
 //             (k_lerp_tracked), or by a stand-alone pass (k_distance*), added across workgroups with
 //             the hardware fp64 add and finished by k_distance_finish.
+//             Opt-in too: the same sums for every parameter tensor over its own elements, by a
+//             stand-alone pass that looks each span's tensors up in a device table
+//             (k_param_distance) and one finishing workgroup per tensor (k_param_distance_finish).
 //  * factor:  the same fp64 math as a one-thread kernel for the split API.
 //  * publish: update_send's snapshot (dpwa.py:111-116, pytorch.py:49-53) -- clock += 1 on
 //             the device and one copy of the flat buffer into a snapshot slot behind its
@@ -810,6 +813,209 @@ __global__ __launch_bounds__(kDistFinishBlock) void k_distance_finish(double *__
     out->n = n;
 }
 
+// ---------------------------------------------------------------- distance to the peer, per tensor
+// The same two sums for every parameter tensor of the model over that tensor's own elements only
+// (include/dpwa_hip.h "per-parameter distance"): a stand-alone pass beside k_distance, then one
+// finishing workgroup per tensor.  A tensor starts on a 256-byte boundary of the payload only, so
+// each 256-byte quarter of a 1-KiB span -- 16 lanes' items -- holds bytes of at most one tensor
+// (and perhaps the gap behind it): a span holds at most four.  The tensors are a table in device
+// memory sorted by byte_begin (a model has tens to thousands: too many for kernel arguments); the
+// tensor of a quarter is the last entry that begins at or before it, found by a binary search on
+// uniform values while the span's loads are in flight.  Bytes of no tensor (the 256-byte gaps, a
+// segment's padding) are loaded with their item but never enter a sum: every element at or beyond
+// its tensor's end is masked.
+//
+// Tensor t owns rows [first_row, first_row + rows), rows = min(spans it touches, kParamDistRows),
+// each a 128-byte row as above; the tensor's span s (counted from the span holding its first
+// byte) adds into row s mod rows, so that the workgroups in flight on one large tensor do not
+// meet on one address, as in the whole-model pass.
+
+// The last entry with begin <= off, or -1 (uniform in, uniform out).
+__device__ __forceinline__ int param_lookup(const ParamEntry *__restrict__ table, int count, int64_t off)
+{
+    int lo = 0, hi = count;   // entries below lo begin at or before off, entries from hi on after it
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (table[mid].begin <= off) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;
+}
+
+// One element into the sums when `in` (it lies wholly before its tensor's end).
+__device__ __forceinline__ void dist_term_if(bool in, double q, double p, double &d2, double &n2)
+{
+    const double d = q - p;
+    const double a = d2 + d * d, b = n2 + p * p;
+    d2 = in ? a : d2;
+    n2 = in ? b : n2;
+}
+
+// A lane's 16-byte item at payload byte `at`, the elements whose bytes end at or before `end` only.
+__device__ __forceinline__ void dist_add_until(int32_t dtype, u32x4 q, u32x4 p, int64_t at, int64_t end, double &d2,
+                                               double &n2)
+{
+    const int64_t room = end - at;   // bytes of the tensor from this item on (<= 0: none)
+    const uint32_t qw[4] = {q.x, q.y, q.z, q.w}, pw[4] = {p.x, p.y, p.z, p.w};
+    if (dtype == DPWA_F32) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            dist_term_if(room >= 4 * (j + 1), (double)__uint_as_float(qw[j]), (double)__uint_as_float(pw[j]), d2, n2);
+    } else if (dtype == DPWA_BF16) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            dist_term_if(room >= 4 * j + 2, (double)bf_lo(qw[j]), (double)bf_lo(pw[j]), d2, n2);
+            dist_term_if(room >= 4 * j + 4, (double)bf_hi(qw[j]), (double)bf_hi(pw[j]), d2, n2);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f16x2v qh = __builtin_bit_cast(f16x2v, qw[j]), ph = __builtin_bit_cast(f16x2v, pw[j]);
+            dist_term_if(room >= 4 * j + 2, (double)qh.x, (double)ph.x, d2, n2);
+            dist_term_if(room >= 4 * j + 4, (double)qh.y, (double)ph.y, d2, n2);
+        }
+    }
+}
+
+// The sum over the 16 lanes of a quarter, the same in each of them: four xor steps.
+__device__ __forceinline__ double quarter_sum(double v)
+{
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// The row of tensor entry e that the payload span `span` adds into.
+__device__ __forceinline__ double *param_row(double *acc, const ParamEntry &e, int64_t span)
+{
+    const uint32_t s = (uint32_t)(span - e.begin / (kStreamBlock * 16));   // the tensor's own span index (grid < 2^31)
+    return acc + ((size_t)e.first_row + (size_t)(s % (uint32_t)e.rows)) * kDistAccStride;
+}
+
+// `total`: the payload's bytes; the vector loads cover its whole 16-byte items, and the bytes
+// behind the last whole item (a single-dtype payload of n elements may end inside one) are read
+// element by element by the lane whose item they would be.  One-wave workgroups, an exact grid of
+// spans over the payload.  The loads take the default cache policy, as k_distance's.
+__global__ __launch_bounds__(kStreamBlock) void k_param_distance(const u32x4 *__restrict__ param,
+                                                                 const u32x4 *__restrict__ peer, int64_t total,
+                                                                 const ParamEntry *__restrict__ table, int count,
+                                                                 double *__restrict__ acc)
+{
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t vbytes = total / 16 * 16;
+    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
+    const int lane = threadIdx.x;
+    const int lane_off = lane * 16;
+    u32x4 q = span_load<u32x4, 0>(span_rsrc<SPAN>(peer, span_off, vbytes), lane_off);
+    u32x4 p = span_load<u32x4, 0>(span_rsrc<SPAN>(param, span_off, vbytes), lane_off);
+    const int t0 = param_lookup(table, count, span_off);
+    double d2 = 0.0, n2 = 0.0;
+    if (t0 >= 0 && table[t0].end >= span_off + SPAN) {   // the span lies inside one tensor: k_distance's body
+        const ParamEntry e = table[t0];
+        if (e.dtype == DPWA_F32) dist_add(OpsF32{}, __builtin_bit_cast(f32x4, q), __builtin_bit_cast(f32x4, p), d2, n2);
+        else if (e.dtype == DPWA_BF16) dist_add(OpsBF16{}, q, p, d2, n2);
+        else dist_add(OpsF16{}, q, p, d2, n2);
+        d2 = wave_sum(d2);
+        n2 = wave_sum(n2);
+        if (lane < 2) unsafeAtomicAdd(param_row(acc, e, blockIdx.x) + lane, lane ? n2 : d2);
+        return;
+    }
+    const int64_t at = span_off + lane_off;
+    if (at == vbytes && at < total) {   // the payload ends inside this lane's item: its bytes one by one
+        const unsigned char *qb = (const unsigned char *)peer + at, *pb = (const unsigned char *)param + at;
+        uint32_t qw[4] = {0, 0, 0, 0}, pw[4] = {0, 0, 0, 0};
+        for (int b = 0; b < (int)(total - at); ++b) {
+            qw[b >> 2] |= (uint32_t)qb[b] << (8 * (b & 3));
+            pw[b >> 2] |= (uint32_t)pb[b] << (8 * (b & 3));
+        }
+        q = u32x4{qw[0], qw[1], qw[2], qw[3]};
+        p = u32x4{pw[0], pw[1], pw[2], pw[3]};
+    }
+    // each quarter's tensor, then this lane's own by its quarter: the table is sorted, so a later
+    // quarter's tensor is the one before it or one of the next few (a step or two forward, not another
+    // search -- a search per quarter made the pass 82.6 us against 48.5 at 16,384 tensors).  The index
+    // is the same in every lane, but the compiler emits these steps' loads as global_load_dwordx2 of
+    // one address for the wave, not as scalar loads (readfirstlane on the index does not change that).
+    int mine = -1, t = t0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        while (t + 1 < count && table[t + 1].begin <= span_off + k * 256) ++t;
+        if ((lane >> 4) == k) mine = t;
+    }
+    ParamEntry e{};
+    bool live = false;
+    if (mine >= 0) {
+        e = table[mine];
+        live = e.end > span_off + (lane >> 4) * 256;   // else the quarter is all gap
+    }
+    if (live) dist_add_until(e.dtype, q, p, at, e.end, d2, n2);
+    d2 = quarter_sum(d2);
+    n2 = quarter_sum(n2);
+    if (live && (lane & 15) < 2) unsafeAtomicAdd(param_row(acc, e, blockIdx.x) + (lane & 15), (lane & 15) ? n2 : d2);
+}
+
+// Finishing: one workgroup per tensor behind the pass (and behind the average, whose coefficients
+// it reads) on the same stream.  kParamFinishBlock lanes, lane i taking rows i, i + kParamFinishBlock,
+// ... of the tensor (all its loads in flight at once; most tensors of a model have a handful of rows,
+// and a 1024-lane workgroup for each of 16,384 small tensors took 70 us); the sums in a fixed order
+// -- a lane's rows in order, the butterfly inside each wave, then the waves in order -- and the rows
+// left zero whatever the round did.  The tensor's pair -- and, by workgroup 0, the clock and the
+// count -- is written only when the round averaged.  Agent-scope accesses, as k_distance_finish.
+constexpr int kParamFinishBlock = 256;
+static_assert(kParamDistRows % kParamFinishBlock == 0 && kParamFinishBlock % 64 == 0, "whole lanes' worth of rows");
+
+__global__ __launch_bounds__(kParamFinishBlock) void k_param_distance_finish(double *__restrict__ acc,
+                                                                            const ParamEntry *__restrict__ table,
+                                                                            dpwa_param_distance_head *__restrict__ out,
+                                                                            const dpwa_coef *__restrict__ coef,
+                                                                            int64_t count)
+{
+    constexpr int PER = kParamDistRows / kParamFinishBlock;
+    __shared__ double s_d2[kParamFinishBlock / 64], s_n2[kParamFinishBlock / 64];
+    const ParamEntry e = table[blockIdx.x];
+    double rd[PER], rn[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int row = (int)threadIdx.x + j * kParamFinishBlock;
+        rd[j] = rn[j] = 0.0;
+        if (row < e.rows) {
+            double *a = acc + ((size_t)e.first_row + row) * kDistAccStride;
+            rd[j] = __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            rn[j] = __hip_atomic_load(a + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a + 1, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    double d2 = rd[0], n2 = rn[0];
+#pragma unroll
+    for (int j = 1; j < PER; ++j) {
+        d2 = d2 + rd[j];
+        n2 = n2 + rn[j];
+    }
+    d2 = wave_sum(d2);
+    n2 = wave_sum(n2);
+    if ((threadIdx.x & 63) == 0) {
+        s_d2[threadIdx.x >> 6] = d2;
+        s_n2[threadIdx.x >> 6] = n2;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0 || (coef && coef->status != DPWA_STATUS_OK)) return;
+    d2 = s_d2[0];
+    n2 = s_n2[0];
+#pragma unroll
+    for (int w = 1; w < kParamFinishBlock / 64; ++w) {
+        d2 = d2 + s_d2[w];
+        n2 = n2 + s_n2[w];
+    }
+    dpwa_param_pair *pair = reinterpret_cast<dpwa_param_pair *>(out + 1) + blockIdx.x;   // the pairs follow the head
+    pair->dist2 = d2;
+    pair->norm2 = n2;
+    if (blockIdx.x == 0) {
+        out->clock = coef ? coef->new_clock : 0.0;
+        out->count = count;
+    }
+}
+
 // The relay's fused second phase: the fused average reads the peer's snapshot stripe by stripe
 // where the relay left it (stripe s in rank s's relay buffer, the peer's own stripe in its slot,
 // ours in local HBM) instead of gathering it into staging first.
@@ -1247,6 +1453,27 @@ hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_co
 {
     if (!acc || !out) return hipErrorInvalidValue;
     return launch(k_distance_finish, dim3(1), dim3(kDistFinishBlock), s, timing, acc, out, coef, n);
+}
+
+hipError_t launch_param_distance(const void *param, const void *peer, int64_t total, const ParamEntry *table,
+                                 int64_t count, double *acc, hipStream_t s, const LaunchTiming *timing)
+{
+    if (total < 0 || count < 1 || count > 0x7fffffffLL || !table || !acc || !aligned16(param) || !aligned16(peer))
+        return hipErrorInvalidValue;
+    const int64_t g = (total + kStreamBlock * 16 - 1) / (kStreamBlock * 16);
+    if (g > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (g == 0) return hipSuccess;
+    return launch(k_param_distance, dim3((uint32_t)g), dim3(kStreamBlock), s, timing, param, peer, total, table,
+                  (int)count, acc);
+}
+
+hipError_t launch_param_distance_finish(double *acc, const ParamEntry *table, int64_t count,
+                                        dpwa_param_distance_head *out, const dpwa_coef *coef, hipStream_t s,
+                                        const LaunchTiming *timing)
+{
+    if (count < 1 || count > 0x7fffffffLL || !table || !acc || !out) return hipErrorInvalidValue;
+    return launch(k_param_distance_finish, dim3((uint32_t)count), dim3(kParamFinishBlock), s, timing, acc, table, out, coef,
+                  count);
 }
 
 // Some buffer is read by two entries (as parameters or as the peer snapshot).

@@ -91,6 +91,30 @@ hipError_t launch_distance_mixed(const dpwa_layout &layout, const void *param, c
 hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
                                   const LaunchTiming *timing = nullptr);
 
+// The distance to the peer for every parameter tensor (dpwa_param_range, include/dpwa_hip.h;
+// kernels.hip "distance to the peer, per tensor").  The device table has one ParamEntry per
+// tensor, sorted by `begin`; tensor t adds into rows [first_row, first_row + rows) of `acc`
+// (DPWA_DISTANCE_ACC_STRIDE bytes each, zero before the first use and after every finish),
+// rows = min(the 1-KiB spans of the payload it touches, kParamDistRows).
+//   param_distance         the pass over `total` payload bytes of (param, peer), both 16-B aligned
+//   param_distance_finish  one workgroup per tensor: the pairs behind *out, its clock and count,
+//                          written when the round averaged (`coef` null, or its status OK)
+constexpr int kParamDistRows = 1024;
+constexpr int kParamDistEntryBytes = 32;
+struct ParamEntry {
+    int64_t begin, end;   // payload bytes [begin, end); begin a multiple of 256
+    int32_t dtype;
+    int32_t first_row;
+    int32_t rows;         // 0: an empty tensor
+    int32_t reserved;
+};
+static_assert(sizeof(ParamEntry) == kParamDistEntryBytes, "table entry size");
+hipError_t launch_param_distance(const void *param, const void *peer, int64_t total, const ParamEntry *table,
+                                 int64_t count, double *acc, hipStream_t s, const LaunchTiming *timing = nullptr);
+hipError_t launch_param_distance_finish(double *acc, const ParamEntry *table, int64_t count,
+                                        dpwa_param_distance_head *out, const dpwa_coef *coef, hipStream_t s,
+                                        const LaunchTiming *timing = nullptr);
+
 // Several fused averages (co-resident learners) in one dispatch: entry i's workgroups follow
 // entry i-1's.  Every pointer 16-B aligned; `dual` = every entry writes through (snap non-null).
 constexpr int kMaxAvgBatch = 8;

@@ -532,6 +532,13 @@ struct dpwa_learner {
     // allocated when first switched on, kept until destroy
     bool track = false;
     DevBuf dist_mem;
+    // the per-parameter distance (dpwa_learner_set_param_distance): table, workspace and record in one
+    // allocation made when it is switched on; the pass runs on every pd_every-th round that launches
+    // an average (pd_rounds counts them), and pd_now says that this round's finishing step is due
+    bool ptrack = false, pd_now = false;
+    int pd_every = 1;
+    int64_t pd_rounds = 0, pd_measured = 0, pd_count = 0, pd_workspace_off = 0, pd_record_off = 0;
+    DevBuf pd_mem;
     HostWord<int32_t> status;           // pinned mirror of coef.status for non-blocking polls
 };
 
@@ -542,6 +549,18 @@ static char *slot_payload(const dpwa_learner *l, int k)
 
 static double *dist_acc(const dpwa_learner *l) { return (double *)l->dist_mem.ptr(); }
 static dpwa_distance *dist_record(const dpwa_learner *l) { return (dpwa_distance *)(l->dist_mem.ptr() + kDistanceWorkspaceBytes); }
+
+static const ParamEntry *pd_table(const dpwa_learner *l) { return (const ParamEntry *)l->pd_mem.ptr(); }
+static double *pd_acc(const dpwa_learner *l) { return (double *)(l->pd_mem.ptr() + l->pd_workspace_off); }
+static dpwa_param_distance_head *pd_record(const dpwa_learner *l)
+{
+    return (dpwa_param_distance_head *)(l->pd_mem.ptr() + l->pd_record_off);
+}
+// The bytes of the learner's payload.
+static int64_t payload_bytes(const dpwa_learner *l)
+{
+    return l->dtype == DPWA_MIXED ? l->n : l->n * (int64_t)dtype_size(l->dtype);
+}
 
 static int64_t now_ns()
 {
@@ -784,6 +803,155 @@ int dpwa_distance_finish(void *workspace, dpwa_distance *out_dev, const dpwa_coe
         return set_error(DPWA_ERR_ARG, "dpwa_distance_finish: bad arguments (NULL or misaligned pointer, n < 0)");
     HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, (hipStream_t)stream,
                                    CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
+// ---------------------------------------------------------------- per-parameter distance
+static_assert(sizeof(dpwa_param_range) == 24 && sizeof(dpwa_param_pair) == 16 && sizeof(dpwa_param_distance_head) == 16,
+              "per-parameter distance records");
+
+// The rules of a list of dpwa_param_range (include/dpwa_hip.h).  `payload`: also the rules that
+// need one -- `dtype` and `n` of a single-dtype payload, or DPWA_MIXED with `layout`.  Returns
+// DPWA_OK or DPWA_ERR_ARG with the rule broken.  Host only, no HIP call.
+static int param_ranges_problem(const char *fn, const dpwa_param_range *ranges, int64_t count, bool payload,
+                                int32_t dtype, int64_t n, const dpwa_layout *layout)
+{
+    if (count < 0 || (count > 0 && !ranges)) return set_error(DPWA_ERR_ARG, "%s: NULL ranges or count < 0", fn);
+    if (count > 0x7fffffffLL / kParamDistRows)
+        return set_error(DPWA_ERR_ARG, "%s: more than %lld ranges", fn, 0x7fffffffLL / kParamDistRows);
+    if (payload) {
+        if (dtype == DPWA_MIXED) {
+            if (!layout) return set_error(DPWA_ERR_ARG, "%s: a DPWA_MIXED payload needs its layout", fn);
+            if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "%s: %s", fn, why);
+        } else if (dtype_size(dtype) == 0 || dtype == DPWA_F64 || n < 0) {
+            return set_error(DPWA_ERR_ARG, "%s: unknown dtype %d or n < 0", fn, dtype);
+        }
+    }
+    int64_t prev_end = 0;
+    for (int64_t t = 0; t < count; ++t) {
+        const dpwa_param_range &r = ranges[t];
+        const long long i = (long long)t, off = (long long)r.byte_offset, len = (long long)r.byte_length;
+        if (r.dtype != DPWA_F32 && r.dtype != DPWA_BF16 && r.dtype != DPWA_F16)
+            return set_error(DPWA_ERR_ARG, "%s: range %lld: dtype %d is not DPWA_F32, DPWA_BF16 or DPWA_F16", fn, i, r.dtype);
+        if (r.reserved != 0) return set_error(DPWA_ERR_ARG, "%s: range %lld: reserved must be 0", fn, i);
+        if (r.byte_offset < 0 || r.byte_offset % DPWA_PARAM_ALIGN)
+            return set_error(DPWA_ERR_ARG, "%s: range %lld: byte_offset %lld is not a non-negative multiple of %d", fn, i,
+                             off, DPWA_PARAM_ALIGN);
+        if (r.byte_length < 0 || r.byte_length % (int64_t)dtype_size(r.dtype))
+            return set_error(DPWA_ERR_ARG, "%s: range %lld: byte_length %lld is not a non-negative multiple of the "
+                                           "element size %d", fn, i, len, (int)dtype_size(r.dtype));
+        if (r.byte_length > INT64_MAX - r.byte_offset)
+            return set_error(DPWA_ERR_ARG, "%s: range %lld: byte_offset + byte_length overflows", fn, i);
+        if (r.byte_offset < prev_end)
+            return set_error(DPWA_ERR_ARG, "%s: range %lld: ranges must be ascending and non-overlapping (it begins at "
+                                           "%lld, the one before ends at %lld)", fn, i, off, (long long)prev_end);
+        prev_end = r.byte_offset + r.byte_length;
+        if (!payload) continue;
+        if (dtype != DPWA_MIXED) {
+            if (r.dtype != dtype)
+                return set_error(DPWA_ERR_ARG, "%s: range %lld: dtype %d in a payload of dtype %d", fn, i, r.dtype, dtype);
+            if (prev_end > n * (int64_t)dtype_size(dtype))
+                return set_error(DPWA_ERR_ARG, "%s: range %lld: it ends at byte %lld, outside the payload of %lld bytes",
+                                 fn, i, (long long)prev_end, (long long)(n * (int64_t)dtype_size(dtype)));
+            continue;
+        }
+        bool inside = false;
+        for (int k = 0; k < layout->count; ++k) {
+            const dpwa_segment &g = layout->seg[k];
+            if (g.dtype == r.dtype && r.byte_offset >= g.byte_offset && prev_end <= g.byte_offset + g.byte_length)
+                inside = true;
+        }
+        if (!inside)
+            return set_error(DPWA_ERR_ARG, "%s: range %lld: bytes [%lld, %lld) do not lie wholly inside the segment of "
+                                           "dtype %d", fn, i, off, (long long)prev_end, r.dtype);
+    }
+    return DPWA_OK;
+}
+
+// The device table of valid ranges, and the accumulator rows they need in all.
+static int64_t param_table(const dpwa_param_range *ranges, int64_t count, std::vector<ParamEntry> *out)
+{
+    constexpr int64_t span = 1024;   // the pass's one-wave span
+    int64_t rows = 0;
+    if (out) out->assign((size_t)count, ParamEntry{});
+    for (int64_t t = 0; t < count; ++t) {
+        const int64_t begin = ranges[t].byte_offset, end = begin + ranges[t].byte_length;
+        const int64_t spans = end > begin ? (end + span - 1) / span - begin / span : 0;
+        const int64_t r = std::min<int64_t>(spans, kParamDistRows);
+        if (out) (*out)[(size_t)t] = ParamEntry{begin, end, ranges[t].dtype, (int32_t)rows, (int32_t)r, 0};
+        rows += r;
+    }
+    return rows;
+}
+
+static void param_sizes(const dpwa_param_range *ranges, int64_t count, dpwa_param_sizes &z)
+{
+    z.table_bytes = std::max<int64_t>(count, 1) * (int64_t)sizeof(ParamEntry);
+    z.workspace_bytes = std::max<int64_t>(param_table(ranges, count, nullptr), 1) * DPWA_DISTANCE_ACC_STRIDE;
+    z.record_bytes = (int64_t)sizeof(dpwa_param_distance_head) + count * (int64_t)sizeof(dpwa_param_pair);
+    z.max_rows = kParamDistRows;
+    z.reserved = 0;
+}
+
+int dpwa_param_ranges_check(const dpwa_param_range *ranges, int64_t count, int32_t dtype, int64_t n,
+                            const dpwa_layout *layout)
+{
+    return param_ranges_problem("dpwa_param_ranges_check", ranges, count, true, dtype, n, layout);
+}
+
+int dpwa_param_distance_sizes(const dpwa_param_range *ranges, int64_t count, dpwa_param_sizes *sizes)
+{
+    if (!sizes) return set_error(DPWA_ERR_ARG, "dpwa_param_distance_sizes: NULL argument");
+    if (int rc = param_ranges_problem("dpwa_param_distance_sizes", ranges, count, false, 0, 0, nullptr)) return rc;
+    param_sizes(ranges, count, *sizes);
+    return DPWA_OK;
+}
+
+int dpwa_param_distance_table(const dpwa_param_range *ranges, int64_t count, void *table_dev)
+{
+    if (count < 1 || !table_dev || ((uintptr_t)table_dev & 15))
+        return set_error(DPWA_ERR_ARG, "dpwa_param_distance_table: count < 1, or a NULL or misaligned table");
+    if (int rc = param_ranges_problem("dpwa_param_distance_table", ranges, count, false, 0, 0, nullptr)) return rc;
+    std::vector<ParamEntry> table;
+    param_table(ranges, count, &table);
+    HIP_TRY(hipMemcpy(table_dev, table.data(), table.size() * sizeof(ParamEntry), hipMemcpyHostToDevice));
+    return DPWA_OK;
+}
+
+static bool param_buffers_ok(const void *table_dev, int64_t count, const void *workspace, const void *out_dev)
+{
+    return count >= 1 && table_dev && workspace && out_dev &&
+           ((((uintptr_t)table_dev | (uintptr_t)workspace) & 15) == 0) && ((uintptr_t)out_dev & 7) == 0;
+}
+
+int dpwa_measure_param_distance(const void *table_dev, int64_t count, const void *param, const void *peer_payload,
+                                int64_t payload_bytes, void *workspace, dpwa_param_distance_head *out_dev,
+                                dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (!param_buffers_ok(table_dev, count, workspace, out_dev) || payload_bytes < 0 || (!start_event) != (!stop_event) ||
+        (payload_bytes > 0 && (!param || !peer_payload)))
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_param_distance: bad arguments (NULL or misaligned pointer, "
+                                       "count < 1, payload_bytes < 0)");
+    if (((uintptr_t)param | (uintptr_t)peer_payload) & 15)
+        return set_error(DPWA_ERR_ARG, "dpwa_measure_param_distance: the parameters and the peer payload are 16-byte "
+                                       "aligned");
+    const CallerTiming timing(start_event, stop_event);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_param_distance(param, peer_payload, payload_bytes, (const ParamEntry *)table_dev, count,
+                                  (double *)workspace, s, timing));
+    HIP_TRY(launch_param_distance_finish((double *)workspace, (const ParamEntry *)table_dev, count, out_dev, nullptr, s));
+    return DPWA_OK;
+}
+
+int dpwa_param_distance_finish(const void *table_dev, int64_t count, void *workspace,
+                               dpwa_param_distance_head *out_dev, const dpwa_coef *coef_dev, dpwa_stream_t stream,
+                               void *start_event, void *stop_event)
+{
+    if (!param_buffers_ok(table_dev, count, workspace, out_dev) || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_param_distance_finish: bad arguments (NULL or misaligned pointer, "
+                                       "count < 1)");
+    HIP_TRY(launch_param_distance_finish((double *)workspace, (const ParamEntry *)table_dev, count, out_dev, coef_dev,
+                                         (hipStream_t)stream, CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -1394,6 +1562,10 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
 static int relay_materialize(dpwa_learner *l);
 static int distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s);
 static int distance_after(dpwa_learner *l, hipStream_t s);
+static int param_distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s);
+static int param_distance_after(dpwa_learner *l, hipStream_t s);
+static const char *const kParamUnaligned = "the per-parameter distance (dpwa_learner_set_param_distance) has no form "
+                                           "for parameters that are not 16-byte aligned";
 
 static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev)
 {
@@ -1456,6 +1628,8 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     hipStream_t s = (hipStream_t)stream;
     if (l->dtype == DPWA_MIXED && ((uintptr_t)flat & 15))   // (its layout is known: the factor was computed)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
+    if (l->ptrack && ((uintptr_t)flat & 15)) return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: %s", kParamUnaligned);
+    if (int rc = param_distance_before(l, flat, l->src + kPayloadOff, s)) return rc;
     if (l->track)
         if (int rc = distance_before(l, flat, l->src + kPayloadOff, s)) return rc;
     if (l->dtype == DPWA_MIXED) {
@@ -1465,6 +1639,7 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     }
     if (l->track)
         if (int rc = distance_after(l, s)) return rc;
+    if (int rc = param_distance_after(l, s)) return rc;
     HIP_TRY(note_consumed(l, s));
     l->written_through.clear();
     finish_fetch(l);
@@ -1493,6 +1668,7 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
     if (int rc = need_layout(l, "dpwa_learner_average")) return rc;
     if (l->dtype == DPWA_MIXED && ((uintptr_t)flat & 15))
         return set_error(DPWA_ERR_ARG, "dpwa_learner_average: a segmented payload is 16-byte aligned");
+    if (l->ptrack && ((uintptr_t)flat & 15)) return set_error(DPWA_ERR_ARG, "dpwa_learner_average: %s", kParamUnaligned);
     p = AvgPlan();
     p.mixed = l->dtype == DPWA_MIXED;
     if (l->resident) {   // read where the parameters are (the published slot), write the next slot
@@ -1578,7 +1754,8 @@ static int distance_after(dpwa_learner *l, hipStream_t s)
     return DPWA_OK;
 }
 
-static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
+// The averaging launch of plan p, and the whole-model distance around or inside it.
+static int average_launch_tracked(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
     if (l->track) {   // never p.relay: relay_phase2 refuses to defer for a tracking learner
         const bool fused = !p.mixed && ((((uintptr_t)p.flat | (uintptr_t)p.peer | (uintptr_t)p.snap) & 15) == 0);
@@ -1599,6 +1776,34 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
         HIP_TRY(launch_average(l->dtype, p.flat, p.peer, l->n, p.fa, p.snap, s, timing, p.oop));
     }
     return l->track ? distance_after(l, s) : DPWA_OK;
+}
+
+// The per-parameter distance around an average, whatever its form (its pass before, since the
+// in-place forms overwrite what it reads; its finishing step behind the coefficients).  Off, or a
+// round it skips: nothing but the average's own launches.
+static int param_distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s)
+{
+    if (!l->ptrack) return DPWA_OK;   // never with a fused relay second phase: relay_phase2 refuses to defer
+    l->pd_now = ++l->pd_rounds % l->pd_every == 0;
+    if (!l->pd_now) return DPWA_OK;
+    HIP_TRY(launch_param_distance(flat, peer, payload_bytes(l), pd_table(l), l->pd_count, pd_acc(l), s));
+    ++l->pd_measured;
+    return DPWA_OK;
+}
+
+static int param_distance_after(dpwa_learner *l, hipStream_t s)
+{
+    if (!l->ptrack || !l->pd_now) return DPWA_OK;
+    l->pd_now = false;
+    HIP_TRY(launch_param_distance_finish(pd_acc(l), pd_table(l), l->pd_count, pd_record(l), &l->ctl->coef, s));
+    return DPWA_OK;
+}
+
+static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
+{
+    if (int rc = param_distance_before(l, p.flat, p.peer, s)) return rc;
+    if (int rc = average_launch_tracked(l, p, s)) return rc;
+    return param_distance_after(l, s);
 }
 
 static int average_impl(dpwa_learner *l, void *flat, double loss, const double *loss_dev, hipStream_t s,
@@ -1639,7 +1844,9 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
         const LaunchTiming *timing = take_timing(la);
         dpwa_learner *tracking[kMaxAvgBatch];   // the dispatch stays as it is: their passes go around it
         int tracking_entry[kMaxAvgBatch], n_tracking = 0;
+        dpwa_learner *member[kMaxAvgBatch];
         auto add = [&](dpwa_learner *l, const AvgPlan &p) {
+            member[b.count] = l;
             if (l->track) {
                 tracking[n_tracking] = l;
                 tracking_entry[n_tracking++] = b.count;
@@ -1661,6 +1868,8 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
             add(ls[ic], plans[ic]);
             done[c] = 1;
         }
+        for (int m = 0; m < b.count; ++m)
+            if (int rc = param_distance_before(member[m], b.e[m].param, (const char *)b.e[m].peer, s)) return rc;
         for (int t = 0; t < n_tracking; ++t) {
             const AvgEntry &e = b.e[tracking_entry[t]];
             if (int rc = distance_before(tracking[t], e.param, (const char *)e.peer, s)) return rc;
@@ -1668,6 +1877,8 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
         HIP_TRY(launch_average_batch(la->dtype, pa.write_through, b, s, timing, pa.oop));
         for (int t = 0; t < n_tracking; ++t)
             if (int rc = distance_after(tracking[t], s)) return rc;
+        for (int m = 0; m < b.count; ++m)
+            if (int rc = param_distance_after(member[m], s)) return rc;
     }
     return DPWA_OK;
 }
@@ -1799,6 +2010,63 @@ int dpwa_learner_distance(dpwa_learner *l, const dpwa_distance **dev)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_distance: distance tracking was never switched on "
                                          "(dpwa_learner_set_distance)");
     *dev = dist_record(l);
+    return DPWA_OK;
+}
+
+int dpwa_learner_set_param_distance(dpwa_learner *l, const dpwa_param_range *ranges, int64_t count, int every)
+{
+    const char *fn = "dpwa_learner_set_param_distance";
+    if (!l) return set_error(DPWA_ERR_ARG, "%s: NULL learner", fn);
+    if (count == 0) {
+        l->ptrack = false;
+        return DPWA_OK;
+    }
+    if (every < 1) return set_error(DPWA_ERR_ARG, "%s: every = %d, it must be >= 1", fn, every);
+    if (int rc = need_layout(l, fn)) return rc;
+    if (int rc = param_ranges_problem(fn, ranges, count, true, l->dtype, l->n, &l->layout)) return rc;
+    if (l->relay_deferred)
+        return set_error(DPWA_ERR_STATE, "%s: a fused relay second phase is pending (dpwa_learner_relay_phase2 with "
+                                         "fuse != 0), which reads no contiguous peer snapshot to measure against", fn);
+    DeviceGuard dg(l->device);
+    dpwa_param_sizes z;
+    param_sizes(ranges, count, z);
+    std::vector<ParamEntry> table;
+    param_table(ranges, count, &table);
+    const int64_t workspace_off = (z.table_bytes + 127) / 128 * 128, record_off = workspace_off + z.workspace_bytes;
+    const size_t bytes = (size_t)(record_off + z.record_bytes);
+    DevBuf mem;   // once, here: never inside a round
+    HIP_TRY(mem.alloc(bytes));
+    hipError_t e = hipMemset(mem.ptr(), 0, bytes);
+    if (e == hipSuccess) e = hipMemcpy(mem.ptr(), table.data(), table.size() * sizeof(ParamEntry), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // (and nothing in flight reads the buffers replaced below)
+    if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+    l->pd_mem = std::move(mem);
+    l->pd_count = count;
+    l->pd_workspace_off = workspace_off;
+    l->pd_record_off = record_off;
+    l->pd_every = every;
+    l->pd_rounds = l->pd_measured = 0;
+    l->pd_now = false;
+    l->ptrack = true;
+    return DPWA_OK;
+}
+
+int dpwa_learner_param_distance(dpwa_learner *l, const dpwa_param_distance_head **dev, int64_t *count)
+{
+    if (!l || !dev || !count) return set_error(DPWA_ERR_ARG, "dpwa_learner_param_distance: NULL argument");
+    if (!l->pd_mem.ptr())
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_param_distance: the per-parameter distance was never switched on "
+                                         "(dpwa_learner_set_param_distance)");
+    *dev = pd_record(l);
+    *count = l->pd_count;
+    return DPWA_OK;
+}
+
+int dpwa_learner_param_distance_rounds(dpwa_learner *l, int64_t *averaged, int64_t *measured)
+{
+    if (!l || !averaged || !measured) return set_error(DPWA_ERR_ARG, "dpwa_learner_param_distance_rounds: NULL argument");
+    *averaged = l->pd_rounds;
+    *measured = l->pd_measured;
     return DPWA_OK;
 }
 
@@ -2131,6 +2399,10 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
         return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
                                          "snapshot, so a learner that tracks the distance (dpwa_learner_set_distance) "
                                          "cannot use it; gather (fuse = 0)");
+    if (fuse && l->ptrack)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
+                                         "snapshot, so a learner that measures the per-parameter distance "
+                                         "(dpwa_learner_set_param_distance) cannot use it; gather (fuse = 0)");
     RelayArgs a;
     int rc = relay_args(l, picks_dev, version, a);
     if (rc) return rc;

@@ -212,6 +212,8 @@ class PeerDistance:
         self._learner = learner
         self._t = None
         self._raw = None
+        # track_distance="per_parameter": the ParameterDistances, once a measured round has averaged
+        self.parameters = None
 
     def _ptr(self):
         learner = self._learner
@@ -263,6 +265,87 @@ class PeerDistance:
         return "PeerDistance(dist2=%r, norm2=%r, clock=%r, n=%d)" % (rec.dist2, rec.norm2, rec.clock, rec.n)
 
 
+class ParameterDistances:
+    """The distance to the peer for every parameter tensor (``track_distance="per_parameter"``;
+    dpwa_param_range in include/dpwa_hip.h): :class:`PeerDistance`'s two sums over each tensor's own
+    elements only -- the bytes between tensors are read into no sum -- from the newest measured
+    round that averaged (every ``distance_every``-th).
+
+    ``last_distance.parameters`` is None until a round of the learner has launched the measuring pass
+    (see ``written`` for the one case in which that round wrote nothing).
+    ``tensor()`` is a float64 device view ``[T, 2]`` of (dist2, norm2), one row per tensor in
+    ascending byte offset (``names`` in that order; ``named_parameters()`` order for a model of one
+    dtype) -- no copy, no host sync.  ``clock``, ``read()`` -> ``{name: (dist2, norm2)}`` and
+    ``relative()`` -> ``{name: sqrt(dist2 / norm2)}`` (0/0 is 0, x/0 is inf, as
+    ``PeerDistance.relative``) are Python values, so each of them synchronises with the stream that
+    averaged.  Like the whole-model sums these are reproducible to (n_t - 1) * 2**-53 relative, not
+    bit-exact from run to run."""
+
+    def __init__(self, learner, names, where):
+        self._learner = learner
+        self._names = list(names)            # in the caller's order
+        self._where = list(where)            # the record's row of each of them
+        self.names = [None] * len(names)     # in the record's order
+        for name, k in zip(self._names, self._where):
+            self.names[k] = name
+        self._raw = None
+
+    def _record(self):
+        if self._learner._h is None:
+            raise RuntimeError("the connection this distance belongs to is closed")
+        if self._raw is None:
+            from .devview import device_tensor
+            p, count = ctypes.c_void_p(), ctypes.c_int64()
+            _lib.call("dpwa_learner_param_distance", self._learner.handle, ctypes.byref(p), ctypes.byref(count))
+            assert count.value == len(self._names)
+            nbytes = _lib.PARAM_HEAD_BYTES + 16 * count.value
+            self._raw = device_tensor(p.value, nbytes, torch.uint8, self._learner.device).view(torch.float64)
+        return self._raw
+
+    def tensor(self):
+        return self._record()[2:].view(-1, 2)
+
+    def measured_rounds(self):
+        """How many rounds of the learner launched the measuring pass so far (the learner's own host
+        counter: no device read, no sync)."""
+        if self._learner._h is None:
+            raise RuntimeError("the connection this distance belongs to is closed")
+        averaged, measured = ctypes.c_int64(), ctypes.c_int64()
+        _lib.call("dpwa_learner_param_distance_rounds", self._learner.handle, ctypes.byref(averaged),
+                  ctypes.byref(measured))
+        return measured.value
+
+    @property
+    def written(self):
+        """Whether a round has written the record (synchronises).  ``last_distance.parameters`` appears
+        with the first round that launched the measuring pass, which the host knows without waiting;
+        if that round's interpolation divided by zero it averaged nothing and wrote nothing, and until
+        a later measured round averages the record holds zeros, clock 0, and this is False."""
+        return int(self._record()[1:2].view(torch.int64).item()) != 0
+
+    @property
+    def clock(self):
+        return float(self._record()[0].item())
+
+    def read(self):
+        """``{name: (dist2, norm2)}`` in the order the ranges were given; synchronises."""
+        rows = self.tensor().cpu().tolist()
+        return {name: (rows[k][0], rows[k][1]) for name, k in zip(self._names, self._where)}
+
+    def relative(self):
+        """``{name: sqrt(dist2 / norm2)}``; synchronises."""
+        out = {}
+        for name, (d2, n2) in self.read().items():
+            if n2 == 0.0:
+                out[name] = 0.0 if d2 == 0.0 else float("inf")
+            else:
+                out[name] = (d2 / n2) ** 0.5
+        return out
+
+    def __repr__(self):
+        return "ParameterDistances(%d tensors, clock=%r)" % (len(self._names), self.clock)
+
+
 TRACKED_RELAY_AVG = ("pull='relay-avg' is not available with track_distance=True: the relay's fused second phase "
                      "reads the peer's snapshot stripe by stripe and leaves no contiguous snapshot to measure the "
                      "distance against; use 'relay' (the same relay, gathered first), 'kernel' or 'copy', or leave "
@@ -270,7 +353,8 @@ TRACKED_RELAY_AVG = ("pull='relay-avg' is not available with track_distance=True
 
 
 class DpwaConnection:
-    def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None, track_distance=False):
+    def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None, track_distance=False,
+                 parameter_ranges=None, distance_every=1):
         """layout (extension): ``FlatParameters.layout`` when the flat buffer given to update_send
         is the segmented ``torch.uint8`` buffer of a model that mixes dtypes (dpwa_amd/flat.py);
         every peer must hold the same layout.
@@ -282,9 +366,27 @@ class DpwaConnection:
         buffer, ``update_wait()`` + ``average()`` and ``update_wait_average_many`` run a separate
         pass before the average and pay 2*n*s more bytes read.  Not available with
         ``pull='relay-avg'``.  It is a constructor argument only (the YAML schema is the
-        reference's)."""
+        reference's).
+
+        track_distance="per_parameter" (with ``parameter_ranges=FlatParameters.parameter_ranges()``)
+        measures that and also the same two sums for every parameter tensor
+        (``last_distance.parameters``, :class:`ParameterDistances`): on every ``distance_every``-th
+        round that averages, a separate pass before the average reads both operands once more
+        (2*n*s bytes, whatever the form), which is what ``distance_every`` is for.  It needs a
+        16-byte aligned parameter buffer."""
         self.name = name
         self._layout = tuple(layout) if layout is not None else None
+        if isinstance(track_distance, str) and track_distance != "per_parameter":
+            raise ValueError("track_distance must be False, True or 'per_parameter', got %r" % track_distance)
+        self._per_parameter = track_distance == "per_parameter"
+        self._param_ranges = list(parameter_ranges) if parameter_ranges is not None else None
+        self._distance_every = int(distance_every)
+        self._param_distance = None       # the learner's ParameterDistances, once bound
+        if self._per_parameter and not self._param_ranges:
+            raise ValueError("track_distance='per_parameter' needs parameter_ranges "
+                             "(FlatParameters.parameter_ranges())")
+        if self._per_parameter and self._distance_every < 1:
+            raise ValueError("distance_every must be >= 1, got %r" % distance_every)
         self._track_distance = bool(track_distance)
         self._last_distance = None
         if self._layout is not None and pull is not None and pull.partition(":")[0] == "relay-avg":
@@ -459,7 +561,7 @@ class DpwaConnection:
         self.fetching = False
         self._sent = None
         if self._out.value >= 0:
-            self._last_distance = self._distance
+            self._averaged()
         return self._result()
 
     # ---------------------------------------------------------------- extensions
@@ -551,7 +653,7 @@ class DpwaConnection:
             for j, i in enumerate(bound):
                 if peers[j] >= 0:
                     c = conns[i]
-                    c._last_distance = c._distance
+                    c._averaged()
                     out[i] = (PeerSnapshot(c, peers[j], c._learner.version), DeviceFactor(c._learner))
         return out
 
@@ -569,7 +671,14 @@ class DpwaConnection:
         rc = self._f_lerp(self._node, learner._ptr(parameters), s)
         if rc:
             self._fail("dpwa_node_lerp", rc)
+        self._averaged()
+
+    def _averaged(self):
+        """A round of this connection launched an average: its records are the newest ones."""
         self._last_distance = self._distance
+        if self._param_distance is not None and self._distance.parameters is None \
+                and self._param_distance.measured_rounds() > 0:
+            self._distance.parameters = self._param_distance
 
     @property
     def last_distance(self):
@@ -703,6 +812,12 @@ class DpwaConnection:
                 raise ValueError(TRACKED_RELAY_AVG)
             _lib.call("dpwa_learner_set_distance", self._learner.handle, 1)
             self._distance = PeerDistance(self._learner)
+        if self._per_parameter:                       # table, workspace and record: allocated here as well
+            from .flat import c_param_ranges
+            arr, where = c_param_ranges(self._param_ranges)
+            _lib.call("dpwa_learner_set_param_distance", self._learner.handle, arr, len(self._param_ranges),
+                      self._distance_every)
+            self._param_distance = ParameterDistances(self._learner, [r[0] for r in self._param_ranges], where)
         if self._pull.partition(":")[0] in RELAY_PULLS:
             if not hasattr(self._group, "relay_blocks"):
                 raise ValueError("the relay pull needs a DistGroup (one learner per rank)")

@@ -50,6 +50,24 @@ def c_layout(layout):
     return out
 
 
+def c_param_ranges(ranges):
+    """`ranges` -- (name, torch dtype, byte offset, byte length) tuples, ``parameter_ranges()`` -- as the
+    C ABI's dpwa_param_range array, sorted by byte offset (a segmented buffer keeps
+    ``named_parameters()`` order inside a segment only), and the position of each given range in that
+    array."""
+    codes = dict(SEGMENT_DTYPES)
+    order = sorted(range(len(ranges)), key=lambda i: (ranges[i][2], ranges[i][3], i))
+    arr = (_lib.ParamRange * max(1, len(ranges)))()
+    where = [0] * len(ranges)
+    for k, i in enumerate(order):
+        _, dtype, off, length = ranges[i]
+        if dtype not in codes:
+            raise KeyError("dpwa averages float32, bfloat16 or float16 parameters, got %s" % dtype)
+        arr[k] = _lib.ParamRange(int(off), int(length), codes[dtype], 0)
+        where[i] = k
+    return arr, where
+
+
 class FlatParameters:
     def __init__(self, named_parameters, device=None):
         """device: where the flat buffer lives (a config's per-node `gpu:` key); parameters on
@@ -169,6 +187,17 @@ class FlatParameters:
                     self._ptrs[i] = p.data_ptr()
                     moved += 1
         return moved
+
+    def parameter_ranges(self):
+        """``[(name, torch dtype, byte offset, byte length)]`` in ``named_parameters()`` order: where
+        each parameter's elements lie in the buffer, for single-dtype and segmented buffers alike
+        (what ``track_distance="per_parameter"`` measures over; ``c_param_ranges`` makes the C ABI's
+        dpwa_param_range list of it)."""
+        if self.layout is not None:
+            return [(name, d, o, b) for name, d, o, b in zip(self.names, self._pdtypes, self.offsets, self._pbytes)]
+        esize = self.buffer.element_size()
+        return [(name, self.dtype, o * esize, p.numel() * esize)
+                for name, p, o in zip(self.names, self.params, self.offsets)]
 
     def view(self, name):
         return self._view(self.buffer, self.names.index(name))

@@ -75,6 +75,10 @@ def main(argv=None):
                          "update_wait, then the training step -- nothing may write the parameters between "
                          "update_send and update_wait in this form -- instead of the reference's update_send, "
                          "step, update_wait")
+    ap.add_argument("--top-distances", action="store_true",
+                    help="measure the distance to the peer for every parameter tensor on every 100th round that "
+                         "averages (track_distance='per_parameter', distance_every=100) and print the three "
+                         "tensors with the largest relative distance every 100 steps")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -111,7 +115,13 @@ def main(argv=None):
         losses = [torch.tensor(2.3, device=dev) for _ in mine]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for step in range(1, steps + 1):
+            if gossip and args.top_distances and step % 100 == 0 and rank == 0:
+                d = adapters[0].last_distance
+                if d is not None and d.parameters is not None:     # (this read waits for the device)
+                    top = sorted(d.parameters.relative().items(), key=lambda kv: -kv[1])[:3]
+                    print("step %d, clock %g: largest relative distance to the peer: %s"
+                          % (step, d.parameters.clock, ", ".join("%s %.3g" % kv for kv in top)), file=sys.stderr)
             if gossip:
                 for i, a in enumerate(adapters):
                     a.update_send(losses[i])       # a device tensor: no host sync
@@ -133,6 +143,8 @@ def main(argv=None):
     group = {"group": args.gossip} if world > 1 else {}
     if world > 1 and args.pull:
         group["pull"] = args.pull
+    if args.top_distances:
+        group.update(track_distance="per_parameter", distance_every=100)
     adapters = [DpwaPyTorchAdapter(nets[i], names[g], cfg, seed=100 + g, resident=args.resident, **group)
                 for i, g in enumerate(mine)]
     run(args.warmup, False)

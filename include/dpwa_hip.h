@@ -33,7 +33,11 @@ extern "C" {
  * dpwa_node_set_layout; the IPC handle carries the layout digest in bytes that were zero.
  * Still 11, by additions only: the distance to the peer (dpwa_distance) -- dpwa_distance_workspace,
  * dpwa_measure_distance, dpwa_measure_distance_mixed, dpwa_average_tracked, dpwa_distance_finish,
- * dpwa_learner_set_distance, dpwa_learner_distance. */
+ * dpwa_learner_set_distance, dpwa_learner_distance.
+ * Still 11, by additions only: the distance to the peer for every parameter tensor (dpwa_param_range)
+ * -- dpwa_param_ranges_check, dpwa_param_distance_sizes, dpwa_param_distance_table,
+ * dpwa_measure_param_distance, dpwa_param_distance_finish, dpwa_learner_set_param_distance,
+ * dpwa_learner_param_distance, dpwa_learner_param_distance_rounds. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -241,6 +245,78 @@ int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int6
 int dpwa_distance_finish(void *workspace, dpwa_distance *out_dev, const dpwa_coef *coef_dev, int64_t n,
                          dpwa_stream_t stream, void *start_event, void *stop_event);
 
+/* The per-parameter distance (extension, opt-in): the two sums above for every parameter tensor t of
+ * the model, over that tensor's own elements only -- dist2_t = sum (double(q_i) - double(p_i))^2 and
+ * norm2_t = sum double(p_i)^2 with dpwa_distance's arithmetic.  Where the tensors lie in the payload
+ * is a list of dpwa_param_range:
+ *   - ascending and non-overlapping: byte_offset[t] >= byte_offset[t-1] + byte_length[t-1];
+ *   - byte_offset a multiple of DPWA_PARAM_ALIGN (256); byte_length a multiple of the element size,
+ *     0 allowed (an empty tensor reports (0, 0));
+ *   - dtype DPWA_F32, DPWA_BF16 or DPWA_F16; reserved 0;
+ *   - every range inside the payload -- of a single-dtype payload of n elements, with that dtype; of a
+ *     DPWA_MIXED payload, wholly inside the segment of its dtype.
+ * Bytes of no range (the gaps between tensors, a segment's padding) are NOT read into any sum: unlike
+ * the whole-model record this one does not rely on them being zero, and a NaN there shows in no tensor.
+ * Each dist2_t / norm2_t is reproducible to (n_t - 1) * 2^-53 relative, like the whole-model record.
+ *
+ * The record is a dpwa_param_distance_head followed by `count` dpwa_param_pair, in the ranges' order;
+ * `clock` as dpwa_distance's.  The table (the ranges as the kernels read them) and the workspace are
+ * caller-owned device memory of the sizes dpwa_param_distance_sizes gives, 16-B aligned; the workspace
+ * zero before the first use (every entry below leaves it zero again; one stream at a time).  Tensor t
+ * owns min(the 1-KiB spans of the payload it touches, max_rows) accumulators of DPWA_DISTANCE_ACC_STRIDE
+ * bytes each, and its span s adds into accumulator s modulo that count.
+ *   dpwa_param_ranges_check      the rules above against a payload: (dtype, n) for a single dtype, or
+ *                                DPWA_MIXED with its layout.  Needs no device.
+ *   dpwa_param_distance_sizes    the bytes of table, workspace and record for the ranges (checks the
+ *                                rules that need no payload).  Needs no device.
+ *   dpwa_param_distance_table    writes the table to `table_dev` (a blocking copy).
+ *   dpwa_measure_param_distance  the pass over `payload_bytes` of `param` and `peer_payload` (16-B aligned,
+ *                                any form of payload the table was made for), then the finishing step:
+ *                                writes the whole record, clock 0.  The events time the pass.  The table is
+ *                                opaque device memory and is not checked against payload_bytes here: make
+ *                                it from ranges that dpwa_param_ranges_check accepts for this payload.
+ *                                Nothing is read beyond payload_bytes whatever the table says; elements of
+ *                                a range that ends beyond it count as zeros.
+ *   dpwa_param_distance_finish   the finishing step alone: one workgroup per tensor sums its accumulators
+ *                                in a fixed order and zeroes them; the record is written only when
+ *                                coef_dev is NULL or its status is DPWA_STATUS_OK (clock: its new_clock).
+ *                                The events time it.
+ * DPWA_ERR_ARG (no device touched) with a message naming the broken rule, for NULL or misaligned
+ * pointers, count < 1 (count < 0 for the check and the sizes), payload_bytes < 0. */
+#define DPWA_PARAM_ALIGN 256
+typedef struct dpwa_param_range {
+    int64_t byte_offset;
+    int64_t byte_length;
+    int32_t dtype;
+    int32_t reserved;
+} dpwa_param_range;
+typedef struct dpwa_param_pair {
+    double dist2;
+    double norm2;
+} dpwa_param_pair;
+typedef struct dpwa_param_distance_head {
+    double clock;
+    int64_t count;
+    /* dpwa_param_pair pair[count] follows */
+} dpwa_param_distance_head;
+typedef struct dpwa_param_sizes {
+    int64_t table_bytes;
+    int64_t workspace_bytes;
+    int64_t record_bytes;
+    int32_t max_rows;   /* accumulators of the largest tensors (the modulus above) */
+    int32_t reserved;
+} dpwa_param_sizes;
+int dpwa_param_ranges_check(const dpwa_param_range *ranges, int64_t count, int32_t dtype, int64_t n,
+                            const dpwa_layout *layout);
+int dpwa_param_distance_sizes(const dpwa_param_range *ranges, int64_t count, dpwa_param_sizes *sizes);
+int dpwa_param_distance_table(const dpwa_param_range *ranges, int64_t count, void *table_dev);
+int dpwa_measure_param_distance(const void *table_dev, int64_t count, const void *param, const void *peer_payload,
+                                int64_t payload_bytes, void *workspace, dpwa_param_distance_head *out_dev,
+                                dpwa_stream_t stream, void *start_event, void *stop_event);
+int dpwa_param_distance_finish(const void *table_dev, int64_t count, void *workspace,
+                               dpwa_param_distance_head *out_dev, const dpwa_coef *coef_dev, dpwa_stream_t stream,
+                               void *start_event, void *stop_event);
+
 /* dpwa_average over several independent (param, peer slot) pairs in ONE dispatch -- the averages
  * of co-resident learners of one round (pytorch.py:66-68 once per learner).  Each descriptor is
  * one dpwa_average call: its own clock_dev (reads [0], writes [1]), coefficient block and loss;
@@ -410,6 +486,29 @@ int dpwa_learner_average_many(dpwa_learner *const *learners, void *const *flats,
  * set_distance(on)); read it in order with the stream that averaged. */
 int dpwa_learner_set_distance(dpwa_learner *l, int on);
 int dpwa_learner_distance(dpwa_learner *l, const dpwa_distance **dev);
+/* The per-parameter distance of a learner (dpwa_param_range above; off by default, and off every launch
+ * is the launch it was).  set_param_distance(ranges, count, every) checks the ranges against the
+ * learner's n / dtype / layout (DPWA_ERR_ARG; a DPWA_MIXED learner needs its layout first:
+ * DPWA_ERR_STATE), allocates the table, the workspace and the record once, here, and from then on the
+ * every-th, 2*every-th, ... round of this learner that launches an average also runs the pass
+ * (dpwa_measure_param_distance's) BEFORE that average on the same stream and the finishing step after
+ * it, whatever the form: average / average_through / resident (it reads the published slot) /
+ * DPWA_MIXED / the split factor -> lerp / an average inside dpwa_learner_average_many.  2*n*s more
+ * bytes read on a measured round; other rounds launch nothing new and leave the record.  The
+ * whole-model record (set_distance) is independent of it.  count = 0 switches it off (ranges may be
+ * NULL); every >= 1.  The same two rules as set_distance hold for the relay's fused second phase.
+ * While it is on, parameters that are not 16-byte aligned are refused by the average (DPWA_ERR_ARG,
+ * nothing queued).  A round that does not average (the ZeroDivision no-op) leaves the record as it
+ * was.  dpwa_learner_param_distance: the record's device address and its tensor count (borrowed, valid
+ * until the next set_param_distance with count > 0 or dpwa_learner_destroy; DPWA_ERR_STATE before the
+ * first). */
+int dpwa_learner_set_param_distance(dpwa_learner *l, const dpwa_param_range *ranges, int64_t count, int every);
+int dpwa_learner_param_distance(dpwa_learner *l, const dpwa_param_distance_head **dev, int64_t *count);
+/* Host counters since the last set_param_distance with count > 0 (no device touched, no sync): the
+ * rounds of this learner that launched an average, and those of them on which the pass and its
+ * finishing step were launched.  A measured round that turned out a ZeroDivision no-op counts here
+ * and writes no record: the record's `count` stays 0 until a round has written it. */
+int dpwa_learner_param_distance_rounds(dpwa_learner *l, int64_t *averaged, int64_t *measured);
 
 /* always != 0: a write-through average never writes the next publish's header ahead; that
  * publish then writes it with the loss given to it (a snapshot served over the wire bridge
