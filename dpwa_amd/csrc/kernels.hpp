@@ -14,6 +14,10 @@ inline size_t dtype_size(int32_t dtype)
 {
     return dtype == DPWA_F32 ? 4 : dtype == DPWA_BF16 || dtype == DPWA_F16 ? 2 : dtype == DPWA_MIXED ? 1 : 0;
 }
+// One of the element types a kernel averages and measures (not DPWA_MIXED, which names a layout of them).
+inline bool is_float_dtype(int32_t dtype) { return dtype == DPWA_F32 || dtype == DPWA_BF16 || dtype == DPWA_F16; }
+// Is every one of the pointers 16-byte aligned (a null one is)?
+template <class... P> inline bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15) == 0; }
 
 // The rules of a dpwa_layout (include/dpwa_hip.h); total_bytes >= 0: it must cover exactly that
 // many.  Returns null when valid, else the rule broken.  Host only, no HIP call.
@@ -23,6 +27,13 @@ inline int64_t layout_bytes(const dpwa_layout &layout)
 {
     const dpwa_segment &last = layout.seg[layout.count - 1];
     return last.byte_offset + last.byte_length;
+}
+// The element slots of a valid layout's segments.
+inline int64_t layout_elements(const dpwa_layout &layout)
+{
+    int64_t n = 0;
+    for (int i = 0; i < layout.count; ++i) n += layout.seg[i].byte_length / (int64_t)dtype_size(layout.seg[i].dtype);
+    return n;
 }
 
 // Inputs/outputs of the device factor computation (dpwa.py:139-155).  clock_in and
@@ -216,5 +227,33 @@ hipError_t launch_release_system(hipStream_t s);
 
 // A system-scope release store of one 64-bit word after the work already on `s`.
 hipError_t launch_store_u64(uint64_t *p, uint64_t v, hipStream_t s);
+
+// What the stateless entry points (learner.cpp, distance.cpp) share; `fn` names the entry in messages.
+// The caller's begin/end events as a launch's timing argument: NULL when none were given.
+struct CallerTiming {
+    LaunchTiming t;
+    CallerTiming(void *start_event, void *stop_event) : t{(hipEvent_t)start_event, (hipEvent_t)stop_event} {}
+    operator const LaunchTiming *() const { return t.start ? &t : nullptr; }
+};
+
+inline int check_method(const dpwa_interp *cfg, const char *fn)
+{
+    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "%s: unknown method %d", fn, cfg->method);
+    return DPWA_OK;
+}
+
+// Factor from the header of `peer_slot`, clock read at clock_dev and written behind it.
+inline FusedArgs stateless_args(const dpwa_interp *cfg, double *clock_dev, const void *peer_slot, double loss,
+                                dpwa_coef *coef_dev)
+{
+    FusedArgs fa{};
+    fa.cfg = *cfg;
+    fa.clock_in = clock_dev;
+    fa.clock_out = clock_dev + 1;
+    fa.hdr = (const dpwa_header *)peer_slot;
+    fa.loss_h = loss;
+    fa.coef_out = coef_dev;
+    return fa;
+}
 
 }  // namespace dpwa

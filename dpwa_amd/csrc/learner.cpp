@@ -27,6 +27,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "measure.hpp"
 #include "order.hpp"
 
 namespace {
@@ -116,14 +117,10 @@ struct DevMem {
     }
 };
 
-// Owners of the plain HIP objects a learner holds, like order.hpp's of the events.
+// Owner of the streams a learner holds, like order.hpp's of the events and the plain buffers (DevBuf).
 struct Stream : Owned<hipStream_t, hipStreamDestroy> {   // non-blocking
     hipError_t create() { return hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
     hipError_t create(int priority) { return hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority); }
-};
-struct DevBuf : Owned<void *, hipFree> {
-    hipError_t alloc(size_t bytes) { return hipMalloc(&h, bytes); }
-    char *ptr() const { return (char *)h; }
 };
 
 // One pinned 32-bit word, zero at first, that the device writes through `dev` and the host polls
@@ -528,17 +525,9 @@ struct dpwa_learner {
     // learners (local) that read our slot k and must be waited for before rewriting it
     std::mutex readers_mu;
     std::vector<dpwa_learner *> readers[2];
-    // distance tracking (dpwa_learner_set_distance): the accumulators and, behind them, the record;
-    // allocated when first switched on, kept until destroy
-    bool track = false;
-    DevBuf dist_mem;
-    // the per-parameter distance (dpwa_learner_set_param_distance): table, workspace and record in one
-    // allocation made when it is switched on; the pass runs on every pd_every-th round that launches
-    // an average (pd_rounds counts them), and pd_now says that this round's finishing step is due
-    bool ptrack = false, pd_now = false;
-    int pd_every = 1;
-    int64_t pd_rounds = 0, pd_measured = 0, pd_count = 0, pd_workspace_off = 0, pd_record_off = 0;
-    DevBuf pd_mem;
+    // the distances to the peer (dpwa_learner_set_distance, dpwa_learner_set_param_distance) and all
+    // that is launched for them around an average (measure.hpp)
+    Measure measure;
     HostWord<int32_t> status;           // pinned mirror of coef.status for non-blocking polls
 };
 
@@ -547,19 +536,10 @@ static char *slot_payload(const dpwa_learner *l, int k)
     return l->slot_mem.ptr + (size_t)k * l->slot_stride + kPayloadOff;
 }
 
-static double *dist_acc(const dpwa_learner *l) { return (double *)l->dist_mem.ptr(); }
-static dpwa_distance *dist_record(const dpwa_learner *l) { return (dpwa_distance *)(l->dist_mem.ptr() + kDistanceWorkspaceBytes); }
-
-static const ParamEntry *pd_table(const dpwa_learner *l) { return (const ParamEntry *)l->pd_mem.ptr(); }
-static double *pd_acc(const dpwa_learner *l) { return (double *)(l->pd_mem.ptr() + l->pd_workspace_off); }
-static dpwa_param_distance_head *pd_record(const dpwa_learner *l)
+// What the learner averages, as its measurements see it.
+static Payload payload(const dpwa_learner *l)
 {
-    return (dpwa_param_distance_head *)(l->pd_mem.ptr() + l->pd_record_off);
-}
-// The bytes of the learner's payload.
-static int64_t payload_bytes(const dpwa_learner *l)
-{
-    return l->dtype == DPWA_MIXED ? l->n : l->n * (int64_t)dtype_size(l->dtype);
+    return Payload{l->dtype, l->n, l->layout_digest ? &l->layout : nullptr, &l->ctl->coef};
 }
 
 static int64_t now_ns()
@@ -575,7 +555,7 @@ static bool is_live(dpwa_learner *l)
 }
 
 // ---------------------------------------------------------------- stateless entry points
-// What they share; `fn` names the entry in messages.  The six lerp wrappers' body:
+// (What they share: kernels.hpp.)  The six lerp wrappers' body; `fn` names the entry in messages.
 static int lerp_entry(const char *fn, int32_t dtype, void *param, const void *peer, int64_t n,
                       const dpwa_coef *coef_dev, const double *factor, dpwa_stream_t stream)
 {
@@ -583,33 +563,6 @@ static int lerp_entry(const char *fn, int32_t dtype, void *param, const void *pe
     const float f = factor ? (float)*factor : 0.f, g = factor ? (float)(1.0 - *factor) : 0.f;
     HIP_TRY(launch_lerp(dtype, param, peer, n, factor ? nullptr : coef_dev, f, g, (hipStream_t)stream));
     return DPWA_OK;
-}
-
-// The caller's begin/end events as a launch's timing argument: NULL when none were given.
-struct CallerTiming {
-    LaunchTiming t;
-    CallerTiming(void *start_event, void *stop_event) : t{(hipEvent_t)start_event, (hipEvent_t)stop_event} {}
-    operator const LaunchTiming *() const { return t.start ? &t : nullptr; }
-};
-
-static int check_method(const dpwa_interp *cfg, const char *fn)
-{
-    if (cfg->method < 0 || cfg->method > 2) return set_error(DPWA_ERR_ARG, "%s: unknown method %d", fn, cfg->method);
-    return DPWA_OK;
-}
-
-// Factor from the header of `peer_slot`, clock read at clock_dev and written behind it.
-static FusedArgs stateless_args(const dpwa_interp *cfg, double *clock_dev, const void *peer_slot, double loss,
-                                dpwa_coef *coef_dev)
-{
-    FusedArgs fa{};
-    fa.cfg = *cfg;
-    fa.clock_in = clock_dev;
-    fa.clock_out = clock_dev + 1;
-    fa.hdr = (const dpwa_header *)peer_slot;
-    fa.loss_h = loss;
-    fa.coef_out = coef_dev;
-    return fa;
 }
 
 extern "C" {
@@ -710,248 +663,12 @@ int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_
     if (!layout || !cfg || !clock_dev || !coef_dev || !peer_slot || !param || (!start_event) != (!stop_event))
         return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: bad arguments");
     if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: %s", why);
-    if (((uintptr_t)param | (uintptr_t)peer_slot | (uintptr_t)snap_payload) & 15)
+    if (!aligned16(param, peer_slot, snap_payload))
         return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: a segmented payload is 16-byte aligned");
     if (int rc = check_method(cfg, "dpwa_average_mixed")) return rc;
     const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
     HIP_TRY(launch_average_mixed(*layout, param, (const char *)peer_slot + kPayloadOff, fa, snap_payload,
                                  (hipStream_t)stream, CallerTiming(start_event, stop_event)));
-    return DPWA_OK;
-}
-
-static_assert(sizeof(dpwa_distance) == 32, "dpwa_distance must be 32 bytes");
-static_assert(kDistanceWorkspaceBytes % DPWA_DISTANCE_ACC_STRIDE == 0 && kDistanceWorkspaceBytes <= (1 << 20),
-              "distance workspace");
-
-int dpwa_distance_workspace(int64_t *bytes)
-{
-    if (!bytes) return set_error(DPWA_ERR_ARG, "dpwa_distance_workspace: NULL argument");
-    *bytes = kDistanceWorkspaceBytes;
-    return DPWA_OK;
-}
-
-// The workspace and the record of a stateless distance entry: non-null, 16-B / 8-B aligned.
-static bool distance_buffers_ok(const void *workspace, const dpwa_distance *out_dev)
-{
-    return workspace && out_dev && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)out_dev & 7) == 0;
-}
-
-int dpwa_measure_distance(int32_t dtype, const void *param, const void *peer_payload, int64_t n, void *workspace,
-                          dpwa_distance *out_dev, dpwa_stream_t stream)
-{
-    if (n < 0 || (n > 0 && (!param || !peer_payload)) || !distance_buffers_ok(workspace, out_dev))
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: bad arguments (NULL or misaligned pointer, n < 0)");
-    if (dtype == DPWA_MIXED)
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: a DPWA_MIXED payload needs its layout "
-                                       "(dpwa_measure_distance_mixed)");
-    if (dtype != DPWA_F32 && dtype != DPWA_BF16 && dtype != DPWA_F16)
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: unknown dtype %d", dtype);
-    const size_t es = dtype_size(dtype);
-    if (((uintptr_t)param | (uintptr_t)peer_payload) & (es - 1))
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: an operand is not aligned to its element size");
-    HIP_TRY(launch_distance(dtype, param, peer_payload, n, (double *)workspace, (hipStream_t)stream));
-    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, nullptr, n, (hipStream_t)stream));
-    return DPWA_OK;
-}
-
-int dpwa_measure_distance_mixed(const dpwa_layout *layout, const void *param, const void *peer_payload,
-                                void *workspace, dpwa_distance *out_dev, dpwa_stream_t stream)
-{
-    if (!layout || !param || !peer_payload || !distance_buffers_ok(workspace, out_dev))
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: bad arguments (NULL or misaligned pointer)");
-    if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: %s", why);
-    if (((uintptr_t)param | (uintptr_t)peer_payload) & 15)
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: a segmented payload is 16-byte aligned");
-    int64_t n = 0;
-    for (int i = 0; i < layout->count; ++i) n += layout->seg[i].byte_length / (int64_t)dtype_size(layout->seg[i].dtype);
-    HIP_TRY(launch_distance_mixed(*layout, param, peer_payload, (double *)workspace, (hipStream_t)stream));
-    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, nullptr, n, (hipStream_t)stream));
-    return DPWA_OK;
-}
-
-int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int64_t n, const dpwa_interp *cfg,
-                         double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, void *workspace,
-                         dpwa_distance *out_dev, dpwa_stream_t stream, void *start_event, void *stop_event)
-{
-    if (!cfg || !clock_dev || !coef_dev || !peer_slot || n < 0 || (n > 0 && !param) || (!start_event) != (!stop_event) ||
-        !distance_buffers_ok(workspace, out_dev))
-        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: bad arguments (NULL or misaligned pointer, n < 0)");
-    if (dtype == DPWA_MIXED)
-        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: segmented (DPWA_MIXED) payloads have no tracked kernel "
-                                       "(dpwa_measure_distance_mixed, then dpwa_average_mixed)");
-    if (dtype != DPWA_F32 && dtype != DPWA_BF16 && dtype != DPWA_F16)
-        return set_error(DPWA_ERR_ARG, "dpwa_average_tracked: unknown dtype %d", dtype);
-    if (int rc = check_method(cfg, "dpwa_average_tracked")) return rc;
-    const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
-    const CallerTiming timing(start_event, stop_event);
-    hipStream_t s = (hipStream_t)stream;
-    const char *peer = (const char *)peer_slot + kPayloadOff;
-    if ((((uintptr_t)param | (uintptr_t)peer | (uintptr_t)snap_payload) & 15) == 0) {
-        HIP_TRY(launch_average_tracked(dtype, param, peer, n, fa, snap_payload, false, (double *)workspace, s, timing));
-    } else {   // the stand-alone pass, then dpwa_average's own (unaligned) kernel
-        HIP_TRY(launch_distance(dtype, param, peer, n, (double *)workspace, s));
-        HIP_TRY(launch_average(dtype, param, peer, n, fa, snap_payload, s, timing));
-    }
-    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, s));
-    return DPWA_OK;
-}
-
-int dpwa_distance_finish(void *workspace, dpwa_distance *out_dev, const dpwa_coef *coef_dev, int64_t n,
-                         dpwa_stream_t stream, void *start_event, void *stop_event)
-{
-    if (n < 0 || (!start_event) != (!stop_event) || !distance_buffers_ok(workspace, out_dev))
-        return set_error(DPWA_ERR_ARG, "dpwa_distance_finish: bad arguments (NULL or misaligned pointer, n < 0)");
-    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, (hipStream_t)stream,
-                                   CallerTiming(start_event, stop_event)));
-    return DPWA_OK;
-}
-
-// ---------------------------------------------------------------- per-parameter distance
-static_assert(sizeof(dpwa_param_range) == 24 && sizeof(dpwa_param_pair) == 16 && sizeof(dpwa_param_distance_head) == 16,
-              "per-parameter distance records");
-
-// The rules of a list of dpwa_param_range (include/dpwa_hip.h).  `payload`: also the rules that
-// need one -- `dtype` and `n` of a single-dtype payload, or DPWA_MIXED with `layout`.  Returns
-// DPWA_OK or DPWA_ERR_ARG with the rule broken.  Host only, no HIP call.
-static int param_ranges_problem(const char *fn, const dpwa_param_range *ranges, int64_t count, bool payload,
-                                int32_t dtype, int64_t n, const dpwa_layout *layout)
-{
-    if (count < 0 || (count > 0 && !ranges)) return set_error(DPWA_ERR_ARG, "%s: NULL ranges or count < 0", fn);
-    if (count > 0x7fffffffLL / kParamDistRows)
-        return set_error(DPWA_ERR_ARG, "%s: more than %lld ranges", fn, 0x7fffffffLL / kParamDistRows);
-    if (payload) {
-        if (dtype == DPWA_MIXED) {
-            if (!layout) return set_error(DPWA_ERR_ARG, "%s: a DPWA_MIXED payload needs its layout", fn);
-            if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "%s: %s", fn, why);
-        } else if (dtype_size(dtype) == 0 || dtype == DPWA_F64 || n < 0) {
-            return set_error(DPWA_ERR_ARG, "%s: unknown dtype %d or n < 0", fn, dtype);
-        }
-    }
-    int64_t prev_end = 0;
-    for (int64_t t = 0; t < count; ++t) {
-        const dpwa_param_range &r = ranges[t];
-        const long long i = (long long)t, off = (long long)r.byte_offset, len = (long long)r.byte_length;
-        if (r.dtype != DPWA_F32 && r.dtype != DPWA_BF16 && r.dtype != DPWA_F16)
-            return set_error(DPWA_ERR_ARG, "%s: range %lld: dtype %d is not DPWA_F32, DPWA_BF16 or DPWA_F16", fn, i, r.dtype);
-        if (r.reserved != 0) return set_error(DPWA_ERR_ARG, "%s: range %lld: reserved must be 0", fn, i);
-        if (r.byte_offset < 0 || r.byte_offset % DPWA_PARAM_ALIGN)
-            return set_error(DPWA_ERR_ARG, "%s: range %lld: byte_offset %lld is not a non-negative multiple of %d", fn, i,
-                             off, DPWA_PARAM_ALIGN);
-        if (r.byte_length < 0 || r.byte_length % (int64_t)dtype_size(r.dtype))
-            return set_error(DPWA_ERR_ARG, "%s: range %lld: byte_length %lld is not a non-negative multiple of the "
-                                           "element size %d", fn, i, len, (int)dtype_size(r.dtype));
-        if (r.byte_length > INT64_MAX - r.byte_offset)
-            return set_error(DPWA_ERR_ARG, "%s: range %lld: byte_offset + byte_length overflows", fn, i);
-        if (r.byte_offset < prev_end)
-            return set_error(DPWA_ERR_ARG, "%s: range %lld: ranges must be ascending and non-overlapping (it begins at "
-                                           "%lld, the one before ends at %lld)", fn, i, off, (long long)prev_end);
-        prev_end = r.byte_offset + r.byte_length;
-        if (!payload) continue;
-        if (dtype != DPWA_MIXED) {
-            if (r.dtype != dtype)
-                return set_error(DPWA_ERR_ARG, "%s: range %lld: dtype %d in a payload of dtype %d", fn, i, r.dtype, dtype);
-            if (prev_end > n * (int64_t)dtype_size(dtype))
-                return set_error(DPWA_ERR_ARG, "%s: range %lld: it ends at byte %lld, outside the payload of %lld bytes",
-                                 fn, i, (long long)prev_end, (long long)(n * (int64_t)dtype_size(dtype)));
-            continue;
-        }
-        bool inside = false;
-        for (int k = 0; k < layout->count; ++k) {
-            const dpwa_segment &g = layout->seg[k];
-            if (g.dtype == r.dtype && r.byte_offset >= g.byte_offset && prev_end <= g.byte_offset + g.byte_length)
-                inside = true;
-        }
-        if (!inside)
-            return set_error(DPWA_ERR_ARG, "%s: range %lld: bytes [%lld, %lld) do not lie wholly inside the segment of "
-                                           "dtype %d", fn, i, off, (long long)prev_end, r.dtype);
-    }
-    return DPWA_OK;
-}
-
-// The device table of valid ranges, and the accumulator rows they need in all.
-static int64_t param_table(const dpwa_param_range *ranges, int64_t count, std::vector<ParamEntry> *out)
-{
-    constexpr int64_t span = 1024;   // the pass's one-wave span
-    int64_t rows = 0;
-    if (out) out->assign((size_t)count, ParamEntry{});
-    for (int64_t t = 0; t < count; ++t) {
-        const int64_t begin = ranges[t].byte_offset, end = begin + ranges[t].byte_length;
-        const int64_t spans = end > begin ? (end + span - 1) / span - begin / span : 0;
-        const int64_t r = std::min<int64_t>(spans, kParamDistRows);
-        if (out) (*out)[(size_t)t] = ParamEntry{begin, end, ranges[t].dtype, (int32_t)rows, (int32_t)r, 0};
-        rows += r;
-    }
-    return rows;
-}
-
-static void param_sizes(const dpwa_param_range *ranges, int64_t count, dpwa_param_sizes &z)
-{
-    z.table_bytes = std::max<int64_t>(count, 1) * (int64_t)sizeof(ParamEntry);
-    z.workspace_bytes = std::max<int64_t>(param_table(ranges, count, nullptr), 1) * DPWA_DISTANCE_ACC_STRIDE;
-    z.record_bytes = (int64_t)sizeof(dpwa_param_distance_head) + count * (int64_t)sizeof(dpwa_param_pair);
-    z.max_rows = kParamDistRows;
-    z.reserved = 0;
-}
-
-int dpwa_param_ranges_check(const dpwa_param_range *ranges, int64_t count, int32_t dtype, int64_t n,
-                            const dpwa_layout *layout)
-{
-    return param_ranges_problem("dpwa_param_ranges_check", ranges, count, true, dtype, n, layout);
-}
-
-int dpwa_param_distance_sizes(const dpwa_param_range *ranges, int64_t count, dpwa_param_sizes *sizes)
-{
-    if (!sizes) return set_error(DPWA_ERR_ARG, "dpwa_param_distance_sizes: NULL argument");
-    if (int rc = param_ranges_problem("dpwa_param_distance_sizes", ranges, count, false, 0, 0, nullptr)) return rc;
-    param_sizes(ranges, count, *sizes);
-    return DPWA_OK;
-}
-
-int dpwa_param_distance_table(const dpwa_param_range *ranges, int64_t count, void *table_dev)
-{
-    if (count < 1 || !table_dev || ((uintptr_t)table_dev & 15))
-        return set_error(DPWA_ERR_ARG, "dpwa_param_distance_table: count < 1, or a NULL or misaligned table");
-    if (int rc = param_ranges_problem("dpwa_param_distance_table", ranges, count, false, 0, 0, nullptr)) return rc;
-    std::vector<ParamEntry> table;
-    param_table(ranges, count, &table);
-    HIP_TRY(hipMemcpy(table_dev, table.data(), table.size() * sizeof(ParamEntry), hipMemcpyHostToDevice));
-    return DPWA_OK;
-}
-
-static bool param_buffers_ok(const void *table_dev, int64_t count, const void *workspace, const void *out_dev)
-{
-    return count >= 1 && table_dev && workspace && out_dev &&
-           ((((uintptr_t)table_dev | (uintptr_t)workspace) & 15) == 0) && ((uintptr_t)out_dev & 7) == 0;
-}
-
-int dpwa_measure_param_distance(const void *table_dev, int64_t count, const void *param, const void *peer_payload,
-                                int64_t payload_bytes, void *workspace, dpwa_param_distance_head *out_dev,
-                                dpwa_stream_t stream, void *start_event, void *stop_event)
-{
-    if (!param_buffers_ok(table_dev, count, workspace, out_dev) || payload_bytes < 0 || (!start_event) != (!stop_event) ||
-        (payload_bytes > 0 && (!param || !peer_payload)))
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_param_distance: bad arguments (NULL or misaligned pointer, "
-                                       "count < 1, payload_bytes < 0)");
-    if (((uintptr_t)param | (uintptr_t)peer_payload) & 15)
-        return set_error(DPWA_ERR_ARG, "dpwa_measure_param_distance: the parameters and the peer payload are 16-byte "
-                                       "aligned");
-    const CallerTiming timing(start_event, stop_event);
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_param_distance(param, peer_payload, payload_bytes, (const ParamEntry *)table_dev, count,
-                                  (double *)workspace, s, timing));
-    HIP_TRY(launch_param_distance_finish((double *)workspace, (const ParamEntry *)table_dev, count, out_dev, nullptr, s));
-    return DPWA_OK;
-}
-
-int dpwa_param_distance_finish(const void *table_dev, int64_t count, void *workspace,
-                               dpwa_param_distance_head *out_dev, const dpwa_coef *coef_dev, dpwa_stream_t stream,
-                               void *start_event, void *stop_event)
-{
-    if (!param_buffers_ok(table_dev, count, workspace, out_dev) || (!start_event) != (!stop_event))
-        return set_error(DPWA_ERR_ARG, "dpwa_param_distance_finish: bad arguments (NULL or misaligned pointer, "
-                                       "count < 1)");
-    HIP_TRY(launch_param_distance_finish((double *)workspace, (const ParamEntry *)table_dev, count, out_dev, coef_dev,
-                                         (hipStream_t)stream, CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -965,9 +682,9 @@ int dpwa_stream_mix(void *const *dst, int nw, const void *const *src, int nr, in
     for (int i = 0; i < nr; ++i) a.src[i] = (const char *)src[i];
     for (int j = 0; j < nw; ++j) a.dst[j] = (char *)dst[j];
     for (int i = 0; i < nr; ++i)
-        if (!a.src[i] || ((uintptr_t)a.src[i] & 15)) return set_error(DPWA_ERR_ARG, "dpwa_stream_mix: source %d", i);
+        if (!a.src[i] || !aligned16(a.src[i])) return set_error(DPWA_ERR_ARG, "dpwa_stream_mix: source %d", i);
     for (int j = 0; j < nw; ++j)
-        if (!a.dst[j] || ((uintptr_t)a.dst[j] & 15)) return set_error(DPWA_ERR_ARG, "dpwa_stream_mix: destination %d", j);
+        if (!a.dst[j] || !aligned16(a.dst[j])) return set_error(DPWA_ERR_ARG, "dpwa_stream_mix: destination %d", j);
     a.nbytes = nbytes;
     a.nr = nr;
     a.nw = nw;
@@ -1205,12 +922,7 @@ int dpwa_learner_publish_reuse(dpwa_learner *l, const void *flat, double loss, c
 }
 
 // A DPWA_MIXED learner averages only once it knows its layout.
-static int need_layout(const dpwa_learner *l, const char *fn)
-{
-    if (l->dtype == DPWA_MIXED && !l->layout_digest)
-        return set_error(DPWA_ERR_STATE, "%s: a DPWA_MIXED learner has no layout yet (dpwa_learner_set_layout)", fn);
-    return DPWA_OK;
-}
+static int need_layout(const dpwa_learner *l, const char *fn) { return payload(l).need_layout(fn); }
 
 int dpwa_learner_set_layout(dpwa_learner *l, const dpwa_layout *layout)
 {
@@ -1560,12 +1272,6 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
 }
 
 static int relay_materialize(dpwa_learner *l);
-static int distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s);
-static int distance_after(dpwa_learner *l, hipStream_t s);
-static int param_distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s);
-static int param_distance_after(dpwa_learner *l, hipStream_t s);
-static const char *const kParamUnaligned = "the per-parameter distance (dpwa_learner_set_param_distance) has no form "
-                                           "for parameters that are not 16-byte aligned";
 
 static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev)
 {
@@ -1626,20 +1332,19 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_lerp: a resident learner averages with dpwa_learner_average");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    if (l->dtype == DPWA_MIXED && ((uintptr_t)flat & 15))   // (its layout is known: the factor was computed)
+    if (l->dtype == DPWA_MIXED && !aligned16(flat))   // (its layout is known: the factor was computed)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
-    if (l->ptrack && ((uintptr_t)flat & 15)) return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: %s", kParamUnaligned);
-    if (int rc = param_distance_before(l, flat, l->src + kPayloadOff, s)) return rc;
-    if (l->track)
-        if (int rc = distance_before(l, flat, l->src + kPayloadOff, s)) return rc;
-    if (l->dtype == DPWA_MIXED) {
-        HIP_TRY(launch_lerp_mixed(l->layout, flat, l->src + kPayloadOff, &l->ctl->coef, s));
-    } else {
-        HIP_TRY(launch_lerp(l->dtype, flat, l->src + kPayloadOff, l->n, &l->ctl->coef, 0.f, 0.f, s));
-    }
-    if (l->track)
-        if (int rc = distance_after(l, s)) return rc;
-    if (int rc = param_distance_after(l, s)) return rc;
+    if (int rc = l->measure.operands_problem("dpwa_learner_lerp", flat)) return rc;
+    const Measured m{&l->measure, payload(l), flat, l->src + kPayloadOff, nullptr};
+    int rc = measured_average(&m, 1, s, [&]() -> int {
+        if (l->dtype == DPWA_MIXED) {
+            HIP_TRY(launch_lerp_mixed(l->layout, flat, m.peer, &l->ctl->coef, s));
+        } else {
+            HIP_TRY(launch_lerp(l->dtype, flat, m.peer, l->n, &l->ctl->coef, 0.f, 0.f, s));
+        }
+        return DPWA_OK;
+    });
+    if (rc) return rc;
     HIP_TRY(note_consumed(l, s));
     l->written_through.clear();
     finish_fetch(l);
@@ -1666,9 +1371,9 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
 {
     if (!l->have_fetch || l->have_factor) return set_error(DPWA_ERR_STATE, "dpwa_learner_average: no fetch in flight");
     if (int rc = need_layout(l, "dpwa_learner_average")) return rc;
-    if (l->dtype == DPWA_MIXED && ((uintptr_t)flat & 15))
+    if (l->dtype == DPWA_MIXED && !aligned16(flat))
         return set_error(DPWA_ERR_ARG, "dpwa_learner_average: a segmented payload is 16-byte aligned");
-    if (l->ptrack && ((uintptr_t)flat & 15)) return set_error(DPWA_ERR_ARG, "dpwa_learner_average: %s", kParamUnaligned);
+    if (int rc = l->measure.operands_problem("dpwa_learner_average", flat)) return rc;
     p = AvgPlan();
     p.mixed = l->dtype == DPWA_MIXED;
     if (l->resident) {   // read where the parameters are (the published slot), write the next slot
@@ -1695,7 +1400,7 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
             p.fa.dtype = l->dtype;
         }
     }
-    if (l->relay_deferred && (((uintptr_t)flat | (uintptr_t)p.snap) & 15) == 0) {
+    if (l->relay_deferred && aligned16(flat, p.snap)) {
         // the relay's phase 2 fused into the average: stripes read where phase 1 left them
         const RelayArgs &a = l->relay_saved;
         p.fa.hdr = (const dpwa_header *)(a.slots[l->relay_saved_pick] + a.slot_off);
@@ -1732,78 +1437,25 @@ static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
     return DPWA_OK;
 }
 
-// Distance tracking around an average that has no tracked kernel: the stand-alone pass over the
-// operands before the average on `s` (the in-place forms overwrite what it reads), the finishing
-// step after it (it reads the coefficients that average committed).
-static int distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s)
-{
-    if (l->dtype == DPWA_MIXED) HIP_TRY(launch_distance_mixed(l->layout, flat, peer, dist_acc(l), s));
-    else HIP_TRY(launch_distance(l->dtype, flat, peer, l->n, dist_acc(l), s));
-    return DPWA_OK;
-}
-
-static int distance_after(dpwa_learner *l, hipStream_t s)
-{
-    int64_t n = l->n;
-    if (l->dtype == DPWA_MIXED) {   // the element slots of its segments
-        n = 0;
-        for (int i = 0; i < l->layout.count; ++i)
-            n += l->layout.seg[i].byte_length / (int64_t)dtype_size(l->layout.seg[i].dtype);
-    }
-    HIP_TRY(launch_distance_finish(dist_acc(l), dist_record(l), &l->ctl->coef, n, s));
-    return DPWA_OK;
-}
-
-// The averaging launch of plan p, and the whole-model distance around or inside it.
-static int average_launch_tracked(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
-{
-    if (l->track) {   // never p.relay: relay_phase2 refuses to defer for a tracking learner
-        const bool fused = !p.mixed && ((((uintptr_t)p.flat | (uintptr_t)p.peer | (uintptr_t)p.snap) & 15) == 0);
-        if (fused) {
-            HIP_TRY(launch_average_tracked(l->dtype, p.flat, p.peer, l->n, p.fa, p.snap, p.oop, dist_acc(l), s,
-                                           take_timing(l)));
-            return distance_after(l, s);
-        }
-        if (int rc = distance_before(l, p.flat, p.peer, s)) return rc;
-    }
-    if (p.mixed) {   // never p.relay: relay_phase2 refuses to defer for a segmented payload
-        HIP_TRY(launch_average_mixed(l->layout, p.flat, p.peer, p.fa, p.snap, s, take_timing(l), p.oop));
-    } else if (p.relay) {
-        HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
-                                     take_timing(l), p.oop));
-    } else {
-        const LaunchTiming *timing = ((uintptr_t)p.flat & 15) == 0 ? take_timing(l) : nullptr;
-        HIP_TRY(launch_average(l->dtype, p.flat, p.peer, l->n, p.fa, p.snap, s, timing, p.oop));
-    }
-    return l->track ? distance_after(l, s) : DPWA_OK;
-}
-
-// The per-parameter distance around an average, whatever its form (its pass before, since the
-// in-place forms overwrite what it reads; its finishing step behind the coefficients).  Off, or a
-// round it skips: nothing but the average's own launches.
-static int param_distance_before(dpwa_learner *l, const void *flat, const char *peer, hipStream_t s)
-{
-    if (!l->ptrack) return DPWA_OK;   // never with a fused relay second phase: relay_phase2 refuses to defer
-    l->pd_now = ++l->pd_rounds % l->pd_every == 0;
-    if (!l->pd_now) return DPWA_OK;
-    HIP_TRY(launch_param_distance(flat, peer, payload_bytes(l), pd_table(l), l->pd_count, pd_acc(l), s));
-    ++l->pd_measured;
-    return DPWA_OK;
-}
-
-static int param_distance_after(dpwa_learner *l, hipStream_t s)
-{
-    if (!l->ptrack || !l->pd_now) return DPWA_OK;
-    l->pd_now = false;
-    HIP_TRY(launch_param_distance_finish(pd_acc(l), pd_table(l), l->pd_count, pd_record(l), &l->ctl->coef, s));
-    return DPWA_OK;
-}
-
+// The averaging launch of plan p with the learner's measurements around it (measured_average); a
+// fused whole-model record gets the tracked kernel in its place.
 static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
-    if (int rc = param_distance_before(l, p.flat, p.peer, s)) return rc;
-    if (int rc = average_launch_tracked(l, p, s)) return rc;
-    return param_distance_after(l, s);
+    // (the unaligned launch_average is not timed; p.relay: relay_phase2 refuses to defer for a
+    // segmented payload or a measuring learner)
+    const LaunchTiming *timing = p.mixed || p.relay || aligned16(p.flat) ? take_timing(l) : nullptr;
+    const Measured m{&l->measure, payload(l), p.flat, p.peer, p.snap, &p.fa, p.oop, timing};
+    return measured_average(&m, 1, s, [&]() -> int {
+        if (p.mixed) {
+            HIP_TRY(launch_average_mixed(l->layout, p.flat, p.peer, p.fa, p.snap, s, timing, p.oop));
+        } else if (p.relay) {
+            HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
+                                         timing, p.oop));
+        } else {
+            HIP_TRY(launch_average(l->dtype, p.flat, p.peer, l->n, p.fa, p.snap, s, timing, p.oop));
+        }
+        return DPWA_OK;
+    });
 }
 
 static int average_impl(dpwa_learner *l, void *flat, double loss, const double *loss_dev, hipStream_t s,
@@ -1820,7 +1472,7 @@ static int average_impl(dpwa_learner *l, void *flat, double loss, const double *
 // element type (a segmented payload is not batched).
 static bool batchable(const AvgPlan &p)
 {
-    return !p.relay && !p.mixed && ((((uintptr_t)p.flat | (uintptr_t)p.peer | (uintptr_t)p.snap) & 15) == 0);
+    return !p.relay && !p.mixed && aligned16(p.flat, p.peer, p.snap);
 }
 
 // Launches the batchable plans in groups of the same (dtype, write-through), up to
@@ -1842,15 +1494,9 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
         }
         AvgBatch b{};
         const LaunchTiming *timing = take_timing(la);
-        dpwa_learner *tracking[kMaxAvgBatch];   // the dispatch stays as it is: their passes go around it
-        int tracking_entry[kMaxAvgBatch], n_tracking = 0;
-        dpwa_learner *member[kMaxAvgBatch];
+        Measured member[kMaxAvgBatch];   // the dispatch stays as it is: their measurements go around it
         auto add = [&](dpwa_learner *l, const AvgPlan &p) {
-            member[b.count] = l;
-            if (l->track) {
-                tracking[n_tracking] = l;
-                tracking_entry[n_tracking++] = b.count;
-            }
+            member[b.count] = Measured{&l->measure, payload(l), p.flat, p.peer, p.snap};
             AvgEntry &e = b.e[b.count++];
             e.param = p.flat;
             e.peer = p.peer;
@@ -1868,17 +1514,11 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
             add(ls[ic], plans[ic]);
             done[c] = 1;
         }
-        for (int m = 0; m < b.count; ++m)
-            if (int rc = param_distance_before(member[m], b.e[m].param, (const char *)b.e[m].peer, s)) return rc;
-        for (int t = 0; t < n_tracking; ++t) {
-            const AvgEntry &e = b.e[tracking_entry[t]];
-            if (int rc = distance_before(tracking[t], e.param, (const char *)e.peer, s)) return rc;
-        }
-        HIP_TRY(launch_average_batch(la->dtype, pa.write_through, b, s, timing, pa.oop));
-        for (int t = 0; t < n_tracking; ++t)
-            if (int rc = distance_after(tracking[t], s)) return rc;
-        for (int m = 0; m < b.count; ++m)
-            if (int rc = param_distance_after(member[m], s)) return rc;
+        int rc = measured_average(member, b.count, s, [&]() -> int {
+            HIP_TRY(launch_average_batch(la->dtype, pa.write_through, b, s, timing, pa.oop));
+            return DPWA_OK;
+        });
+        if (rc) return rc;
     }
     return DPWA_OK;
 }
@@ -1946,7 +1586,7 @@ static int average_many_impl(const char *fn, int32_t dtype, const dpwa_average_d
         const dpwa_average_desc &d = descs[i];
         if ((!d.param && d.n > 0) || !d.peer_slot || !d.clock_dev || !d.coef_dev || d.n < 0 ||
             (d.snap_payload == nullptr && d.n > 0 && dual) ||
-            (((uintptr_t)d.param | (uintptr_t)d.peer_slot | (uintptr_t)d.snap_payload) & 15))
+            !aligned16(d.param, d.peer_slot, d.snap_payload))
             return set_error(DPWA_ERR_ARG, "%s: descriptor %d: NULL, unaligned or mixed write-through", fn, i);
         AvgEntry &e = b.e[b.count++];
         e.param = d.param;
@@ -1981,35 +1621,17 @@ int dpwa_average_many_resident(int32_t dtype, const dpwa_average_desc *descs, in
 int dpwa_learner_set_distance(dpwa_learner *l, int on)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_distance: NULL learner");
-    if (!on) {
-        l->track = false;
-        return DPWA_OK;
-    }
-    if (l->relay_deferred)
-        return set_error(DPWA_ERR_STATE, "dpwa_learner_set_distance: a fused relay second phase is pending "
-                                         "(dpwa_learner_relay_phase2 with fuse != 0), which reads no contiguous peer "
-                                         "snapshot to measure against");
-    if (!l->dist_mem.ptr()) {   // once, here: never inside a round
-        DeviceGuard dg(l->device);
-        const size_t bytes = (size_t)kDistanceWorkspaceBytes + sizeof(dpwa_distance);
-        DevBuf mem;
-        HIP_TRY(mem.alloc(bytes));
-        hipError_t e = hipMemset(mem.ptr(), 0, bytes);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "dpwa_learner_set_distance: %s", hipGetErrorString(e));
-        l->dist_mem = std::move(mem);
-    }
-    l->track = true;
-    return DPWA_OK;
+    DeviceGuard dg(l->device);
+    return l->measure.set_whole("dpwa_learner_set_distance", on != 0, l->relay_deferred);
 }
 
 int dpwa_learner_distance(dpwa_learner *l, const dpwa_distance **dev)
 {
     if (!l || !dev) return set_error(DPWA_ERR_ARG, "dpwa_learner_distance: NULL argument");
-    if (!l->dist_mem.ptr())
+    if (!l->measure.record())
         return set_error(DPWA_ERR_STATE, "dpwa_learner_distance: distance tracking was never switched on "
                                          "(dpwa_learner_set_distance)");
-    *dev = dist_record(l);
+    *dev = l->measure.record();
     return DPWA_OK;
 }
 
@@ -2017,56 +1639,26 @@ int dpwa_learner_set_param_distance(dpwa_learner *l, const dpwa_param_range *ran
 {
     const char *fn = "dpwa_learner_set_param_distance";
     if (!l) return set_error(DPWA_ERR_ARG, "%s: NULL learner", fn);
-    if (count == 0) {
-        l->ptrack = false;
-        return DPWA_OK;
-    }
-    if (every < 1) return set_error(DPWA_ERR_ARG, "%s: every = %d, it must be >= 1", fn, every);
-    if (int rc = need_layout(l, fn)) return rc;
-    if (int rc = param_ranges_problem(fn, ranges, count, true, l->dtype, l->n, &l->layout)) return rc;
-    if (l->relay_deferred)
-        return set_error(DPWA_ERR_STATE, "%s: a fused relay second phase is pending (dpwa_learner_relay_phase2 with "
-                                         "fuse != 0), which reads no contiguous peer snapshot to measure against", fn);
     DeviceGuard dg(l->device);
-    dpwa_param_sizes z;
-    param_sizes(ranges, count, z);
-    std::vector<ParamEntry> table;
-    param_table(ranges, count, &table);
-    const int64_t workspace_off = (z.table_bytes + 127) / 128 * 128, record_off = workspace_off + z.workspace_bytes;
-    const size_t bytes = (size_t)(record_off + z.record_bytes);
-    DevBuf mem;   // once, here: never inside a round
-    HIP_TRY(mem.alloc(bytes));
-    hipError_t e = hipMemset(mem.ptr(), 0, bytes);
-    if (e == hipSuccess) e = hipMemcpy(mem.ptr(), table.data(), table.size() * sizeof(ParamEntry), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // (and nothing in flight reads the buffers replaced below)
-    if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-    l->pd_mem = std::move(mem);
-    l->pd_count = count;
-    l->pd_workspace_off = workspace_off;
-    l->pd_record_off = record_off;
-    l->pd_every = every;
-    l->pd_rounds = l->pd_measured = 0;
-    l->pd_now = false;
-    l->ptrack = true;
-    return DPWA_OK;
+    return l->measure.set_param(fn, ranges, count, every, payload(l), l->relay_deferred);
 }
 
 int dpwa_learner_param_distance(dpwa_learner *l, const dpwa_param_distance_head **dev, int64_t *count)
 {
     if (!l || !dev || !count) return set_error(DPWA_ERR_ARG, "dpwa_learner_param_distance: NULL argument");
-    if (!l->pd_mem.ptr())
+    if (!l->measure.param_record())
         return set_error(DPWA_ERR_STATE, "dpwa_learner_param_distance: the per-parameter distance was never switched on "
                                          "(dpwa_learner_set_param_distance)");
-    *dev = pd_record(l);
-    *count = l->pd_count;
+    *dev = l->measure.param_record();
+    *count = l->measure.param_count();
     return DPWA_OK;
 }
 
 int dpwa_learner_param_distance_rounds(dpwa_learner *l, int64_t *averaged, int64_t *measured)
 {
     if (!l || !averaged || !measured) return set_error(DPWA_ERR_ARG, "dpwa_learner_param_distance_rounds: NULL argument");
-    *averaged = l->pd_rounds;
-    *measured = l->pd_measured;
+    *averaged = l->measure.rounds();
+    *measured = l->measure.measured();
     return DPWA_OK;
 }
 
@@ -2395,11 +1987,11 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
     if (fuse && l->dtype == DPWA_MIXED)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_phase2: the fused second phase is not built for segmented "
                                        "(DPWA_MIXED) payloads; gather (fuse = 0)");
-    if (fuse && l->track)
+    if (fuse && l->measure.whole())
         return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
                                          "snapshot, so a learner that tracks the distance (dpwa_learner_set_distance) "
                                          "cannot use it; gather (fuse = 0)");
-    if (fuse && l->ptrack)
+    if (fuse && l->measure.param())
         return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
                                          "snapshot, so a learner that measures the per-parameter distance "
                                          "(dpwa_learner_set_param_distance) cannot use it; gather (fuse = 0)");

@@ -34,6 +34,12 @@ template <class T, hipError_t (*Free)(T)> struct Owned {
     }
 };
 
+// A plain device allocation.
+struct DevBuf : Owned<void *, hipFree> {
+    hipError_t alloc(size_t bytes) { return hipMalloc(&h, bytes); }
+    char *ptr() const { return (char *)h; }
+};
+
 // An event made by init() or at first need; hipEventDefault for one whose timestamp is read.
 struct Event : Owned<hipEvent_t, hipEventDestroy> {
     hipError_t init(unsigned flags = hipEventDisableTiming) { return h ? hipSuccess : hipEventCreateWithFlags(&h, flags); }

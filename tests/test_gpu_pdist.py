@@ -373,6 +373,71 @@ def test_two_learners_through_update_wait_average_many(tmp_path):
     assert all(np.array_equal(a, b) for a, b in zip(runs[False][3], runs[True][3]))
 
 
+def test_three_learners_with_different_options_in_one_dispatch(tmp_path):
+    """Three co-resident learners in one batched dispatch, one with the whole-model record, one with
+    "per_parameter", one with neither: two rounds, write-through off and then on.  Every learner's
+    parameters are bit-equal to the same rounds with every option off; the first learner's record meets
+    dist_ref's bound against the exact reference, and so does the record of the same learner when its
+    average runs alone (the tracked kernel: the two are compared with the reference, never with each
+    other, since the accumulation order is not fixed); the second learner's pairs meet pdist_ref's
+    rule; the third has no record."""
+    lay = LAYOUTS["A"]
+    cfg = tmp_path / "three.yaml"
+    cfg.write_text("\n".join(["- nodes:", *["  - {name: a%d, host: localhost, port: %d}" % (g, 46210 + g) for g in range(3)],
+                              "- fetch_probability: 1.0", "- timeout_ms: 2500", "- interpolation: clock",
+                              "- divergence_threshold: 0", "- constant: { value: 0.5 }", "- clock: 0", "- loss: 0"]) + "\n")
+    data = [ref.inputs(lay, case) for case in ("normal", "signed-zeros", "subnormal-differences")]
+    measuring = [dict(track_distance=True), dict(track_distance="per_parameter", parameter_ranges=py_ranges(lay)), {}]
+    real = sum(lay.elements(t) for t in range(len(lay.tensors)))
+
+    def run(options, alone):
+        grp = LocalGroup()
+        conns = [DpwaConnection("a%d" % g, str(cfg), seed=40 + g, group=grp, **options[g]) for g in range(3)]
+        flats = [to_dev(lay, data[g][0]) for g in range(3)]
+        for r in range(2):
+            snaps = [data[(g + r) % 3][0] for g in range(3)]    # what each learner publishes
+            mine = [data[(g + r) % 3][1] for g in range(3)]     # what it holds at the average
+            for g in range(3):
+                flats[g].copy_(to_dev(lay, snaps[g]))
+                conns[g].update_send(flats[g], 1.0 + g + r)
+            for g in range(3):
+                flats[g].copy_(to_dev(lay, mine[g]))
+            if alone:    # the first learner's average in a launch of its own, the others' in one dispatch
+                got = [conns[0].update_wait_average(flats[0], 0.5, write_through=bool(r))]
+                got += DpwaConnection.update_wait_average_many(conns[1:], flats[1:], [0.75, 0.6], write_through=bool(r))
+            else:
+                got = DpwaConnection.update_wait_average_many(conns, flats, [0.5, 0.75, 0.6], write_through=bool(r))
+            assert all(snap is not None for snap, _ in got)
+            peer = [snaps[int(snap.peer[1:])] for snap, _ in got]   # the snapshot each learner averaged with
+            if options[0]:
+                whole = conns[0].last_distance.read()
+                parts = [(dt, ref.tensor_bits(lay, t, mine[0]), ref.tensor_bits(lay, t, peer[0]))
+                         for t, (_, dt, _, _) in enumerate(lay.tensors)]
+                want = dist_ref.reference_many(parts)
+                for value, w in ((whole.dist2, want[0]), (whole.norm2, want[1])):
+                    assert dist_ref.problem(value, w, real) is None, (alone, r, dist_ref.problem(value, w, real))
+                assert whole.clock == conns[0].clock and conns[0].last_distance.parameters is None
+            if options[1]:
+                pd = conns[1].last_distance.parameters
+                pairs = pd.read()
+                check(lay, [pairs[n] for n, _, _, _ in lay.tensors], ref.reference(lay, mine[1], peer[1]),
+                      "three round %d" % r)
+                assert pd.clock == conns[1].clock
+            assert conns[2].last_distance is None
+        torch.cuda.synchronize()
+        out = ([f.cpu().view(torch.uint8).numpy().copy() for f in flats], [c.clock for c in conns],
+               [bytes(c._learner.read_coef()) for c in conns])
+        for c in conns:
+            c.close()
+        return out
+
+    off = run([{}, {}, {}], False)
+    for alone in (False, True):
+        on = run(measuring, alone)
+        assert all(np.array_equal(a, b) for a, b in zip(off[0], on[0])), alone
+        assert off[1:] == on[1:], alone
+
+
 def test_zero_division_and_gated_off_rounds_leave_the_record(tmp_path):
     lay = LAYOUTS["A"]
     kw = dict(track_distance="per_parameter", parameter_ranges=py_ranges(lay))

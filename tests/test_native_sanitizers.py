@@ -83,6 +83,30 @@ def test_stream_ordering_types_under_asan_ubsan(tmp_path):
     assert "order check ok" in r.stdout
 
 
+def test_measurements_around_an_average_under_asan_ubsan(tmp_path):
+    """measure.hpp's Measure and measured_average -- every distance launch of a learner goes through
+    them -- against recording stand-ins of the launches, host rules and HIP calls they make
+    (tests/native/measure_check.cpp, which links no HIP runtime).  The exact launches, with their
+    arguments, of: both options off (the average alone); the whole-model record fused (T F) and, with
+    one operand 4 bytes off, split or segmented, around the average (D A F, the finish's n being the
+    segments' element slots); the per-parameter record alone and with the other (P A Pf, P T F Pf,
+    P D A F Pf); distance_every = 3 over seven rounds; a batch of three members; a failing launch;
+    and the refusals, after which nothing is switched on or allocated."""
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    cxx = os.path.join(rocm, "lib", "llvm", "bin", "clang++")
+    if not os.path.exists(cxx):
+        pytest.skip("no ROCm clang++")
+    exe = str(tmp_path / "measure_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", *SAN, "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+           os.path.join(ROOT, "tests/native/measure_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "measure check ok" in r.stdout
+
+
 def _tsan_build(tmp_path):
     gxx = shutil.which("g++")
     if gxx is None:
