@@ -5,7 +5,7 @@
 // over TCP (conn.py:197-334).  Here a node (learner) owns, on its GPU:
 //   slots    two snapshot slots [header 256 B | pad to 4 KiB | payload] -- RxThread.state/payload,
 //            double-buffered so a publish never overwrites the slot a peer may be reading
-//   staging  one slot-sized buffer receiving a peer's snapshot -- TxThread.peer_payload
+//   staging  one slot-sized buffer receiving a peer's snapshot -- TxThread.peer_payload (fetch.hpp)
 //   ctl      the device clock and the averaging coefficients (dpwa_coef)
 // and a side stream on which fetches (xGMI pulls for peers on other GPUs) overlap the
 // training step.  Nothing here synchronises the host with the device except the explicit
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fetch.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
 #include "order.hpp"
@@ -115,12 +116,6 @@ struct DevMem {
             (void)hipFree(ptr);
         }
     }
-};
-
-// Owner of the streams a learner holds, like order.hpp's of the events and the plain buffers (DevBuf).
-struct Stream : Owned<hipStream_t, hipStreamDestroy> {   // non-blocking
-    hipError_t create() { return hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
-    hipError_t create(int priority) { return hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority); }
 };
 
 // One pinned 32-bit word, zero at first, that the device writes through `dev` and the host polls
@@ -337,38 +332,7 @@ static void close_endpoint(Endpoint &ep)
     ep.base = nullptr;
 }
 
-// A rescue lane: where a fetch re-selected after a timed-out pull goes (conn.py:304-309) -- a
-// buffer and a stream of the greatest priority (a hardware queue no stalled normal-priority stream
-// shares), so no stalled pull ahead of it can hold it up.  Lanes are made at first use, up to
-// kMaxRescueLanes, only while the device keeps kRescueReserve free beyond the new buffer and all
-// lanes together stay within 1/kRescueShare of the device's memory (7B bf16: two 14 GB lanes on a
-// 288 GB GPU); an allocation that fails caps the count where it is (rescue_cap) instead of failing
-// the round.  Lanes beyond the first kKeepRescueLanes are given back once they have been idle for
-// kLaneIdleRounds fetch rounds (trim_lanes), so a burst of stalled pulls does not hold HBM outside
-// PyTorch's allocator for the rest of the process.
-constexpr int kMaxRescueLanes = 8;
-constexpr int kKeepRescueLanes = 2;
-constexpr uint64_t kLaneIdleRounds = 8;
-constexpr size_t kRescueShare = 8;
-// fetch_state: a backlog on the caller's stream longer than this no longer defers the timeout (a
-// stream that never reaches update_send is stuck, not slow); a probe waits at most kProbeWaitUs
-constexpr int64_t kMaxBacklogMs = 60000;
-constexpr int64_t kProbeWaitUs = 2000;
-constexpr size_t kRescueReserve = (size_t)1 << 30;
 namespace {
-
-struct RescueLane {
-    DevBuf buf;
-    Stream stream;
-    DoneEvent landed;                   // its last pull landed (recorded: a pull was issued into it)
-    DoneEvent done;                     // the last reader of its buffer is done
-    uint64_t last_round = 0;            // fetch round of its last pull
-};
-
-struct Probe {   // fetch_state's clock (probe_since): a stream that only ever holds `ev`, a timing event
-    Stream stream;
-    Event ev;
-};
 
 // Window guard (resident, with reuse_guard): each publish checks the payload published last time
 // against the samples saved then and saves the new payload's (kernels.hip k_window_roll); written
@@ -440,7 +404,6 @@ struct dpwa_learner {
     // Every HIP object below has an owner that frees it: `delete` tears a learner down (after
     // dpwa_learner_destroy's device sync nothing is in flight, so the members go in any order).
     DevMem slot_mem;                // 2 slots
-    DevBuf staging;                 // 1 slot
     Ctl *ctl = nullptr;             // (= ctl_mem.ptr())
     DevBuf ctl_mem;
     uint64_t version = 0;
@@ -449,29 +412,9 @@ struct dpwa_learner {
     Stream side;
     // who waits for whom across streams (order.hpp)
     StreamMark published[2];            // slot k's publish (noted under pub_mu)
-    Event ev_issue;                     // fetch may start (recorded on the caller's stream); timed
-    DoneEvent fetched;                  // fetch landed (recorded on the stream that moved it)
-    StreamMark consumed;                // this learner finished reading its fetch source
-    // Fetches of published snapshots (DPWA_FETCH_PUBLISHED: the gossip board) alternate between
-    // two staging buffers and are not ordered after the caller's stream: each waits only for
-    // the average that last read its buffer (stage_done), so a pull starts at update_send
-    // instead of after the caller's queued work, and a peer's read mark is released sooner.
-    DevBuf staging_alt;                 // second staging buffer, allocated at the first such fetch
-    DoneEvent stage_done[2];
-    // rescue lanes (RescueLane), allocated at first use: a lane whose pull has not landed stays
-    // taken and the next re-selected pull takes another, as TxThread keeps re-selecting
-    RescueLane rescue[kMaxRescueLanes];
-    int rescue_lanes = 0;
-    int rescue_cap = kMaxRescueLanes;   // lowered when a lane's allocation fails
-    uint64_t fetch_rounds = 0;          // first (non-rescue) pulls issued: the lanes' idle clock
-    int64_t fetch_issue_ns = 0;         // host time the fetch in flight was issued (its timeout clock)
-    // the fetch in flight waits for ev_issue (the caller's stream at update_send): its deadline runs
-    // from when that point is reached, not from the host's enqueue (fetch_state)
-    bool issue_evented = false;
-    Probe probe;                        // made at the first probe (probe_since)
-    hipStream_t fetch_stream = nullptr; // stream the fetch in flight moves its bytes on (not owned)
-    int stage_next = 0;
-    int src_stage = -1;                 // buffer l->src points into: staging 0 / 1, rescue lane 2 + j; -1: none
+    // the fetch in flight: its source, staging buffers and rescue lanes, who waits for it and when
+    // its buffer may be refilled (fetch.hpp)
+    Fetch fetch;
     DoneEvent factor_done;              // last factor computation done
     int pull_mode = DPWA_PULL_COPY_ENGINE;   // how cross-device fetches move bytes
     int pull_blocks = 512;
@@ -514,13 +457,6 @@ struct dpwa_learner {
     std::mutex pub_mu;
     Stream read_stream;
     Event ev_read;
-    // fetch state
-    const char *src = nullptr;          // header of the snapshot to average with
-    bool src_copied = false;
-    bool have_fetch = false;
-    bool have_factor = false;
-    dpwa_learner *src_owner = nullptr;  // local peer whose slot is being read (reader tracking)
-    int src_slot = -1;
     std::unordered_map<int, Endpoint> peers;
     // learners (local) that read our slot k and must be waited for before rewriting it
     std::mutex readers_mu;
@@ -542,7 +478,7 @@ static Payload payload(const dpwa_learner *l)
     return Payload{l->dtype, l->n, l->layout_digest ? &l->layout : nullptr, &l->ctl->coef};
 }
 
-static int64_t now_ns()
+int64_t dpwa::now_ns()
 {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch())
         .count();
@@ -711,16 +647,13 @@ int dpwa_learner_create(dpwa_learner **out, int device, int64_t n, int32_t dtype
     // what a learner holds from its creation on (the rest is made at first use); the first failure ends it
     hipError_t e = hipSuccess;
     auto ok = [&e](hipError_t r) { return (e = r) == hipSuccess; };
-    if (ok(devmem_alloc(l->slot_mem, 2 * l->slot_stride, device)) && ok(l->staging.alloc(l->slot_stride)) &&
-        ok(l->ctl_mem.alloc(sizeof(Ctl)))) {
+    if (ok(devmem_alloc(l->slot_mem, 2 * l->slot_stride, device)) && ok(l->side.create()) &&
+        ok(l->fetch.init(l->slot_stride, l->side.h)) && ok(l->ctl_mem.alloc(sizeof(Ctl)))) {
         l->ctl = (Ctl *)l->ctl_mem.ptr();
         if (ok(hipMemset(l->slot_mem.ptr, 0, kPayloadOff)) && ok(hipMemset(l->slot_mem.ptr + l->slot_stride, 0, kPayloadOff)) &&
-            ok(hipMemset(l->staging.ptr(), 0, kPayloadOff)) && ok(hipMemset(l->ctl, 0, sizeof(Ctl))) &&
-            ok(l->side.create()) && ok(l->published[0].init()) && ok(l->published[1].init()) &&
-            ok(l->ev_issue.init(hipEventDefault)) &&   // timed: the fetch deadline
-            ok(l->fetched.init()) && ok(l->consumed.init()) && ok(l->stage_done[0].init()) &&
-            ok(l->stage_done[1].init()) && ok(l->factor_done.init()) && ok(l->written_through.init()) &&
-            ok(l->status.alloc()))
+            ok(hipMemset(l->fetch.staging(), 0, kPayloadOff)) && ok(hipMemset(l->ctl, 0, sizeof(Ctl))) &&
+            ok(l->published[0].init()) && ok(l->published[1].init()) && ok(l->factor_done.init()) &&
+            ok(l->written_through.init()) && ok(l->status.alloc()))
             ok(hipDeviceSynchronize());
     }
     if (e != hipSuccess) {   // the owners give back whatever was made
@@ -761,13 +694,13 @@ static int wait_slot_readers(dpwa_learner *l, int k, hipStream_t s)
 {
     std::lock_guard<std::mutex> g(l->readers_mu);
     for (dpwa_learner *r : l->readers[k]) {
-        if (r->have_fetch && r->src_owner == l && r->src_slot == k)
+        if (r->fetch.reads(l, k))
             return set_error(DPWA_ERR_STATE,
                              "a peer still has an unconsumed fetch of the snapshot slot about to be rewritten "
                              "(publish at most once per round)");
-        if (r->consumed.crosses(s)) {
+        if (r->fetch.consumed_mark().crosses(s)) {
             DeviceGuard rg(r->device);
-            HIP_TRY(r->consumed.order(s));
+            HIP_TRY(r->fetch.consumed_mark().order(s));
         }
     }
     l->readers[k].clear();
@@ -1087,108 +1020,8 @@ int dpwa_learner_attach_fds(dpwa_learner *l, int peer_id, const void *handle, in
     return DPWA_OK;
 }
 
-// A free rescue lane: one whose last pull landed (or none issued); *lane = -1 when every lane made
-// so far is still pulling.
-static int free_lane(dpwa_learner *l, int *lane)
-{
-    *lane = -1;
-    for (int j = 0; j < l->rescue_lanes; ++j) {
-        const hipError_t e = l->rescue[j].landed.query();
-        if (e == hipSuccess) {
-            *lane = j;
-            return DPWA_OK;
-        }
-        if (e != hipErrorNotReady) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
-    }
-    return DPWA_OK;
-}
-
-// A free rescue lane, making a new one when every lane is taken and fewer than rescue_cap exist;
-// *lane = -1 when none is free and none can be made.  A new lane is built in a local and counted
-// only once every resource exists.  Running short of memory (or an allocation failing) is not an
-// error of the round: the lane count is capped where it is and the caller waits for a lane to land.
-static int rescue_lane(dpwa_learner *l, int *lane)
-{
-    int rc = free_lane(l, lane);
-    if (rc || *lane >= 0 || l->rescue_lanes >= l->rescue_cap) return rc;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < l->slot_stride + kRescueReserve ||
-        (size_t)(l->rescue_lanes + 1) * l->slot_stride > total_b / kRescueShare) {
-        (void)hipGetLastError();
-        l->rescue_cap = l->rescue_lanes;
-        return DPWA_OK;
-    }
-    RescueLane r;
-    int least = 0, greatest = 0;
-    hipError_t e = r.buf.alloc(l->slot_stride);
-    if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e == hipSuccess) e = r.stream.create(greatest);
-    if (e == hipSuccess) e = r.landed.init();
-    if (e == hipSuccess) e = r.done.init();
-    if (e != hipSuccess) {                // `r` gives back what it made
-        (void)hipGetLastError();          // clear the sticky error: the round goes on without a new lane
-        l->rescue_cap = l->rescue_lanes;
-        return DPWA_OK;
-    }
-    l->rescue[l->rescue_lanes] = std::move(r);
-    *lane = l->rescue_lanes++;
-    return DPWA_OK;
-}
-
-// Gives back the lanes beyond the first kKeepRescueLanes, last first, once idle for kLaneIdleRounds
-// fetch rounds: their pull landed and the last reader of their buffer is done (event queries, no
-// wait).  Called at a round's first pull, the normal path, where it costs one comparison.
-static void trim_lanes(dpwa_learner *l)
-{
-    while (l->rescue_lanes > kKeepRescueLanes) {
-        const int j = l->rescue_lanes - 1;
-        RescueLane &r = l->rescue[j];
-        if (l->fetch_rounds - r.last_round < kLaneIdleRounds || l->src_stage == 2 + j) return;
-        if (r.landed.query() != hipSuccess || r.done.query() != hipSuccess) break;
-        r = RescueLane();
-        l->rescue_lanes--;
-    }
-    (void)hipGetLastError();   // a not-ready query leaves no error behind
-}
-
-// `to` runs on from the point `s` has reached; fetch_state reads ev_issue's time of reaching it
-static hipError_t issue_after(dpwa_learner *l, hipStream_t s, hipStream_t to)
-{
-    const hipError_t e = hipEventRecord(l->ev_issue.h, s);
-    return e == hipSuccess ? hipStreamWaitEvent(to, l->ev_issue.h, 0) : e;
-}
-
-// One snapshot from `peer_slot` into the slot-sized `dst` on `stream`, by the copy engine or the
-// pull kernel (dpwa_learner_set_pull); `timed` takes the next fetch-timing pair, if one is left.
-static int pull_into(dpwa_learner *l, char *dst, const char *peer_slot, bool cross_device, hipStream_t stream,
-                     bool timed)
-{
-    const size_t nbytes = kPayloadOff + round_up(l->payload_bytes, 16);
-    const LaunchTiming *ft = timed ? l->fetch_times.take() : nullptr;
-    if (ft) HIP_TRY(hipEventRecord(ft->start, stream));
-    if (l->pull_mode == DPWA_PULL_KERNEL)
-        HIP_TRY(launch_pull(dst, peer_slot, (int64_t)nbytes, l->pull_blocks, cross_device, stream));
-    else
-        HIP_TRY(hipMemcpyAsync(dst, peer_slot, nbytes, hipMemcpyDefault, stream));
-    if (ft) HIP_TRY(hipEventRecord(ft->stop, stream));
-    return DPWA_OK;
-}
-
-// The fetch in flight reads the snapshot at `src`: in buffer `stage` (src_stage), a copy that
-// `fetched` covers or not, of local peer `owner`'s slot `slot` (NULL, -1: not a local peer's).
-static void set_source(dpwa_learner *l, const char *src, int stage, bool copied, dpwa_learner *owner, int slot)
-{
-    l->src = src;
-    l->src_copied = copied;
-    l->src_stage = stage;
-    l->src_owner = owner;
-    l->src_slot = slot;
-    l->have_fetch = true;
-}
-
 int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int flags, dpwa_stream_t stream)
 {
-    const int zero_copy = flags & DPWA_FETCH_ZERO_COPY;
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_fetch: NULL learner");
     auto it = l->peers.find(peer_id);
     if (it == l->peers.end()) return set_error(DPWA_ERR_ARG, "dpwa_learner_fetch: peer %d not attached", peer_id);
@@ -1212,63 +1045,16 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
         if (std::find(rv.begin(), rv.end(), l) == rv.end()) rv.push_back(l);
     }
     dpwa_learner *const owner = ep.kind == 1 ? ep.local : nullptr;
-    const bool cross_device = ep.kind == 2 || ep.device != l->device;
-    hipStream_t side = l->side.h;
-    l->fetch_issue_ns = now_ns();
-    l->fetch_stream = side;
-    l->issue_evented = false;
-    if (!(flags & DPWA_FETCH_RESCUE)) {
-        l->fetch_rounds++;
-        if (l->rescue_lanes > kKeepRescueLanes) trim_lanes(l);
+    const Pull pull{peer_slot, kPayloadOff + round_up(l->payload_bytes, 16), l->pull_mode, l->pull_blocks,
+                    ep.kind == 2 || ep.device != l->device};
+    if (flags & DPWA_FETCH_RESCUE) return l->fetch.pull_rescue(pull, s, !(flags & DPWA_FETCH_PUBLISHED), owner, k);
+    if ((flags & DPWA_FETCH_ZERO_COPY) && ep.kind == 1 && ep.device == l->device) {
+        l->fetch.read_in_place(peer_slot, owner, k);
+        return DPWA_OK;
     }
-    if (flags & DPWA_FETCH_RESCUE) {
-        // re-selected after a timed-out pull: a free lane (its own stream and buffer), ordered
-        // after the publish of the snapshot (above, local peers) and after the last reader of the
-        // lane's buffer
-        int j = -1;
-        if (int rc = rescue_lane(l, &j)) return rc;
-        if (j < 0)
-            return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: all %d rescue lanes are still pulling",
-                             l->rescue_lanes);
-        RescueLane &r = l->rescue[j];
-        if (!(flags & DPWA_FETCH_PUBLISHED)) {
-            HIP_TRY(issue_after(l, s, r.stream.h));
-            l->issue_evented = true;
-        }
-        HIP_TRY(r.done.wait(r.stream.h));
-        if (int rc = pull_into(l, r.buf.ptr(), peer_slot, cross_device, r.stream.h, false)) return rc;
-        HIP_TRY(r.landed.record(r.stream.h));
-        HIP_TRY(l->fetched.record(r.stream.h));
-        r.last_round = l->fetch_rounds;
-        l->fetch_stream = r.stream.h;
-        set_source(l, r.buf.ptr(), 2 + j, true, owner, k);
-    } else if (zero_copy && ep.kind == 1 && ep.device == l->device) {
-        set_source(l, peer_slot, -1, false, owner, k);   // read in place; stream order covers the rest
-    } else if ((flags & DPWA_FETCH_PUBLISHED) && ep.kind == 2) {
-        if (!l->staging_alt.ptr()) {
-            HIP_TRY(l->staging_alt.alloc(l->slot_stride));
-            HIP_TRY(hipMemsetAsync(l->staging_alt.ptr(), 0, kPayloadOff, side));
-        }
-        const int b = l->stage_next;
-        l->stage_next ^= 1;
-        char *dst = b == 0 ? l->staging.ptr() : l->staging_alt.ptr();
-        // WAR: the average that last read this buffer; nothing else on the caller's stream
-        HIP_TRY(l->stage_done[b].wait(side));
-        if (int rc = pull_into(l, dst, peer_slot, true, side, true)) return rc;
-        HIP_TRY(l->fetched.record(side));
-        set_source(l, dst, b, true, owner, k);
-    } else {
-        HIP_TRY(l->stage_done[0].wait(side));
-        HIP_TRY(issue_after(l, s, side));
-        l->issue_evented = true;
-        // WAR on our own staging buffer: the previous average must have consumed it (the side
-        // stream waits, and now follows `s`, which covers a consumption on itself)
-        HIP_TRY(l->consumed.order(side, s));
-        if (int rc = pull_into(l, l->staging.ptr(), peer_slot, cross_device, side, true)) return rc;
-        HIP_TRY(l->fetched.record(side));
-        set_source(l, l->staging.ptr(), 0, true, owner, k);
-    }
-    return DPWA_OK;
+    // a staging pull takes the next fetch-timing pair, if one is left
+    if ((flags & DPWA_FETCH_PUBLISHED) && ep.kind == 2) return l->fetch.pull_published(pull, l->fetch_times.take(), owner, k);
+    return l->fetch.pull_ordered(pull, l->fetch_times.take(), s, owner, k);
 }
 
 static int relay_materialize(dpwa_learner *l);
@@ -1279,7 +1065,7 @@ static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev
     fa.cfg = l->cfg;
     fa.clock_in = &l->ctl->clock[l->cur];
     fa.clock_out = &l->ctl->clock[(l->cur + 1) & 3];
-    fa.hdr = (const dpwa_header *)l->src;
+    fa.hdr = (const dpwa_header *)l->fetch.source().ptr;
     fa.loss_h = loss;
     fa.loss_d = loss_dev;
     fa.loss_f32 = l->loss_f32 ? 1 : 0;
@@ -1288,46 +1074,27 @@ static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev
     return fa;
 }
 
-// Everything enqueued on `s` so far has read the fetch source: a staging buffer or lane may be
-// refilled once `s` gets here (recorded now: refills run elsewhere); so may the source itself.
-static hipError_t note_consumed(dpwa_learner *l, hipStream_t s)
-{
-    hipError_t e = hipSuccess;
-    if (l->src_stage >= 0 && l->src_copied)
-        e = l->src_stage >= 2 ? l->rescue[l->src_stage - 2].done.record(s) : l->stage_done[l->src_stage].record(s);
-    if (e == hipSuccess) l->consumed.note(s);
-    return e;
-}
-
 int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dpwa_stream_t stream)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_factor: NULL learner");
-    if (!l->have_fetch) return set_error(DPWA_ERR_STATE, "dpwa_learner_factor: no fetch in flight");
-    if (l->have_factor) return set_error(DPWA_ERR_STATE, "dpwa_learner_factor: factor already computed for this fetch");
+    if (!l->fetch.fetched()) return set_error(DPWA_ERR_STATE, "dpwa_learner_factor: no fetch in flight");
+    if (l->fetch.factored()) return set_error(DPWA_ERR_STATE, "dpwa_learner_factor: factor already computed for this fetch");
     if (int rc = need_layout(l, "dpwa_learner_factor")) return rc;
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = relay_materialize(l)) return rc;
-    if (l->src_copied) HIP_TRY(l->fetched.wait(s));   // TxThread.fetch_wait
+    HIP_TRY(l->fetch.wait_landed(s));
     HIP_TRY(launch_factor(fused_args(l, loss, loss_dev), s));
     HIP_TRY(l->factor_done.record(s));
-    HIP_TRY(note_consumed(l, s));   // the header has been read on s: a later pull into this buffer waits for it
+    HIP_TRY(l->fetch.factored_on(s));   // the header has been read on s: a later pull into this buffer waits for it
     l->cur = (l->cur + 1) & 3;
-    l->have_factor = true;
     return DPWA_OK;
-}
-
-static void finish_fetch(dpwa_learner *l)
-{
-    l->have_fetch = false;
-    l->have_factor = false;
-    l->src = nullptr;
 }
 
 int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
 {
     if (!l || (!flat && l->n > 0)) return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: NULL argument");
-    if (!l->have_factor) return set_error(DPWA_ERR_STATE, "dpwa_learner_lerp: no factor computed for this fetch");
+    if (!l->fetch.factored()) return set_error(DPWA_ERR_STATE, "dpwa_learner_lerp: no factor computed for this fetch");
     if (l->resident)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_lerp: a resident learner averages with dpwa_learner_average");
     DeviceGuard dg(l->device);
@@ -1335,7 +1102,7 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     if (l->dtype == DPWA_MIXED && !aligned16(flat))   // (its layout is known: the factor was computed)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
     if (int rc = l->measure.operands_problem("dpwa_learner_lerp", flat)) return rc;
-    const Measured m{&l->measure, payload(l), flat, l->src + kPayloadOff, nullptr};
+    const Measured m{&l->measure, payload(l), flat, l->fetch.source().ptr + kPayloadOff, nullptr};
     int rc = measured_average(&m, 1, s, [&]() -> int {
         if (l->dtype == DPWA_MIXED) {
             HIP_TRY(launch_lerp_mixed(l->layout, flat, m.peer, &l->ctl->coef, s));
@@ -1345,9 +1112,9 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
         return DPWA_OK;
     });
     if (rc) return rc;
-    HIP_TRY(note_consumed(l, s));
+    HIP_TRY(l->fetch.note_consumed(s));
     l->written_through.clear();
-    finish_fetch(l);
+    l->fetch.finish();
     return DPWA_OK;
 }
 
@@ -1369,7 +1136,7 @@ struct AvgPlan {
 static int average_prepare(dpwa_learner *l, void *flat, double loss, const double *loss_dev, hipStream_t s,
                            bool write_through, AvgPlan &p)
 {
-    if (!l->have_fetch || l->have_factor) return set_error(DPWA_ERR_STATE, "dpwa_learner_average: no fetch in flight");
+    if (!l->fetch.fetched() || l->fetch.factored()) return set_error(DPWA_ERR_STATE, "dpwa_learner_average: no fetch in flight");
     if (int rc = need_layout(l, "dpwa_learner_average")) return rc;
     if (l->dtype == DPWA_MIXED && !aligned16(flat))
         return set_error(DPWA_ERR_ARG, "dpwa_learner_average: a segmented payload is 16-byte aligned");
@@ -1404,13 +1171,12 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
         // the relay's phase 2 fused into the average: stripes read where phase 1 left them
         const RelayArgs &a = l->relay_saved;
         p.fa.hdr = (const dpwa_header *)(a.slots[l->relay_saved_pick] + a.slot_off);
-        HIP_TRY(l->fetched.wait(s));
         p.relay = true;
     } else {
         if (int rc = relay_materialize(l)) return rc;
-        if (l->src_copied) HIP_TRY(l->fetched.wait(s));   // TxThread.fetch_wait
-        p.peer = l->src + kPayloadOff;
+        p.peer = l->fetch.source().ptr + kPayloadOff;
     }
+    HIP_TRY(l->fetch.wait_landed(s));
     return DPWA_OK;
 }
 
@@ -1424,16 +1190,16 @@ static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
     if (p.relay) {
         HIP_TRY(l->relay_done.record(s));   // the next round's barrier waits for these reads
         l->relay_deferred = false;
-        l->consumed.note(s);   // the stripes were read where phase 1 left them: no staging buffer
+        l->fetch.note_consumed_in_place(s);
     } else {
-        HIP_TRY(note_consumed(l, s));
+        HIP_TRY(l->fetch.note_consumed(s));
     }
     l->timing_armed = false;
     l->cur = (l->cur + 1) & 3;
     if (p.oop) l->res_slot = p.snap_slot;   // the parameters moved into the next publish's slot
     set_written_through(l, p.oop ? p.snap : p.flat, p.fa.next_header != nullptr, s);
     if (!p.write_through) l->written_through.clear();
-    finish_fetch(l);
+    l->fetch.finish();
     return DPWA_OK;
 }
 
@@ -1695,7 +1461,7 @@ int dpwa_learner_set_resident(dpwa_learner *l, const void *init, dpwa_stream_t s
 {
     if (!l || (!init && l->n > 0)) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_resident: NULL argument");
     if (l->resident) return set_error(DPWA_ERR_STATE, "dpwa_learner_set_resident: already resident");
-    if (l->version != 0 || l->have_fetch)
+    if (l->version != 0 || l->fetch.fetched())
         return set_error(DPWA_ERR_STATE, "dpwa_learner_set_resident: only before the first publish");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
@@ -1720,7 +1486,7 @@ int dpwa_learner_resident_params(dpwa_learner *l, void **params, int *slot)
 int dpwa_learner_relocate(dpwa_learner *l, dpwa_stream_t stream)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_relocate: NULL learner");
-    if (l->have_fetch) return set_error(DPWA_ERR_STATE, "dpwa_learner_relocate: a fetch is in flight (average it)");
+    if (l->fetch.fetched()) return set_error(DPWA_ERR_STATE, "dpwa_learner_relocate: a fetch is in flight (average it)");
     DeviceGuard dg(l->device);
     return relocate_impl(l, (hipStream_t)stream);
 }
@@ -1807,7 +1573,7 @@ int dpwa_learner_fetch_host(dpwa_learner *l, const void *header, const void *pay
     // records stage_done), not for all the work queued on the caller's stream: it starts
     // at once, beside a training step already enqueued.
     hipStream_t side = l->side.h;
-    HIP_TRY(l->stage_done[0].wait(side));
+    HIP_TRY(l->fetch.staging_writable());
     // Pageable host sources: the calls return once the host bytes have been taken.  A
     // page-locked source is copied asynchronously, so the copy is waited for: either way the
     // caller may reuse its buffer when this returns.
@@ -1815,13 +1581,12 @@ int dpwa_learner_fetch_host(dpwa_learner *l, const void *header, const void *pay
     const bool pinned = payload_bytes > 0 && hipPointerGetAttributes(&attr, payload) == hipSuccess &&
                         attr.type == hipMemoryTypeHost;
     (void)hipGetLastError();   // a pageable pointer is "invalid" to hipPointerGetAttributes
-    HIP_TRY(hipMemcpyAsync(l->staging.ptr(), header, kHeader, hipMemcpyHostToDevice, side));
+    HIP_TRY(hipMemcpyAsync(l->fetch.staging(), header, kHeader, hipMemcpyHostToDevice, side));
     if (payload_bytes)
-        HIP_TRY(hipMemcpyAsync(l->staging.ptr() + kPayloadOff, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, side));
-    HIP_TRY(l->fetched.record(side));
-    if (pinned) HIP_TRY(hipEventSynchronize(l->fetched.event()));
-    set_source(l, l->staging.ptr(), 0, true, nullptr, -1);
-    l->have_factor = false;
+        HIP_TRY(hipMemcpyAsync(l->fetch.staging() + kPayloadOff, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, side));
+    HIP_TRY(l->fetch.landed_on_side());
+    if (pinned) HIP_TRY(l->fetch.host_wait_landed());
+    l->fetch.arrived_in_staging();
     return DPWA_OK;
 }
 
@@ -1919,7 +1684,7 @@ static int relay_args(dpwa_learner *l, const int32_t *picks_dev, uint64_t versio
         a.relays[r] = l->relay_bufs[r];
     }
     a.relay_mine = l->relay_mem.ptr;
-    a.staging = l->staging.ptr();
+    a.staging = l->fetch.staging();
     a.picks = picks_dev;
     a.slot_off = (int64_t)((version - 1) % 2) * (int64_t)l->slot_stride;
     a.stripe = l->relay_stripe;
@@ -1947,8 +1712,7 @@ int dpwa_learner_relay_phase1(dpwa_learner *l, const int32_t *picks_dev, uint64_
     RelayArgs a;
     if (int rc = relay_args(l, picks_dev, version, a)) return rc;
     DeviceGuard dg(l->device);
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(issue_after(l, s, l->side.h));
+    HIP_TRY(l->fetch.side_after((hipStream_t)stream));
     HIP_TRY(launch_relay(1, a, blocks, l->side.h));
     HIP_TRY(l->relay_done.record(l->side.h));
     return DPWA_OK;
@@ -1958,14 +1722,10 @@ int dpwa_learner_relay_phase1(dpwa_learner *l, const int32_t *picks_dev, uint64_
 static int relay_phase2_now(dpwa_learner *l, const RelayArgs &a, int my_pick, int blocks)
 {
     hipStream_t side = l->side.h;
-    if (my_pick >= 0) {   // WAR on staging
-        // covered_by = nullptr: a consumption on the default stream is indistinguishable from "never"
-        HIP_TRY(l->consumed.order(side, nullptr));
-        HIP_TRY(l->stage_done[0].wait(side));
-    }
+    if (my_pick >= 0) HIP_TRY(l->fetch.staging_writable_after_consumption());   // WAR on staging
     HIP_TRY(launch_relay(2, a, blocks, side));
     HIP_TRY(l->relay_done.record(side));
-    if (my_pick >= 0) HIP_TRY(l->fetched.record(side));
+    if (my_pick >= 0) HIP_TRY(l->fetch.landed_on_side());
     return DPWA_OK;
 }
 
@@ -2002,7 +1762,7 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
     l->relay_deferred = false;
     if (fuse && my_pick >= 0) {
         // everything the fused average needs is on the side stream now (phase 1, the barrier)
-        HIP_TRY(l->fetched.record(l->side.h));
+        HIP_TRY(l->fetch.landed_on_side());
         l->relay_saved = a;
         l->relay_saved_pick = my_pick;
         l->relay_saved_blocks = blocks;
@@ -2010,10 +1770,7 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
     } else if (!fuse || my_pick >= 0) {
         if ((rc = relay_phase2_now(l, a, my_pick, blocks))) return rc;
     }
-    if (my_pick >= 0) {
-        set_source(l, l->staging.ptr(), 0, true, nullptr, -1);
-        l->have_factor = false;
-    }
+    if (my_pick >= 0) l->fetch.arrived_in_staging();
     return DPWA_OK;
 }
 
@@ -2070,10 +1827,10 @@ int dpwa_learner_side_stream(dpwa_learner *l, dpwa_stream_t *stream)
 int dpwa_learner_wait_fetch(dpwa_learner *l, dpwa_stream_t stream)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_wait_fetch: NULL learner");
-    if (l->have_fetch && l->src_copied) {
+    if (l->fetch.awaits_copy()) {
         DeviceGuard dg(l->device);
         if (int rc = relay_materialize(l)) return rc;
-        HIP_TRY(l->fetched.wait((hipStream_t)stream));
+        HIP_TRY(l->fetch.wait_landed((hipStream_t)stream));
     }
     return DPWA_OK;
 }
@@ -2106,43 +1863,14 @@ int dpwa_learner_copy_factor(dpwa_learner *l, double *dst_dev, dpwa_stream_t str
 int dpwa_learner_copy_fetched(dpwa_learner *l, void *dst_dev, dpwa_stream_t stream)
 {
     if (!l || (!dst_dev && l->n > 0)) return set_error(DPWA_ERR_ARG, "dpwa_learner_copy_fetched: NULL argument");
-    if (!l->have_fetch || !l->src) return set_error(DPWA_ERR_STATE, "dpwa_learner_copy_fetched: no fetch in flight");
+    if (!l->fetch.fetched()) return set_error(DPWA_ERR_STATE, "dpwa_learner_copy_fetched: no fetch in flight");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = relay_materialize(l)) return rc;
-    if (l->src_copied) HIP_TRY(l->fetched.wait(s));
+    HIP_TRY(l->fetch.wait_landed(s));
     if (l->payload_bytes)
-        HIP_TRY(hipMemcpyAsync(dst_dev, l->src + kPayloadOff, l->payload_bytes, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(note_consumed(l, s));   // a later pull into this staging buffer waits for this copy
-    return DPWA_OK;
-}
-
-// Milliseconds since the (completed, timing) event `since`, on the device's clock: an event
-// recorded now on the probe stream -- a stream that holds nothing else -- and the two timestamps'
-// difference.  DPWA_ERR_STATE when the probe does not complete within kProbeWaitUs (its hardware
-// queue is held up by another stream mapped to it: no measurement).  The probe stream has the
-// normal priority: the greatest-priority hardware queues are left to the rescue lanes (streams are
-// dealt round-robin onto a few queues per priority, so a probe there would push a lane onto a
-// queue another lane already uses).
-static int probe_since(dpwa_learner *l, hipEvent_t since, float *ms)
-{
-    if (!l->probe.stream.h) {
-        Probe p;
-        hipError_t e = p.stream.create();
-        if (e == hipSuccess) e = p.ev.init(hipEventDefault);
-        if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "probe stream: %s", hipGetErrorString(e));
-        l->probe = std::move(p);
-    }
-    const hipEvent_t ev_probe = l->probe.ev.h;
-    HIP_TRY(hipEventRecord(ev_probe, l->probe.stream.h));
-    const int64_t t0 = now_ns();
-    for (;;) {
-        const hipError_t q = hipEventQuery(ev_probe);
-        if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(q));
-        if (now_ns() - t0 > kProbeWaitUs * 1000) return set_error(DPWA_ERR_STATE, "probe held up");
-    }
-    HIP_TRY(hipEventElapsedTime(ms, since, ev_probe));
+        HIP_TRY(hipMemcpyAsync(dst_dev, l->fetch.source().ptr + kPayloadOff, l->payload_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(l->fetch.note_consumed(s));   // a later pull into this staging buffer waits for this copy
     return DPWA_OK;
 }
 
@@ -2150,32 +1878,9 @@ int dpwa_learner_fetch_state(dpwa_learner *l, int64_t timeout_ms, int *state)
 {
     if (!l || !state) return set_error(DPWA_ERR_ARG, "dpwa_learner_fetch_state: NULL argument");
     *state = DPWA_FETCH_LANDED;
-    if (!l->have_fetch || !l->src_copied || l->relay_deferred) return DPWA_OK;
+    if (!l->fetch.awaits_copy() || l->relay_deferred) return DPWA_OK;   // (no device call)
     DeviceGuard dg(l->device);
-    const hipError_t e = l->fetched.query();
-    if (e == hipSuccess) return DPWA_OK;
-    if (e != hipErrorNotReady) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
-    *state = DPWA_FETCH_IN_FLIGHT;
-    if (timeout_ms < 0) return DPWA_OK;
-    // The host's enqueue is an upper bound on how long the request has been out: within the
-    // timeout by it, the pull is in time.  Past it, a pull ordered after the caller's stream
-    // (ev_issue: a local peer's snapshot) is timed from when that stream reached update_send --
-    // the reference's socket timeout bounds only the wait for the reply (conn.py:249), and work the
-    // caller queued before update_send is not the peer's delay.
-    const int64_t waited_ns = now_ns() - l->fetch_issue_ns;
-    if (waited_ns < timeout_ms * 1000000LL) return DPWA_OK;
-    if (l->issue_evented && waited_ns < (timeout_ms + kMaxBacklogMs) * 1000000LL) {
-        const hipError_t q = hipEventQuery(l->ev_issue.h);
-        if (q == hipErrorNotReady) return DPWA_OK;        // the request has not gone out yet
-        if (q != hipSuccess) return set_error(DPWA_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(q));
-        float ms = 0.f;
-        if (probe_since(l, l->ev_issue.h, &ms) == DPWA_OK && ms >= 0.f) {
-            *state = ms >= (float)timeout_ms ? DPWA_FETCH_TIMED_OUT : DPWA_FETCH_IN_FLIGHT;
-            return DPWA_OK;
-        }
-    }
-    *state = DPWA_FETCH_TIMED_OUT;
-    return DPWA_OK;
+    return l->fetch.state(timeout_ms, l->relay_deferred, state);
 }
 
 int dpwa_learner_rescue_free(dpwa_learner *l, int *free_out)
@@ -2185,7 +1890,7 @@ int dpwa_learner_rescue_free(dpwa_learner *l, int *free_out)
     int lane = -1;
     // makes a lane now if one is needed and can be made: at most one allocation per wait (the
     // node's poll ends as soon as a lane is free); with the lanes at their cap a poll only queries
-    const int rc = rescue_lane(l, &lane);
+    const int rc = l->fetch.lanes().acquire(l->slot_stride, &lane);
     *free_out = lane >= 0 ? 1 : 0;
     return rc;
 }
@@ -2193,22 +1898,22 @@ int dpwa_learner_rescue_free(dpwa_learner *l, int *free_out)
 int dpwa_learner_rescue_lanes(dpwa_learner *l, int *lanes, int *cap)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_rescue_lanes: NULL learner");
-    if (lanes) *lanes = l->rescue_lanes;
-    if (cap) *cap = l->rescue_cap;
+    if (lanes) *lanes = l->fetch.lanes().count();
+    if (cap) *cap = l->fetch.lanes().cap();
     return DPWA_OK;
 }
 
 int dpwa_learner_set_rescue_cap(dpwa_learner *l, int cap)
 {
     if (!l || cap < 0) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_rescue_cap: bad arguments");
-    l->rescue_cap = std::min(std::max(cap, l->rescue_lanes), kMaxRescueLanes);
+    l->fetch.lanes().set_cap(cap);
     return DPWA_OK;
 }
 
 int dpwa_learner_fetch_stream(dpwa_learner *l, dpwa_stream_t *stream)
 {
     if (!l || !stream) return set_error(DPWA_ERR_ARG, "dpwa_learner_fetch_stream: NULL argument");
-    *stream = l->fetch_stream ? l->fetch_stream : l->side.h;
+    *stream = l->fetch.stream();
     return DPWA_OK;
 }
 
@@ -2216,7 +1921,7 @@ int dpwa_learner_cancel(dpwa_learner *l)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_cancel: NULL learner");
     l->relay_deferred = false;   // nothing reads the stripes: no gather
-    finish_fetch(l);
+    l->fetch.finish();
     return DPWA_OK;
 }
 
@@ -2226,8 +1931,8 @@ int dpwa_learner_pointers(dpwa_learner *l, double **clock_dev, dpwa_coef **coef_
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_pointers: NULL learner");
     if (clock_dev) *clock_dev = &l->ctl->clock[l->cur];
     if (coef_dev) *coef_dev = &l->ctl->coef;
-    if (staging_header_dev) *staging_header_dev = (dpwa_header *)l->staging.ptr();
-    if (staging_payload_dev) *staging_payload_dev = l->staging.ptr() + kPayloadOff;
+    if (staging_header_dev) *staging_header_dev = (dpwa_header *)l->fetch.staging();
+    if (staging_payload_dev) *staging_payload_dev = l->fetch.staging() + kPayloadOff;
     return DPWA_OK;
 }
 

@@ -40,6 +40,12 @@ struct DevBuf : Owned<void *, hipFree> {
     char *ptr() const { return (char *)h; }
 };
 
+// A non-blocking stream.
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+    hipError_t create() { return hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+    hipError_t create(int priority) { return hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority); }
+};
+
 // An event made by init() or at first need; hipEventDefault for one whose timestamp is read.
 struct Event : Owned<hipEvent_t, hipEventDestroy> {
     hipError_t init(unsigned flags = hipEventDisableTiming) { return h ? hipSuccess : hipEventCreateWithFlags(&h, flags); }

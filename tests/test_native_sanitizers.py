@@ -107,6 +107,36 @@ def test_measurements_around_an_average_under_asan_ubsan(tmp_path):
     assert "measure check ok" in r.stdout
 
 
+def test_fetch_in_flight_and_rescue_lanes_under_asan_ubsan(tmp_path):
+    """fetch.hpp's Fetch and RescueLanes -- the snapshot a learner is about to average with, the buffer it
+    lands in, who waits for it and when the buffer may be refilled -- against recording stand-ins of every
+    HIP call they and order.hpp make, of launch_pull and of the host clock (tests/native/fetch_check.cpp,
+    which links no HIP runtime).  The exact calls of: the ordered staging pull (first round without a wait;
+    after a consumption on the caller's stream, on a third stream; a timing pair around the pull kernel);
+    the published pull (the second buffer made and cleared once, buffers 0 1 0 1 each waiting for its own
+    done, ev_issue never recorded and state() never probing); the in-place read (no call at all); the
+    rescue pull (how a lane is made, untimed, lane 1 while lane 0 pulls, lane 0 again once landed and after
+    its done, no lane at the cap, none recorded for a published snapshot); the memory budget one byte
+    either side of the reserve and the share, a failing hipMalloc, a stream that cannot be made after the
+    buffer, the cap staying where a failure put it, set_cap's clamp; the trim (7 and 8 rounds idle, the
+    source's lane, a pull or a reader not done, lanes 3 then 2 released and two kept); note_consumed per
+    kind of source; the phase through pull, factor, a second pull, the host and relay arrivals, finish;
+    every branch of state() by the check's clock.  Every stream, event and allocation is given back once."""
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    cxx = os.path.join(rocm, "lib", "llvm", "bin", "clang++")
+    if not os.path.exists(cxx):
+        pytest.skip("no ROCm clang++")
+    exe = str(tmp_path / "fetch_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", *SAN, "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+           os.path.join(ROOT, "tests/native/fetch_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "fetch check ok" in r.stdout
+
+
 def _tsan_build(tmp_path):
     gxx = shutil.which("g++")
     if gxx is None:
