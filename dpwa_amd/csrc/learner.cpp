@@ -1088,6 +1088,9 @@ int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dp
     HIP_TRY(l->factor_done.record(s));
     HIP_TRY(l->fetch.factored_on(s));   // the header has been read on s: a later pull into this buffer waits for it
     l->cur = (l->cur + 1) & 3;
+    // A header that a write-through average wrote ahead carries that average's clock, and the clock it
+    // wrote ahead lay in the ring place this factor has just written: the next publish writes both anew
+    l->wt_header = false;   // (as dpwa_learner_write_clock does, for the same reason)
     return DPWA_OK;
 }
 

@@ -561,7 +561,10 @@ int dpwa_learner_resident_params(dpwa_learner *l, void **params, int *slot);
 int dpwa_learner_relocate(dpwa_learner *l, dpwa_stream_t stream);
 
 /* Split form of dpwa_learner_average for the DpwaConnection / adapter seam:
- * factor only (update_wait's return value), then lerp with the learner's coefficients. */
+ * factor only (update_wait's return value), then lerp with the learner's coefficients.
+ * A factor computed while a write-through average's snapshot still awaits its publish moves the clock
+ * that the header written ahead was made from: the reusing publish then writes the header anew from the
+ * live clock (one small kernel), as after dpwa_learner_write_clock. */
 int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dpwa_stream_t stream);
 int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream);
 
