@@ -19,14 +19,45 @@ averaged one launch each instead of one batched dispatch.
 """
 import ctypes
 import logging
+import weakref
 
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from .. import _lib
 from ..dpwa import DpwaConfiguration, DpwaConnection
 from ..flat import FlatParameters
 
 LOGGER = logging.getLogger(__name__)
+
+# One process-wide optimizer hook (torch.optim's step post hook) tells every open adapter that an
+# optimizer holding one of its parameters has stepped: the fused optimizers (``fused=True``) change
+# the parameters and move no version counter.
+_OPEN = weakref.WeakSet()
+_HOOK = []
+
+
+def _optimizer_stepped(optimizer, args, kwargs):
+    if not _OPEN:               # every adapter was closed or collected: the hook goes too
+        while _HOOK:
+            _HOOK.pop().remove()
+        return
+    for adapter in _OPEN:
+        if not adapter._stepped and adapter._holds(optimizer):
+            adapter._stepped = True
+
+
+def _watch(adapter):
+    _OPEN.add(adapter)
+    if not _HOOK:
+        _HOOK.append(register_optimizer_step_post_hook(_optimizer_stepped))
+
+
+def _unwatch(adapter):
+    _OPEN.discard(adapter)
+    if not _OPEN:
+        while _HOOK:
+            _HOOK.pop().remove()
 
 
 class DpwaPyTorchAdapter:
@@ -37,8 +68,16 @@ class DpwaPyTorchAdapter:
     and examples/pytorch-cifar/main.py:130-145: update_send, forward/backward/step, update_wait).
     Before reusing a snapshot the adapter checks that no parameter was re-homed
     (``param.data = ...``), that no parameter's version counter moved (optimizer steps,
-    ``param.add_``, ``load_state_dict``) and that the flat buffer's own counter did not move;
-    any of these forces a full publish.  In-place writes through ``param.data`` bypass version
+    ``param.add_``, ``load_state_dict``), that the flat buffer's own counter did not move, that no
+    optimizer holding one of the parameters stepped (torch.optim's global step hook: the fused
+    optimizers, ``fused=True``, change the parameters and move no version counter) and that the
+    module still holds the ``Parameter`` objects the flat buffer was built from
+    (``load_state_dict(assign=True)`` and ``mod.weight = nn.Parameter(...)`` put others there: they
+    are taken into the buffer when names, shapes and dtypes are unchanged, else DpwaError names
+    the parameter; a model whose structure changes needs a new adapter); any of these forces a
+    full publish.  update_wait makes the same two checks of storage and objects first, so it
+    averages what the module holds at that call (pytorch.py:60-68 walks ``named_parameters()``
+    again).  In-place writes through ``param.data`` bypass version
     counters; for them the reuse guard (``reuse_guard``, on by default) compares 4096 16-byte
     words spread over the parameters with the snapshot on the device and publishes in full when
     any differs (two small kernels per update_send, no host sync).  The sampled words move on by
@@ -59,7 +98,8 @@ class DpwaPyTorchAdapter:
     default write-through form; a resident adapter needs update_send, update_wait, step (each
     step then comes after the round's average instead of before it).  update_wait raises
     DpwaError when a parameter's (or the flat buffer's) version counter moved since update_send
-    -- an optimizer step, ``param.add_``, ``load_state_dict`` in the window.  Writes through
+    -- an optimizer step, ``param.add_``, ``load_state_dict`` in the window -- or an optimizer
+    stepped there without moving one (``fused=True``).  Writes through
     ``param.data`` bypass version counters; for them the reuse guard (``reuse_guard``) is a window
     guard here: every update_send runs one small kernel that compares the parameters published at
     the previous update_send with 4096 words sampled then, and samples the new ones (no host
@@ -108,6 +148,53 @@ class DpwaPyTorchAdapter:
         self._versions = None
         self._sent = None           # resident: the version counters at the last update_send
         self._warned_rehome = False
+        self._stepped = False       # an optimizer holding a parameter stepped since the last average
+        self._optimizers = weakref.WeakKeyDictionary()     # optimizer -> (its parameter count, holds one of ours)
+        self._take_slots()
+        _watch(self)
+
+    def _take_slots(self):
+        """Where the module keeps each parameter: the submodule's ``_parameters`` dict, the key, and
+        the object's id.  A Parameter object put in another one's place
+        (``load_state_dict(assign=True)``, ``mod.weight = nn.Parameter(...)``) shows as a slot that
+        holds another object; reading the slots costs a small part of a ``named_parameters()`` walk."""
+        slots = [(m._parameters, k, p) for m in self._net.modules() for k, p in m._parameters.items() if p is not None]
+        self._slot_dicts = [d for d, _, _ in slots]
+        self._slot_keys = [k for _, k, _ in slots]
+        self._slot_ids = [id(p) for _, _, p in slots]
+        self._ids = {id(p) for p in self._flat.params}
+        self._optimizers.clear()
+
+    def _holds(self, optimizer):
+        groups = optimizer.param_groups
+        count = sum(len(g["params"]) for g in groups)
+        known = self._optimizers.get(optimizer)
+        if known is None or known[0] != count:
+            ids = self._ids
+            known = self._optimizers[optimizer] = (count, any(id(p) in ids for g in groups for p in g["params"]))
+        return known[1]
+
+    def _fold(self):
+        """The module's parameters as they are now, into the flat buffer: Parameter objects that were
+        replaced are adopted (or DpwaError names the one that does not fit), replaced ``.data`` is
+        re-homed.  Returns how many tensors were copied in."""
+        try:
+            if list(map(id, map(dict.__getitem__, self._slot_dicts, self._slot_keys))) == self._slot_ids:
+                return self._flat.resync()
+        except KeyError:        # a parameter was deleted from its module
+            pass
+        try:
+            taken = self._flat.adopt(self._net.named_parameters())
+        except ValueError as e:
+            raise _lib.DpwaError("DpwaPyTorchAdapter", _lib.ERR_STATE, str(e)) from None
+        self._take_slots()
+        self._versions = None
+        return taken + self._flat.resync()
+
+    def close(self):
+        """Closes the connection and stops watching optimizer steps for this adapter."""
+        _unwatch(self)
+        self._conn.close()
 
     def _warn_rehome(self, moved):
         """Once per adapter: the caller re-homed a parameter (``param.data = ...``), so its loop
@@ -133,7 +220,7 @@ class DpwaPyTorchAdapter:
     def _check_window(self):
         """Resident form: nothing may have written the parameters since update_send (they are
         the snapshot peers read until the average)."""
-        if self._sent is not None and self._param_versions() != self._sent:
+        if self._sent is not None and (self._stepped or self._param_versions() != self._sent):
             raise _lib.DpwaError(
                 "DpwaPyTorchAdapter.update_wait", _lib.ERR_STATE,
                 "the parameters were modified between update_send and update_wait (an optimizer step?); "
@@ -155,17 +242,18 @@ class DpwaPyTorchAdapter:
                 self._flat.rehome(self._conn.make_resident(self._flat.buffer))
                 if self._reuse_guard:                      # the window guard (see the class doc)
                     _lib.call("dpwa_learner_set_reuse_guard", self._conn._learner.handle, 1)
-            self._flat.resync()                        # a parameter re-homed by the caller
+            self._fold()                               # a parameter re-homed or replaced by the caller
             self._conn.update_send(self._flat.buffer, loss)
             # a publish with no average since the last one moved the parameters into the slot it
             # published (dpwa_learner_relocate): the views follow them
             self._flat.rehome(self._conn.parameters)
             self._sent = self._param_versions()
+            self._stepped = False
             return
-        moved = self._flat.resync()
+        moved = self._fold()
         if moved and self._write_through and not self._warned_rehome:
             self._warn_rehome(moved)
-        reuse = (self._write_through and moved == 0 and self._versions is not None
+        reuse = (self._write_through and moved == 0 and not self._stepped and self._versions is not None
                  and self._versions == self._param_versions())
         self._versions = None
         self._conn.update_send(self._flat.buffer, loss, reuse_snapshot=reuse)
@@ -190,9 +278,11 @@ class DpwaPyTorchAdapter:
             self._flat.rehome(self._conn.parameters)
             self._sent = None
             return
+        self._fold()           # what the module holds now is averaged (pytorch.py:60-68 walks it again)
         payload, _ = self._conn.update_wait_average(self._flat.buffer, loss, write_through=self._write_through)
         if self._write_through and payload is not None:
             self._versions = self._param_versions()
+            self._stepped = False
 
     # -- extensions -------------------------------------------------------------------
     @staticmethod
@@ -213,6 +303,9 @@ class DpwaPyTorchAdapter:
         if resident:
             for a in adapters:
                 a._check_window()
+        else:
+            for a in adapters:
+                a._fold()
         res = DpwaConnection.update_wait_average_many([a._conn for a in adapters],
                                                       [a._flat.buffer for a in adapters], list(losses),
                                                       write_through=wt)
@@ -222,6 +315,7 @@ class DpwaPyTorchAdapter:
                 a._sent = None
             elif wt and payload is not None:
                 a._versions = a._param_versions()
+                a._stepped = False
 
     def state_dict(self):
         """The connection's gossip state (clock, scheduler) for a checkpoint beside the model's

@@ -16,6 +16,7 @@ on a 4096-byte boundary and zero-filled up to a multiple of 4096 bytes, so that 
 ``torch.uint8`` tensor, every ``param.data`` a typed view into it, and ``layout`` says which bytes
 hold which dtype (include/dpwa_hip.h ``dpwa_layout``).
 """
+import itertools
 import struct
 
 import torch
@@ -24,6 +25,7 @@ from . import _lib
 
 ALIGN_BYTES = 256
 SEGMENT_BYTES = 4096          # DPWA_LAYOUT_ALIGN
+_DATA_PTR = torch.Tensor.data_ptr
 # the segments' order, and their codes in a dpwa_layout
 SEGMENT_DTYPES = ((torch.float32, _lib.F32), (torch.bfloat16, _lib.BF16), (torch.float16, _lib.F16))
 
@@ -174,7 +176,7 @@ class FlatParameters:
     def resync(self):
         """Re-homes parameters whose ``.data`` was replaced since the last call (e.g. a
         user assigned ``param.data = ...``); returns the number re-homed."""
-        if [p.data_ptr() for p in self.params] == self._ptrs:
+        if list(map(_DATA_PTR, self.params)) == self._ptrs:
             return 0          # the common case: one pointer read per parameter
         moved = 0
         with torch.no_grad():
@@ -187,6 +189,42 @@ class FlatParameters:
                     self._ptrs[i] = p.data_ptr()
                     moved += 1
         return moved
+
+    def adopt(self, named_parameters):
+        """The module holds other ``Parameter`` objects than the ones this buffer was built from
+        (``load_state_dict(..., assign=True)``, ``module.weight = nn.Parameter(...)``): takes the
+        module's objects in their place -- their values copied into the buffer, their ``.data`` a view
+        of it -- when the names, shapes and dtypes are unchanged, and returns how many were taken.
+        The objects left behind get storage of their own, so whoever still holds one (an optimizer
+        created before) no longer writes the buffer through it.  Raises ValueError naming the first
+        parameter that does not fit."""
+        new = list(named_parameters)
+        names = [name for name, _ in new]
+        if names != self.names:
+            odd = next(a or b for a, b in itertools.zip_longest(names, self.names) if a != b)
+            raise ValueError("the module's parameters are no longer the ones the flat buffer was built from "
+                             "(at %r): a model whose structure changed needs a new adapter" % odd)
+        for i, (name, p) in enumerate(new):
+            dtype = self.dtype if self.layout is None else self._pdtypes[i]
+            if p is not self.params[i] and (p.shape != self.params[i].shape or p.dtype != dtype):
+                raise ValueError("parameter %r was replaced by one of shape %s and dtype %s (the flat buffer holds "
+                                 "%s, %s): a model whose structure changed needs a new adapter"
+                                 % (name, tuple(p.shape), p.dtype, tuple(self.params[i].shape), dtype))
+        taken = 0
+        with torch.no_grad():
+            for i, (_, p) in enumerate(new):
+                old = self.params[i]
+                if p is old:
+                    continue
+                if old.data_ptr() == self._ptrs[i]:
+                    old.data = old.data.clone()
+                self.params[i] = p
+                home = self._view(self.buffer, i)
+                home.reshape(-1).copy_(p.data.reshape(-1))
+                p.data = home
+                self._ptrs[i] = p.data_ptr()
+                taken += 1
+        return taken
 
     def parameter_ranges(self):
         """``[(name, torch dtype, byte offset, byte length)]`` in ``named_parameters()`` order: where

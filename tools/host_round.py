@@ -3,7 +3,9 @@
 round: update_send(reuse_snapshot) + update_wait_average(write_through)) and the adapter's round,
 on a parameter small enough (--numel, default 4,096) that the device never holds the host back,
 so wall time per round = the host's issue time.  Also each call alone (perf_counter around it).
-Prints one JSON line."""
+--tensors T gives the adapter's model T parameter tensors of numel/T elements each (62 is ResNet-18's
+count): what the adapter does per tensor on every call -- the version counters, the data pointers,
+the module's slots -- then shows.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -25,6 +27,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--numel", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=5000)
+    ap.add_argument("--tensors", type=int, default=1)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     tmp = tempfile.mkdtemp(prefix="dpwa_host_")
@@ -32,7 +35,7 @@ def main():
     bench.write_config(cfg, ["w1"], "constant", self_peer=True, base_port=45800)
     flat = torch.randn(a.numel, device=dev)
     conn = DpwaConnection("w1", cfg, seed=1000, group=LocalGroup())
-    res = {"numel": a.numel, "rounds": a.rounds}
+    res = {"numel": a.numel, "rounds": a.rounds, "tensors": a.tensors}
 
     def conn_round():
         conn.update_send(flat, 1.0, reuse_snapshot=True)
@@ -65,7 +68,14 @@ def main():
     bench.write_config(cfg2, ["a1"], "constant", self_peer=True, base_port=45850)
     for guard in (True, False):
         net = torch.nn.Module()
-        net.register_parameter("w", torch.nn.Parameter(torch.randn(a.numel, device=dev)))
+        if a.tensors == 1:
+            net.register_parameter("w", torch.nn.Parameter(torch.randn(a.numel, device=dev)))
+        else:
+            net.layers = torch.nn.ModuleList()
+            for _ in range(a.tensors):
+                layer = torch.nn.Module()
+                layer.register_parameter("w", torch.nn.Parameter(torch.randn(max(1, a.numel // a.tensors), device=dev)))
+                net.layers.append(layer)
         ad = DpwaPyTorchAdapter(net, "a1", cfg2, seed=3000, group=LocalGroup(), reuse_guard=guard)
         for _ in range(200):
             ad.update_send(1.0)
