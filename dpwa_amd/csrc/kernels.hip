@@ -33,7 +33,8 @@
 //             header.
 //  * launches: the host half picks a kernel instantiation through with_ops (dtype) and Choice
 //             (workgroup size, cache policy -- "the policy table" says what each averaging form
-//             launches for a requested DPWA_LERP_POLICY) and starts it with launch().
+//             launches for a requested policy: the one policy.hpp chooses from the bytes of the
+//             launch, or DPWA_LERP_POLICY's) and starts it with launch().
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -47,6 +48,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "policy.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -418,7 +420,8 @@ __device__ __forceinline__ void span_store(__amdgpu_buffer_rsrc_t r, int lane_of
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, lane_off, 0, AUX);
 }
 
-// Cache policies of the averaging kernel (a bit set; the product uses 8, see lerp_policy()):
+// Cache policies of the averaging kernel (a bit set; cache-sized launches use 0, larger ones and
+// the resident forms 8, see policy.hpp and lerp_policy()):
 // the peer snapshot is always read `nt`; the parameters are read `nt` or, with bit 1, with the
 // default policy; the result is stored `sc1`, with bit 2 `sc0 sc1`, with bit 4 `nt sc1`.
 template <int POLICY> struct LerpPolicy {
@@ -702,7 +705,8 @@ __global__ __launch_bounds__(kStreamBlock) void k_lerp_mixed(u32x4 *__restrict__
 
 // The tracked form of the single-learner fused average (k_lerp's span code with DistTrack, so the
 // averaged bits are k_lerp's): plain, write-through (DUAL) and resident (OOP), one-wave
-// workgroups, the product cache policy (POLICY = kProductPolicy).  `acc`: the distance accumulators.
+// workgroups, the cache policy k_lerp would take (by size; resident: kProductPolicy).  `acc`: the
+// distance accumulators.
 template <class Ops, bool DUAL, bool OOP, int POLICY>
 __global__ __launch_bounds__(kStreamBlock) void k_lerp_tracked(typename Ops::V *__restrict__ param,
                                                                const typename Ops::V *__restrict__ peer, int64_t n,
@@ -1179,22 +1183,23 @@ static int lerp_block()
     return block;
 }
 
-// The product policy is 8 (parameters stored `nt`, the snapshot `sc1`): with the batched
-// dispatch it lifts every cold averaging kernel by 1-3 % of peak (11.17M batched 0.78 -> 0.80-0.81,
-// 7B bf16 full 0.81 -> 0.82) and leaves the N=1 loop within noise (-0.4 %, two interleaved passes
-// with sweeps, profiles/r03_policy_ab.log).  Round 2's one-launch-per-learner loop lost 2-5 % with it
-// (profiles/r02_policy_ab2.json).  DPWA_LERP_POLICY (0..31) requests another (tuning); what a
-// requested value launches depends on the form, see the table below.
-constexpr int kProductPolicy = 8;
-
-static int lerp_policy()
+// The cache policy requested of a launch that averages `payload` bytes (policy.hpp: kFitPolicy
+// while the parameters and two snapshot slots fit kCacheFitBytes, kProductPolicy above).  The
+// single-learner and batched launches that are not resident, the tracked and the segmented
+// launches ask with their bytes, and so does k_stream_mix, which is measured against them.
+// DPWA_LERP_POLICY (0..31) forces one policy on every launch and DPWA_CACHE_FIT_BYTES moves the
+// threshold (0: never fit) -- tuning and tests; what a requested value launches depends on the
+// form, see the table below.
+static int lerp_policy(int64_t payload)
 {
-    static const int policy = env_knob("DPWA_LERP_POLICY", kProductPolicy, [](const char *e) {
-        const int p = atoi(e);
-        return p >= 0 && p <= 31 ? p : kNoValue;
-    });
-    return policy;
+    static const int forced = parse_lerp_policy(getenv("DPWA_LERP_POLICY"));
+    static const int64_t fit_bytes = parse_cache_fit_bytes(getenv("DPWA_CACHE_FIT_BYTES"));
+    return policy_for_bytes(forced, fit_bytes, payload);
 }
+
+// The resident, pair, group and relay kernels store into a slot that a peer reads next: the
+// product policy whatever the size, unless DPWA_LERP_POLICY forces another.
+static int lerp_policy() { return lerp_policy(INT64_MAX); }
 
 // Span order of a batched dispatch of equal-size entries.  Dealt round-robin, every span is
 // re-read by the next round's dispatch one round after it was written, which keeps the re-reads
@@ -1202,8 +1207,7 @@ static int lerp_policy()
 // half the re-reads come 1.5 rounds after their write.  Measured (profiles/r03_batch_order_ab.log,
 // three interleaved pairs): round-robin +2.8 % at 11.17M fp32 (179 MB written per round), -4 %
 // at 100M fp32 (1.6 GB: twice the concurrent streams, no cache to win).  DPWA_BATCH_ORDER=
-// interleaved / contiguous forces one (1 / 0; -1: by size).
-constexpr size_t kInfinityCacheBytes = (size_t)256 << 20;
+// interleaved / contiguous forces one (1 / 0; -1: by size).  (kInfinityCacheBytes: policy.hpp)
 
 static int batch_order()
 {
@@ -1238,7 +1242,8 @@ static bool pair_fused()
 // Which cache policy (LerpPolicy) each averaging form launches for a requested one
 // (lerp_policy()): the listed values as themselves, every other value as the fallback, which
 // comes first.  These are the instantiated kernels; the launchers below pick through these
-// types, so the table is what runs.
+// types, so the table is what runs.  Every table of a form that chooses by size lists both
+// kFitPolicy and kProductPolicy.
 using Lerp64Policies = Choice<0, 1, 2, 3, 4, 5, 8, 9, 10, 16>;   // k_lerp, 64 lanes, not resident
 using LerpWidePolicies = Choice<0, 8>;                           // k_lerp, 128 / 256 / 512 lanes (tuning sizes)
 // the resident kernels store only the next slot, so their store policy is the snapshot one: bit
@@ -1251,7 +1256,8 @@ using PairF32Policies = Choice<kProductPolicy, 0, 1, 2, 16>;   // k_lerp_pair, f
 using Pair16Policies = Choice<kProductPolicy, 0>;              // k_lerp_pair, bfloat16 / float16
 using GroupPolicies = Choice<kProductPolicy, 0>;               // k_lerp_group
 using RelayPolicies = Choice<0, 8>;                            // k_lerp_relay
-using FixedPolicy = Choice<kProductPolicy>;                    // k_lerp_mixed, k_stream_mix: the knob is ignored
+// k_lerp_tracked and k_lerp_mixed (not resident), k_stream_mix: the two policies the size chooses between
+using BySizePolicies = Choice<kProductPolicy, kFitPolicy>;
 
 template <class Policies, int... Ps> constexpr bool launches_as_itself() { return ((Policies::launched(Ps) == Ps) && ...); }
 static_assert(launches_as_itself<Lerp64Policies, 1, 2, 3, 4, 5, 8, 9, 10, 16>() && Lerp64Policies::launched(6) == 0);
@@ -1264,7 +1270,9 @@ static_assert(launches_as_itself<PairF32Policies, 0, 1, 2, 16>() && PairF32Polic
 static_assert(launches_as_itself<Pair16Policies, 0>() && Pair16Policies::launched(1) == 8 && Pair16Policies::launched(8) == 8);
 static_assert(launches_as_itself<GroupPolicies, 0>() && GroupPolicies::launched(16) == 8 && GroupPolicies::launched(8) == 8);
 static_assert(launches_as_itself<RelayPolicies, 8>() && RelayPolicies::launched(9) == 0);
-static_assert(FixedPolicy::launched(0) == 8 && FixedPolicy::launched(8) == 8);
+static_assert(launches_as_itself<BySizePolicies, kFitPolicy, kProductPolicy>() && BySizePolicies::launched(16) == 8);
+static_assert(launches_as_itself<Lerp64Policies, kFitPolicy, kProductPolicy>() &&
+              launches_as_itself<BatchPolicies, kFitPolicy, kProductPolicy>());
 
 // ---------------------------------------------------------------- averaging launches
 // Workgroups of one 16-byte item per lane over n elements; the last span may be empty
@@ -1283,7 +1291,7 @@ static hipError_t launch_mode(void *param, const void *peer, int64_t n, const Le
     return Choice<256, 64, 128, 512>::with(lerp_block(), [&](auto block) {
         constexpr int BLOCK = decltype(block)::value;
         using Policies = std::conditional_t<BLOCK == 64, Lerp64Policies, LerpWidePolicies>;
-        return Policies::with(lerp_policy(), [&](auto policy) {
+        return Policies::with(lerp_policy(n * (int64_t)sizeof(typename Ops::S)), [&](auto policy) {
             return launch(k_lerp<Ops, MODE, DUAL, BLOCK, decltype(policy)::value>, dim3((uint32_t)span_grid<Ops>(n, BLOCK)),
                           dim3(BLOCK), s, timing, param, peer, n, args);
         });
@@ -1370,8 +1378,12 @@ static hipError_t launch_mixed(const dpwa_layout &layout, void *param, const voi
     const int64_t total = layout_bytes(layout);
     const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
     if (g > 0x7fffffffLL) return hipErrorInvalidValue;
-    return launch(k_lerp_mixed<MODE, DUAL, FixedPolicy::launched(kProductPolicy), OOP>, dim3((uint32_t)g),
-                  dim3(kStreamBlock), s, timing, param, peer, total, args, t);
+    // (resident: the product policy, as the single-dtype resident kernels without the knob)
+    return BySizePolicies::with(OOP ? kProductPolicy : lerp_policy(total), [&](auto policy) {
+        constexpr int P = OOP ? kProductPolicy : decltype(policy)::value;
+        return launch(k_lerp_mixed<MODE, DUAL, P, OOP>, dim3((uint32_t)g), dim3(kStreamBlock), s, timing, param, peer,
+                      total, args, t);
+    });
 }
 
 hipError_t launch_lerp_mixed(const dpwa_layout &layout, void *param, const void *peer, const dpwa_coef *coef,
@@ -1411,9 +1423,11 @@ hipError_t launch_average_tracked(int32_t dtype, void *param, const void *peer, 
             return launch(kernel, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, timing, param,
                           peer, n, args, acc);
         };
-        constexpr int P = kProductPolicy;
-        return oop ? run(k_lerp_tracked<Ops, true, true, P>)
-                   : snap ? run(k_lerp_tracked<Ops, true, false, P>) : run(k_lerp_tracked<Ops, false, false, P>);
+        if (oop) return run(k_lerp_tracked<Ops, true, true, kProductPolicy>);   // resident: no choice by size
+        return BySizePolicies::with(lerp_policy(n * (int64_t)sizeof(typename Ops::S)), [&](auto policy) {
+            constexpr int P = decltype(policy)::value;
+            return snap ? run(k_lerp_tracked<Ops, true, false, P>) : run(k_lerp_tracked<Ops, false, false, P>);
+        });
     });
 }
 
@@ -1567,7 +1581,9 @@ static hipError_t average_batch(bool dual, const AvgBatch &b, hipStream_t s, con
         return ResidentPolicies::with(lerp_policy(), [&](auto policy) {
             return run(k_lerp_batch<Ops, true, decltype(policy)::value, true>, g);
         });
-    return BatchPolicies::with(lerp_policy(), [&](auto policy) {
+    int64_t numel[kMaxAvgBatch];
+    for (int i = 0; i < x.count; ++i) numel[i] = x.e[i].n;
+    return BatchPolicies::with(lerp_policy(payload_bytes(numel, x.count, sizeof(typename Ops::S))), [&](auto policy) {
         constexpr int P = decltype(policy)::value;
         return dual ? run(k_lerp_batch<Ops, true, P, false>, g) : run(k_lerp_batch<Ops, false, P, false>, g);
     });
@@ -2079,37 +2095,43 @@ hipError_t launch_window_roll(const char *old, const char *cur, int64_t nbytes, 
 // (dpwa_stream_mix, bench.py `roofline.mix_ceiling`): each one-wave workgroup loads the same
 // 1-KiB span of NR source buffers and stores one combination of them into the span of NW
 // destinations, with exactly the product kernel's instruction shapes and cache policy
-// (16-B buffer loads `nt`; the first destination stored as the parameters are, the others as the
-// snapshot is) but no factor and no arithmetic beyond one add per word: the ceiling that launch
-// shape reaches on this chip at a given size, timed in the same run as the product kernel.
-template <int NR, int NW>
+// (the first source loaded as the peer is, `nt`, the second as the parameters are; the first
+// destination stored as the parameters are, the others as the snapshot is; POLICY is what an
+// average of nbytes takes, lerp_policy(nbytes)) but no factor and no arithmetic beyond one add
+// per word: the ceiling that launch shape reaches on this chip at a given size, timed in the same
+// run as the product kernel.
+template <int NR, int NW, int POLICY>
 __global__ __launch_bounds__(kStreamBlock) void k_stream_mix(StreamMixArgs a)
 {
     constexpr int SPAN = kStreamBlock * 16;
     const int64_t span_off = (int64_t)blockIdx.x * SPAN;
     const int lane_off = threadIdx.x * 16;
     u32x4 v[NR];
+    v[0] = __builtin_amdgcn_raw_buffer_load_b128(span_rsrc<SPAN>(a.src[0], span_off, a.nbytes), lane_off, 0, kAuxStream);
 #pragma unroll
-    for (int i = 0; i < NR; ++i)
+    for (int i = 1; i < NR; ++i)
         v[i] = __builtin_amdgcn_raw_buffer_load_b128(span_rsrc<SPAN>(a.src[i], span_off, a.nbytes), lane_off, 0,
-                                                     kAuxStream);
+                                                     LerpPolicy<POLICY>::param_load);
     u32x4 r = v[0];
 #pragma unroll
     for (int i = 1; i < NR; ++i) r = r + v[i];
     __builtin_amdgcn_raw_buffer_store_b128(r, span_rsrc<SPAN>(a.dst[0], span_off, a.nbytes), lane_off, 0,
-                                           LerpPolicy<kProductPolicy>::store);
+                                           LerpPolicy<POLICY>::store);
     if (NW > 1)
         __builtin_amdgcn_raw_buffer_store_b128(r, span_rsrc<SPAN>(a.dst[1], span_off, a.nbytes), lane_off, 0,
-                                               LerpPolicy<kProductPolicy>::snap_store);
+                                               LerpPolicy<POLICY>::snap_store);
 }
 
 hipError_t launch_stream_mix(const StreamMixArgs &a, hipStream_t s, const LaunchTiming *timing)
 {
     if (a.nr < 1 || a.nr > 2 || a.nw < 1 || a.nw > 2 || a.nbytes < 0 || (a.nbytes & 15)) return hipErrorInvalidValue;
     const uint32_t g = (uint32_t)(a.nbytes / (kStreamBlock * 16) + 1);
-    void (*k)(StreamMixArgs) = a.nr == 1 ? (a.nw == 1 ? k_stream_mix<1, 1> : k_stream_mix<1, 2>)
-                                         : (a.nw == 1 ? k_stream_mix<2, 1> : k_stream_mix<2, 2>);
-    return launch(k, dim3(g), dim3(kStreamBlock), s, timing, a);
+    return BySizePolicies::with(lerp_policy(a.nbytes), [&](auto policy) {
+        constexpr int P = decltype(policy)::value;
+        void (*k)(StreamMixArgs) = a.nr == 1 ? (a.nw == 1 ? k_stream_mix<1, 1, P> : k_stream_mix<1, 2, P>)
+                                             : (a.nw == 1 ? k_stream_mix<2, 1, P> : k_stream_mix<2, 2, P>);
+        return launch(k, dim3(g), dim3(kStreamBlock), s, timing, a);
+    });
 }
 
 // One 64-bit word into (host-mapped) memory after everything before it on the stream: a
