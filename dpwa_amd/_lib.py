@@ -25,6 +25,7 @@ LAYOUT_MAX_SEGMENTS, LAYOUT_ALIGN = 3, 4096
 DISTANCE_ACC_STRIDE = 128    # bytes from one distance accumulator to the next in a workspace
 INTERP_CONSTANT, INTERP_CLOCK, INTERP_LOSS = 0, 1, 2
 STATUS_OK, STATUS_ZERO_DIVISION = 0, 1
+STATUS_PEER_NONFINITE = 2    # no error: the round was skipped (skip_nonfinite_peer)
 IPC_HANDLE_BYTES = 128
 SLOT_PAYLOAD_OFFSET = 4096   # [dpwa_header | pad | payload]
 CONNECT_OK, CONNECT_REFUSED, CONNECT_ERROR = 0, 1, 2
@@ -146,6 +147,11 @@ SIGNATURES = {
     "dpwa_learner_set_param_distance": [_vp, ctypes.POINTER(ParamRange), _i64, _int],
     "dpwa_learner_param_distance": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64)],
     "dpwa_learner_param_distance_rounds": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "dpwa_check_finite": [_i32, _vp, _i64, _vp, ctypes.c_uint32, _vp, _vp, _vp],
+    "dpwa_check_finite_mixed": [ctypes.POINTER(Layout), _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp],
+    "dpwa_learner_set_finite_check": [_vp, _int],
+    "dpwa_learner_finite_skips": [_vp, ctypes.POINTER(_u64)],
+    "dpwa_node_set_finite_check": [_vp, _int],
     "dpwa_learner_set_distance": [_vp, _int],
     "dpwa_learner_distance": [_vp, ctypes.POINTER(_vp)],
     "dpwa_layout_digest": [ctypes.POINTER(Layout), _i64, ctypes.POINTER(ctypes.c_uint32)],

@@ -111,7 +111,8 @@ class DpwaPyTorchAdapter:
     not use it."""
 
     def __init__(self, net, name, config_file, write_through=True, transport="device", reuse_guard=True,
-                 resident=False, track_distance=False, distance_every=1, **connection_kwargs):
+                 resident=False, track_distance=False, distance_every=1, skip_nonfinite_peer=False,
+                 **connection_kwargs):
         """transport: "device" (peers are learners of this process or of the torch.distributed
         job, pulled from HBM/over xGMI) or "wire" (peers are reached over TCP at the YAML's
         host/port with the reference's protocol -- e.g. reference CPU nodes; dpwa_amd/bridge.py).
@@ -124,8 +125,14 @@ class DpwaPyTorchAdapter:
         track_distance="per_parameter" (device transport): also the same two sums for every parameter
         tensor, ``last_distance.parameters`` -> ``{name: ...}`` keyed by ``named_parameters()`` names
         (``ParameterDistances``), measured on every ``distance_every``-th round that averages by a
-        separate pass that reads both operands once more."""
+        separate pass that reads both operands once more.
+
+        skip_nonfinite_peer (extension, off by default): a round whose fetched peer snapshot holds a NaN
+        or an inf averages nothing and is counted (``nonfinite_skips``) instead of spreading it into
+        this model; see ``DpwaConnection``.  One more read of the peer's snapshot per round."""
         connection_kwargs = dict(connection_kwargs, track_distance=track_distance)
+        if skip_nonfinite_peer:      # (off: the connection is built exactly as before)
+            connection_kwargs["skip_nonfinite_peer"] = True
         if resident and transport != "device":
             raise ValueError("resident parameters need the device transport")
         self._net = net
@@ -344,6 +351,12 @@ class DpwaPyTorchAdapter:
         hits = ctypes.c_uint32()
         _lib.call("dpwa_learner_window_hits", self._conn._learner.handle, ctypes.byref(hits))
         return hits.value
+
+    @property
+    def nonfinite_skips(self):
+        """Rounds skipped because the peer's snapshot held a NaN or an inf (``skip_nonfinite_peer=True``;
+        an int, 0 with the switch off).  Reading it waits for the device."""
+        return self._conn.nonfinite_skips
 
     @property
     def last_distance(self):

@@ -256,8 +256,10 @@ class WireConnection(DpwaConnection):
     training step like the reference's TxThread; eager=False fetches at update_wait
     (deterministic lock-step when every node's update_send precedes every update_wait)."""
 
-    def __init__(self, name, config_file, codec=None, seed=None, eager=True, serve=True, track_distance=False):
-        super().__init__(name, config_file, seed=seed, group=_WireGroup(), track_distance=track_distance)
+    def __init__(self, name, config_file, codec=None, seed=None, eager=True, serve=True, track_distance=False,
+                 skip_nonfinite_peer=False):
+        super().__init__(name, config_file, seed=seed, group=_WireGroup(), track_distance=track_distance,
+                         skip_nonfinite_peer=skip_nonfinite_peer)
         self.codec = codec
         self.eager = eager
         self._wire_peers = [_Peer(p.host, p.port) for p in self.peers]

@@ -148,6 +148,36 @@ int dpwa_measure_distance_mixed(const dpwa_layout *layout, const void *param, co
     return DPWA_OK;
 }
 
+// The stateless non-finite check (the pass a learner runs before its average: learner.cpp finite_pass).
+int dpwa_check_finite(int32_t dtype, const void *peer_payload, int64_t n, uint32_t *veto_dev, uint32_t stamp,
+                      dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (n < 0 || (n > 0 && !peer_payload) || !veto_dev || ((uintptr_t)veto_dev & 3) || stamp == 0 ||
+        (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_check_finite: bad arguments (NULL or misaligned pointer, n < 0, stamp 0)");
+    if (dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_check_finite: a DPWA_MIXED payload needs its layout (dpwa_check_finite_mixed)");
+    if (!is_float_dtype(dtype)) return set_error(DPWA_ERR_ARG, "dpwa_check_finite: unknown dtype %d", dtype);
+    if ((uintptr_t)peer_payload & (dtype_size(dtype) - 1))
+        return set_error(DPWA_ERR_ARG, "dpwa_check_finite: the payload is not aligned to its element size");
+    const CallerTiming timing(start_event, stop_event);
+    HIP_TRY(launch_peer_finite(dtype, peer_payload, n, veto_dev, stamp, (hipStream_t)stream, timing));
+    return DPWA_OK;
+}
+
+int dpwa_check_finite_mixed(const dpwa_layout *layout, const void *peer_payload, uint32_t *veto_dev, uint32_t stamp,
+                            dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (!layout || !peer_payload || !veto_dev || ((uintptr_t)veto_dev & 3) || stamp == 0 || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_check_finite_mixed: bad arguments (NULL or misaligned pointer, stamp 0)");
+    if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_check_finite_mixed: %s", why);
+    if (!aligned16(peer_payload))
+        return set_error(DPWA_ERR_ARG, "dpwa_check_finite_mixed: a segmented payload is 16-byte aligned");
+    const CallerTiming timing(start_event, stop_event);
+    HIP_TRY(launch_peer_finite_mixed(*layout, peer_payload, veto_dev, stamp, (hipStream_t)stream, timing));
+    return DPWA_OK;
+}
+
 int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int64_t n, const dpwa_interp *cfg,
                          double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload, void *workspace,
                          dpwa_distance *out_dev, dpwa_stream_t stream, void *start_event, void *stop_event)

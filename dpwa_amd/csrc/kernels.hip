@@ -27,6 +27,10 @@
 //             Opt-in too: the same sums for every parameter tensor over its own elements, by a
 //             stand-alone pass that looks each span's tensors up in a device table
 //             (k_param_distance) and one finishing workgroup per tensor (k_param_distance_finish).
+//  * non-finite peer check: opt-in -- one read of the fetched peer snapshot before the average
+//             (k_peer_finite*), a test on the exponent bits; a lane that finds a NaN or an inf
+//             stores the round's stamp into the learner's veto word, and the factor of a round
+//             whose stamp it finds there is the no-op's, with a status of its own.
 //  * factor:  the same fp64 math as a one-thread kernel for the split API.
 //  * publish: update_send's snapshot (dpwa.py:111-116, pytorch.py:49-53) -- clock += 1 on
 //             the device and one copy of the flat buffer into a snapshot slot behind its
@@ -296,7 +300,9 @@ __device__ __forceinline__ void factor_commit(const FusedArgs &fa, const dpwa_co
 {
     *fa.clock_out = c.new_clock;                       // dpwa.py:155 (unchanged on error)
     *fa.coef_out = c;
-    if (fa.status_mirror && c.status != DPWA_STATUS_OK) *fa.status_mirror = c.status;   // sticky
+    // sticky, and an error only: a round skipped for a non-finite peer must not make the next call raise
+    if (fa.status_mirror && c.status == DPWA_STATUS_ZERO_DIVISION) *fa.status_mirror = c.status;
+    if (c.status == DPWA_STATUS_PEER_NONFINITE) *fa.skips = *fa.skips + 1;   // (this lane alone writes it)
     if (fa.next_header) {                              // the next publish's state, written ahead
         const double next = c.new_clock + 1.0;         // dpwa.py:112 of that publish
         *fa.clock_next = next;
@@ -311,10 +317,23 @@ __device__ __forceinline__ void factor_commit(const FusedArgs &fa, const dpwa_co
 
 // The fused-factor prologue: the (uniform) factor, evaluated by every lane that calls this;
 // `commit` is true for the one lane of the grid that also writes it out.
+// A learner that skips non-finite peers (fa.veto non-null; "non-finite peer check" below) has had
+// k_peer_finite* look at the snapshot earlier on this stream: the veto word equals this round's
+// stamp when it found a NaN or an inf.  Such a round is the no-op round with a status of its own,
+// DPWA_STATUS_PEER_NONFINITE, which is no error; ZeroDivision keeps precedence.  The word is a
+// uniform load from a kernel-argument pointer, issued before the factor math it overlaps with.
 __device__ __forceinline__ dpwa_coef fused_factor(const FusedArgs &fa, bool commit)
 {
-    const dpwa_coef c = factor_math(fa.cfg, *fa.clock_in, fa.hdr->clock, fa.hdr->loss,
-                                    read_loss(fa.loss_d, fa.loss_f32, fa.loss_h));
+    const bool vetoed = fa.veto && *fa.veto == fa.stamp;
+    const double clock = *fa.clock_in;
+    dpwa_coef c = factor_math(fa.cfg, clock, fa.hdr->clock, fa.hdr->loss, read_loss(fa.loss_d, fa.loss_f32, fa.loss_h));
+    if (vetoed && c.status == DPWA_STATUS_OK) {
+        c.status = DPWA_STATUS_PEER_NONFINITE;
+        c.factor = 0.0;
+        c.new_clock = clock;
+        c.a = 0.0f;
+        c.b = 1.0f;
+    }
     if (commit) factor_commit(fa, c);
     return c;
 }
@@ -815,6 +834,94 @@ __global__ __launch_bounds__(kDistFinishBlock) void k_distance_finish(double *__
     out->norm2 = n2;
     out->clock = coef ? coef->new_clock : 0.0;
     out->n = n;
+}
+
+// ---------------------------------------------------------------- non-finite peer check
+// Opt-in (dpwa_learner_set_finite_check): before a round averages, one pass reads the fetched peer
+// snapshot and vetoes the round when any element of it is NaN or +-inf, so that one replica that
+// overflowed does not spread through the gossip.  k_distance's shape: one-wave workgroups, one
+// 16-byte item per lane, an exact grid of 1-KiB spans whose lanes past the end load zeros (finite),
+// the ragged tail element by element in workgroup 0.
+//
+// The test is on bit patterns: an element is non-finite when its exponent field is all ones, both
+// halves of every dword for the 16-bit types.  No float compare and no conversion, so signalling
+// NaNs, subnormals and the largest finite values come out right whatever the denormal or NaN mode.
+//
+// No reduction, no atomics, nothing to zero: the launch carries a non-zero stamp (the learner's
+// count of checked rounds), and a lane that sees a non-finite element stores it into the veto word
+// with a plain vector store -- several lanes store the same value.  The word is never cleared; it
+// vetoes a round only while it equals that round's stamp (fused_factor), which the kernel boundary
+// behind this pass orders after every store.
+//
+// AUX: the cache policy of the loads.  The average that follows reads the same bytes again, so
+// they take the default policy, at every size (finite_aux(): measured against `nt`).
+__device__ __forceinline__ bool nonfinite_f32(uint32_t w) { return (w & 0x7f800000u) == 0x7f800000u; }
+// the two 16-bit elements of a dword, exponent mask M (bf16 0x7f80, fp16 0x7c00)
+template <uint32_t M> __device__ __forceinline__ bool nonfinite_16x2(uint32_t w)
+{
+    return (w & M) == M || (w & (M << 16)) == (M << 16);
+}
+
+__device__ __forceinline__ bool peer_bad(OpsF32, u32x4 q)
+{
+    return nonfinite_f32(q.x) || nonfinite_f32(q.y) || nonfinite_f32(q.z) || nonfinite_f32(q.w);
+}
+__device__ __forceinline__ bool peer_bad(OpsBF16, u32x4 q)
+{
+    return nonfinite_16x2<0x7f80u>(q.x) || nonfinite_16x2<0x7f80u>(q.y) || nonfinite_16x2<0x7f80u>(q.z) ||
+           nonfinite_16x2<0x7f80u>(q.w);
+}
+__device__ __forceinline__ bool peer_bad(OpsF16, u32x4 q)
+{
+    return nonfinite_16x2<0x7c00u>(q.x) || nonfinite_16x2<0x7c00u>(q.y) || nonfinite_16x2<0x7c00u>(q.z) ||
+           nonfinite_16x2<0x7c00u>(q.w);
+}
+// One element, as its bits (FiniteBits<Ops>::T: an unsigned integer of the element's size).
+__device__ __forceinline__ bool peer_bad_s(OpsF32, uint32_t q) { return nonfinite_f32(q); }
+__device__ __forceinline__ bool peer_bad_s(OpsBF16, uint16_t q) { return (q & 0x7f80u) == 0x7f80u; }
+__device__ __forceinline__ bool peer_bad_s(OpsF16, uint16_t q) { return (q & 0x7c00u) == 0x7c00u; }
+template <class Ops> struct FiniteBits {
+    using T = std::conditional_t<sizeof(typename Ops::S) == 4, uint32_t, uint16_t>;
+};
+
+template <class Ops, int AUX>
+__global__ __launch_bounds__(kStreamBlock) void k_peer_finite(const void *__restrict__ peer, int64_t n, uint32_t *veto,
+                                                              uint32_t stamp)
+{
+    using B = typename FiniteBits<Ops>::T;
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t vbytes = n / Ops::PER * 16;
+    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
+    const u32x4 q = span_load<u32x4, AUX>(span_rsrc<SPAN>(peer, span_off, vbytes), threadIdx.x * 16);
+    bool bad = peer_bad(Ops{}, q);
+    const int64_t tail = n / Ops::PER * Ops::PER;
+    if (blockIdx.x == 0 && threadIdx.x < n - tail) bad = bad || peer_bad_s(Ops{}, reinterpret_cast<const B *>(peer)[tail + threadIdx.x]);
+    if (bad) *veto = stamp;
+}
+
+// The same over a segmented payload: the span's test is its segment's (seg_dtype from the span's
+// byte offset, as k_lerp_mixed; no ragged tail; padding bytes are zeros, which are finite).
+template <int AUX>
+__global__ __launch_bounds__(kStreamBlock) void k_peer_finite_mixed(const u32x4 *__restrict__ peer, int64_t total,
+                                                                    SegTable segs, uint32_t *veto, uint32_t stamp)
+{
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
+    const u32x4 q = span_load<u32x4, AUX>(span_rsrc<SPAN>(peer, span_off, total), threadIdx.x * 16);
+    const int32_t dtype = seg_dtype(segs, span_off);
+    const bool bad = dtype == DPWA_F32 ? peer_bad(OpsF32{}, q) : dtype == DPWA_BF16 ? peer_bad(OpsBF16{}, q) : peer_bad(OpsF16{}, q);
+    if (bad) *veto = stamp;
+}
+
+// Element-wise form for a single-dtype payload that is not 16-byte aligned: a grid-stride loop.
+template <class Ops>
+__global__ __launch_bounds__(kBlock) void k_peer_finite_unaligned(const typename FiniteBits<Ops>::T *__restrict__ peer,
+                                                                  int64_t n, uint32_t *veto, uint32_t stamp)
+{
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) bad = bad || peer_bad_s(Ops{}, peer[i]);
+    if (bad) *veto = stamp;
 }
 
 // ---------------------------------------------------------------- distance to the peer, per tensor
@@ -1488,6 +1595,60 @@ hipError_t launch_param_distance_finish(double *acc, const ParamEntry *table, in
     if (count < 1 || count > 0x7fffffffLL || !table || !acc || !out) return hipErrorInvalidValue;
     return launch(k_param_distance_finish, dim3((uint32_t)count), dim3(kParamFinishBlock), s, timing, acc, table, out, coef,
                   count);
+}
+
+// ---------------------------------------------------------------- non-finite peer check launches
+// The load policy of the pass: the default one at every size.  The rule by size of policy.hpp (`nt`
+// above kCacheFitBytes) was the starting point and lost on both sides of the threshold, pass +
+// average together, fresh processes taking turns (profiles/finite_cost.json): 11,173,962 fp32
+// 27.1-27.4 us against `nt` 27.4-27.5 (the pass itself 9.92 against 10.16); 100M fp32, the snapshot
+// from HBM, 249.3-252.8 us against 262.6-272.7 -- the pass takes 83.2 us either way, the average
+// behind it 166-169 us against 179-189: what the default loads leave in the Infinity Cache, it
+// reads there.  DPWA_FINITE_LOADS=nt / default forces one (tools/finite_cost.py's A/B).
+static int finite_aux()
+{
+    static const int aux = env_knob("DPWA_FINITE_LOADS", 0, [](const char *e) {
+        return strcmp(e, "default") == 0 ? 0 : strcmp(e, "nt") == 0 ? kAuxStream : kNoValue;
+    });
+    return aux;
+}
+using FiniteLoads = Choice<0, kAuxStream>;
+
+hipError_t launch_peer_finite(int32_t dtype, const void *peer, int64_t n, uint32_t *veto, uint32_t stamp, hipStream_t s,
+                              const LaunchTiming *timing)
+{
+    if (n < 0 || !veto || stamp == 0 || ((uintptr_t)veto & 3)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        if (!aligned16(peer))
+            return launch(k_peer_finite_unaligned<Ops>, dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)), dim3(kBlock),
+                          s, timing, peer, n, veto, stamp);
+        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+        return FiniteLoads::with(finite_aux(), [&](auto aux) {
+            return launch(k_peer_finite<Ops, decltype(aux)::value>, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)),
+                          dim3(kStreamBlock), s, timing, peer, n, veto, stamp);
+        });
+    });
+}
+
+hipError_t launch_peer_finite_mixed(const dpwa_layout &layout, const void *peer, uint32_t *veto, uint32_t stamp,
+                                    hipStream_t s, const LaunchTiming *timing)
+{
+    if (layout_problem(layout, -1) || !peer || !aligned16(peer) || !veto || stamp == 0 || ((uintptr_t)veto & 3))
+        return hipErrorInvalidValue;
+    SegTable t;
+    for (int i = 0; i < DPWA_LAYOUT_MAX_SEGMENTS; ++i) {
+        t.begin[i] = i < layout.count ? layout.seg[i].byte_offset : INT64_MAX;
+        t.dtype[i] = i < layout.count ? layout.seg[i].dtype : layout.seg[0].dtype;
+    }
+    const int64_t total = layout_bytes(layout);
+    const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
+    if (g > 0x7fffffffLL) return hipErrorInvalidValue;
+    return FiniteLoads::with(finite_aux(), [&](auto aux) {
+        return launch(k_peer_finite_mixed<decltype(aux)::value>, dim3((uint32_t)g), dim3(kStreamBlock), s, timing, peer, total,
+                      t, veto, stamp);
+    });
 }
 
 // Some buffer is read by two entries (as parameters or as the peer snapshot).

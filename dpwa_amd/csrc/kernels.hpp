@@ -57,6 +57,12 @@ struct FusedArgs {
     uint64_t next_version;
     int64_t n;
     int32_t dtype;
+    // A learner that skips non-finite peers (launch_peer_finite ran earlier on the stream): the round
+    // is a no-op with status DPWA_STATUS_PEER_NONFINITE, counted in *skips, when *veto == stamp.
+    // Null veto: no check.
+    const uint32_t *veto;
+    uint32_t stamp;
+    uint64_t *skips;
 };
 
 // Lerp over n elements; coefficients from `coef` (device) or, when coef is null, from (a, b).
@@ -101,6 +107,14 @@ hipError_t launch_distance_mixed(const dpwa_layout &layout, const void *param, c
                                  hipStream_t s);
 hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
                                   const LaunchTiming *timing = nullptr);
+
+// The non-finite peer check (kernels.hip "non-finite peer check"): one read of the peer payload; a
+// lane that finds a NaN or an inf stores `stamp` (non-zero) into *veto (device memory, 4-B aligned).
+// Any element alignment for a single dtype; a segmented payload is 16-B aligned.
+hipError_t launch_peer_finite(int32_t dtype, const void *peer, int64_t n, uint32_t *veto, uint32_t stamp, hipStream_t s,
+                              const LaunchTiming *timing = nullptr);
+hipError_t launch_peer_finite_mixed(const dpwa_layout &layout, const void *peer, uint32_t *veto, uint32_t stamp,
+                                    hipStream_t s, const LaunchTiming *timing = nullptr);
 
 // The distance to the peer for every parameter tensor (dpwa_param_range, include/dpwa_hip.h;
 // kernels.hip "distance to the peer, per tensor").  The device table has one ParamEntry per

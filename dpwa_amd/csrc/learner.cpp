@@ -285,6 +285,11 @@ struct Ctl {            // device control block
     uint32_t guard_hits;   // ... and how many publishes did
     int32_t window_dirty;  // window guard (resident): the generation of the last window found written
     uint32_t window_hits;  // ... and how many windows were
+    // the non-finite peer check (dpwa_learner_set_finite_check): the stamp of the last checked round whose peer
+    // snapshot held a NaN or an inf (kernels.hip k_peer_finite; never cleared), and the rounds skipped for it
+    uint32_t finite_veto;
+    uint32_t reserved;
+    uint64_t finite_skips;
 };
 
 
@@ -464,6 +469,10 @@ struct dpwa_learner {
     // the distances to the peer (dpwa_learner_set_distance, dpwa_learner_set_param_distance) and all
     // that is launched for them around an average (measure.hpp)
     Measure measure;
+    // skip a round whose peer snapshot is not finite (dpwa_learner_set_finite_check); the stamp of the last
+    // checked round: never 0, so the zeroed veto word matches no round
+    bool finite_check = false;
+    uint32_t finite_stamp = 0;
     HostWord<int32_t> status;           // pinned mirror of coef.status for non-blocking polls
 };
 
@@ -1071,7 +1080,23 @@ static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev
     fa.loss_f32 = l->loss_f32 ? 1 : 0;
     fa.coef_out = &l->ctl->coef;
     fa.status_mirror = l->status.dev;
+    if (l->finite_check) {   // a checked round: its stamp, handed to finite_pass and to the factor
+        if (++l->finite_stamp == 0) l->finite_stamp = 1;
+        fa.veto = &l->ctl->finite_veto;
+        fa.stamp = l->finite_stamp;
+        fa.skips = &l->ctl->finite_skips;
+    }
     return fa;
+}
+
+// The non-finite check of a checked round (fa.veto set): one read of the fetched peer payload on `s`, behind
+// fetch.wait_landed and before the round's factor, average and distance passes.
+static int finite_pass(dpwa_learner *l, const FusedArgs &fa, const void *peer, hipStream_t s)
+{
+    if (!fa.veto) return DPWA_OK;
+    if (l->dtype == DPWA_MIXED) HIP_TRY(launch_peer_finite_mixed(l->layout, peer, &l->ctl->finite_veto, fa.stamp, s));
+    else HIP_TRY(launch_peer_finite(l->dtype, peer, l->n, &l->ctl->finite_veto, fa.stamp, s));
+    return DPWA_OK;
 }
 
 int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dpwa_stream_t stream)
@@ -1084,7 +1109,9 @@ int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dp
     hipStream_t s = (hipStream_t)stream;
     if (int rc = relay_materialize(l)) return rc;
     HIP_TRY(l->fetch.wait_landed(s));
-    HIP_TRY(launch_factor(fused_args(l, loss, loss_dev), s));
+    const FusedArgs fa = fused_args(l, loss, loss_dev);
+    if (int rc = finite_pass(l, fa, l->fetch.source().ptr + kPayloadOff, s)) return rc;
+    HIP_TRY(launch_factor(fa, s));
     HIP_TRY(l->factor_done.record(s));
     HIP_TRY(l->fetch.factored_on(s));   // the header has been read on s: a later pull into this buffer waits for it
     l->cur = (l->cur + 1) & 3;
@@ -1213,6 +1240,7 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
     // (the unaligned launch_average is not timed; p.relay: relay_phase2 refuses to defer for a
     // segmented payload or a measuring learner)
     const LaunchTiming *timing = p.mixed || p.relay || aligned16(p.flat) ? take_timing(l) : nullptr;
+    if (int rc = finite_pass(l, p.fa, p.peer, s)) return rc;   // (never with p.relay: relay_phase2 refuses)
     const Measured m{&l->measure, payload(l), p.flat, p.peer, p.snap, &p.fa, p.oop, timing};
     return measured_average(&m, 1, s, [&]() -> int {
         if (p.mixed) {
@@ -1264,7 +1292,9 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
         AvgBatch b{};
         const LaunchTiming *timing = take_timing(la);
         Measured member[kMaxAvgBatch];   // the dispatch stays as it is: their measurements go around it
+        dpwa_learner *checker[kMaxAvgBatch];
         auto add = [&](dpwa_learner *l, const AvgPlan &p) {
+            checker[b.count] = l;
             member[b.count] = Measured{&l->measure, payload(l), p.flat, p.peer, p.snap};
             AvgEntry &e = b.e[b.count++];
             e.param = p.flat;
@@ -1283,6 +1313,8 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
             add(ls[ic], plans[ic]);
             done[c] = 1;
         }
+        for (int i = 0; i < b.count; ++i)   // each checking member's snapshot, before anything of the dispatch
+            if (int rc = finite_pass(checker[i], b.e[i].fa, b.e[i].peer, s)) return rc;
         int rc = measured_average(member, b.count, s, [&]() -> int {
             HIP_TRY(launch_average_batch(la->dtype, pa.write_through, b, s, timing, pa.oop));
             return DPWA_OK;
@@ -1392,6 +1424,35 @@ int dpwa_learner_set_distance(dpwa_learner *l, int on)
     if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_distance: NULL learner");
     DeviceGuard dg(l->device);
     return l->measure.set_whole("dpwa_learner_set_distance", on != 0, l->relay_deferred);
+}
+
+int dpwa_learner_set_finite_check(dpwa_learner *l, int on)
+{
+    if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_finite_check: NULL learner");
+    if (on && l->relay_deferred)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_set_finite_check: a fused relay second phase is pending "
+                                         "(dpwa_learner_relay_phase2 with fuse != 0), which reads no contiguous peer "
+                                         "snapshot to check");
+    l->finite_check = on != 0;
+    return DPWA_OK;
+}
+
+// (Here and not in node.cpp: the node's host-only stand-in learner of tests/native has no such entry.)
+int dpwa_node_set_finite_check(dpwa_node *n, int on)
+{
+    dpwa_learner *l = nullptr;
+    if (!n || dpwa_node_handles(n, &l, nullptr) || !l)
+        return set_error(DPWA_ERR_STATE, "dpwa_node_set_finite_check: node not bound");
+    return dpwa_learner_set_finite_check(l, on);
+}
+
+int dpwa_learner_finite_skips(dpwa_learner *l, uint64_t *count)
+{
+    if (!l || !count) return set_error(DPWA_ERR_ARG, "dpwa_learner_finite_skips: NULL argument");
+    DeviceGuard dg(l->device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(count, &l->ctl->finite_skips, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return DPWA_OK;
 }
 
 int dpwa_learner_distance(dpwa_learner *l, const dpwa_distance **dev)
@@ -1758,6 +1819,10 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
         return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
                                          "snapshot, so a learner that measures the per-parameter distance "
                                          "(dpwa_learner_set_param_distance) cannot use it; gather (fuse = 0)");
+    if (fuse && l->finite_check)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
+                                         "snapshot, so a learner that skips non-finite peers "
+                                         "(dpwa_learner_set_finite_check) cannot use it; gather (fuse = 0)");
     RelayArgs a;
     int rc = relay_args(l, picks_dev, version, a);
     if (rc) return rc;

@@ -351,10 +351,15 @@ TRACKED_RELAY_AVG = ("pull='relay-avg' is not available with track_distance=True
                      "distance against; use 'relay' (the same relay, gathered first), 'kernel' or 'copy', or leave "
                      "track_distance off")
 
+FINITE_RELAY_AVG = ("pull='relay-avg' is not available with skip_nonfinite_peer=True: the relay's fused second phase "
+                    "reads the peer's snapshot stripe by stripe and leaves no contiguous snapshot to check for NaN "
+                    "or inf; use 'relay' (the same relay, gathered first), 'kernel' or 'copy', or leave "
+                    "skip_nonfinite_peer off")
+
 
 class DpwaConnection:
     def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None, track_distance=False,
-                 parameter_ranges=None, distance_every=1):
+                 parameter_ranges=None, distance_every=1, skip_nonfinite_peer=False):
         """layout (extension): ``FlatParameters.layout`` when the flat buffer given to update_send
         is the segmented ``torch.uint8`` buffer of a model that mixes dtypes (dpwa_amd/flat.py);
         every peer must hold the same layout.
@@ -373,7 +378,21 @@ class DpwaConnection:
         (``last_distance.parameters``, :class:`ParameterDistances`): on every ``distance_every``-th
         round that averages, a separate pass before the average reads both operands once more
         (2*n*s bytes, whatever the form), which is what ``distance_every`` is for.  It needs a
-        16-byte aligned parameter buffer."""
+        16-byte aligned parameter buffer.
+
+        skip_nonfinite_peer (extension, off by default): a round that would average first reads the
+        fetched peer snapshot once more (n*s bytes, one launch); if any element of it is NaN or
+        +-inf the round averages nothing -- parameters, clock and distance records stay as they
+        were, a write-through or resident snapshot receives the unchanged parameters -- and is
+        counted in ``nonfinite_skips``.  It is no error: nothing raises, and the round's
+        coefficients carry ``status == 2`` (``_lib.STATUS_PEER_NONFINITE``).  The scheduler is not
+        told: the fetch succeeded, so scores and peer choice are the reference's.  A ZeroDivision
+        round stays one.  It protects ``update_wait_average`` (every form), ``update_wait_average_many``
+        and ``update_wait()`` followed by ``average()``.  ``update_wait()`` alone is the reference's
+        seam, where the caller does the arithmetic with the returned snapshot: there the factor of a
+        skipped round is 0, and ``0 * nan`` is still ``nan`` -- call ``average()``.  A replica whose
+        own parameters are non-finite is not healed (``b * p`` stays NaN); its peers stop taking
+        from it.  Not available with ``pull='relay-avg'``."""
         self.name = name
         self._layout = tuple(layout) if layout is not None else None
         if isinstance(track_distance, str) and track_distance != "per_parameter":
@@ -393,6 +412,9 @@ class DpwaConnection:
             raise ValueError(MIXED_RELAY_AVG)
         if self._track_distance and pull is not None and pull.partition(":")[0] == "relay-avg":
             raise ValueError(TRACKED_RELAY_AVG)
+        self._skip_nonfinite = bool(skip_nonfinite_peer)
+        if self._skip_nonfinite and pull is not None and pull.partition(":")[0] == "relay-avg":
+            raise ValueError(FINITE_RELAY_AVG)
         self.config = DpwaConfiguration(config_file)
         self.nodes = self.config.get_nodes()
         self.fetch_probability = self.config.get_fetch_probability()
@@ -524,7 +546,12 @@ class DpwaConnection:
 
     def update_wait(self, loss):
         """dpwa.py:125-156: (None, 0) when not fetching or no peer delivered; otherwise the
-        fetched snapshot and the device factor (the clock is updated on the device)."""
+        fetched snapshot and the device factor (the clock is updated on the device).
+
+        With ``skip_nonfinite_peer=True`` a round whose snapshot holds a NaN or an inf returns
+        factor 0 and is counted -- but this is the reference's seam, where the caller does the
+        arithmetic, and ``0 * nan`` is still ``nan``: apply the factor with ``average()``, which
+        leaves the parameters alone in such a round."""
         learner = self._learner
         if learner is None:
             return None, 0
@@ -689,6 +716,15 @@ class DpwaConnection:
         nothing and keeps the previous round's numbers."""
         return self._last_distance
 
+    @property
+    def nonfinite_skips(self):
+        """How many rounds ``skip_nonfinite_peer=True`` has skipped because the peer's snapshot held a
+        NaN or an inf (an int; 0 with the switch off or before the first update_send).  Reading it
+        waits for the device."""
+        if self._learner is None or not self._skip_nonfinite:
+            return 0
+        return int(self._learner.finite_skips())
+
     def synchronize(self):
         """Waits for the device and raises a deferred ZeroDivisionError, if any."""
         if self._learner is not None:
@@ -812,6 +848,10 @@ class DpwaConnection:
                 raise ValueError(TRACKED_RELAY_AVG)
             _lib.call("dpwa_learner_set_distance", self._learner.handle, 1)
             self._distance = PeerDistance(self._learner)
+        if self._skip_nonfinite:
+            if self._pull.partition(":")[0] == "relay-avg":
+                raise ValueError(FINITE_RELAY_AVG)
+            _lib.call("dpwa_node_set_finite_check", self._node, 1)
         if self._per_parameter:                       # table, workspace and record: allocated here as well
             from .flat import c_param_ranges
             arr, where = c_param_ranges(self._param_ranges)
@@ -841,6 +881,8 @@ class DpwaConnection:
             raise ValueError(MIXED_RELAY_AVG)
         if kind == "relay-avg" and self._track_distance:
             raise ValueError(TRACKED_RELAY_AVG)
+        if kind == "relay-avg" and self._skip_nonfinite:
+            raise ValueError(FINITE_RELAY_AVG)
         self._pull = mode
         learner = self._learner
         if learner is None:

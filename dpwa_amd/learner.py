@@ -227,6 +227,16 @@ class Learner:
             self._status.value = 0
         return st
 
+    def set_finite_check(self, on):
+        """dpwa_learner_set_finite_check: skip (and count) a round whose peer snapshot holds a NaN or an inf."""
+        _lib.call("dpwa_learner_set_finite_check", self._h, 1 if on else 0)
+
+    def finite_skips(self):
+        """Rounds skipped for a non-finite peer snapshot so far (waits for the device)."""
+        c = ctypes.c_uint64()
+        _lib.call("dpwa_learner_finite_skips", self._h, ctypes.byref(c))
+        return c.value
+
     def read_clock(self):
         c = ctypes.c_double()
         _lib.call("dpwa_learner_read_clock", self._h, ctypes.byref(c))

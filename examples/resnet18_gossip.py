@@ -79,6 +79,10 @@ def main(argv=None):
                     help="measure the distance to the peer for every parameter tensor on every 100th round that "
                          "averages (track_distance='per_parameter', distance_every=100) and print the three "
                          "tensors with the largest relative distance every 100 steps")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="skip (and count) a round whose peer snapshot holds a NaN or an inf, so that one replica that "
+                         "overflowed does not spread through the gossip (skip_nonfinite_peer=True); the count is "
+                         "printed at the end")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -145,6 +149,8 @@ def main(argv=None):
         group["pull"] = args.pull
     if args.top_distances:
         group.update(track_distance="per_parameter", distance_every=100)
+    if args.skip_nonfinite:
+        group.update(skip_nonfinite_peer=True)
     adapters = [DpwaPyTorchAdapter(nets[i], names[g], cfg, seed=100 + g, resident=args.resident, **group)
                 for i, g in enumerate(mine)]
     run(args.warmup, False)
@@ -171,6 +177,7 @@ def main(argv=None):
             "batched_wait": bool(args.batch_wait and len(adapters) > 1),
             "resident": bool(args.resident),
             "final_clock": adapters[0].connection.clock,
+            "nonfinite_skips": [a.nonfinite_skips for a in adapters] if args.skip_nonfinite else None,
         }))
     for a in adapters:
         a.connection.close()

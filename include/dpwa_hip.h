@@ -37,7 +37,11 @@ extern "C" {
  * Still 11, by additions only: the distance to the peer for every parameter tensor (dpwa_param_range)
  * -- dpwa_param_ranges_check, dpwa_param_distance_sizes, dpwa_param_distance_table,
  * dpwa_measure_param_distance, dpwa_param_distance_finish, dpwa_learner_set_param_distance,
- * dpwa_learner_param_distance, dpwa_learner_param_distance_rounds. */
+ * dpwa_learner_param_distance, dpwa_learner_param_distance_rounds.
+ * Still 11, by additions only: skipping a round whose peer snapshot is not finite
+ * (DPWA_STATUS_PEER_NONFINITE, a new value of dpwa_coef.status) -- dpwa_check_finite,
+ * dpwa_check_finite_mixed, dpwa_learner_set_finite_check, dpwa_learner_finite_skips,
+ * dpwa_node_set_finite_check. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -62,6 +66,8 @@ extern "C" {
 /* status written into dpwa_coef.status by the factor kernel */
 #define DPWA_STATUS_OK 0
 #define DPWA_STATUS_ZERO_DIVISION 1   /* the reference raises ZeroDivisionError (dpwa.py:143) */
+#define DPWA_STATUS_PEER_NONFINITE 2  /* no error: the round was skipped because the peer's snapshot held a NaN
+                                         or an inf (dpwa_learner_set_finite_check); never the sticky status */
 
 typedef void *dpwa_stream_t;
 
@@ -244,6 +250,21 @@ int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int6
                          dpwa_distance *out_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
 int dpwa_distance_finish(void *workspace, dpwa_distance *out_dev, const dpwa_coef *coef_dev, int64_t n,
                          dpwa_stream_t stream, void *start_event, void *stop_event);
+
+/* The non-finite check of a peer payload (extension; stateless, for tests and tools -- a learner runs it
+ * itself, dpwa_learner_set_finite_check).  One read of the n elements at `peer_payload`; an element is
+ * non-finite when its exponent field is all ones (fp32 0x7f800000, bf16 0x7f80, fp16 0x7c00; a test
+ * on bit patterns, so NaNs of either kind and +-inf, never a subnormal or the largest finite value).
+ * When there is one, `stamp` (non-zero) is stored into the 32-bit word *veto_dev (device memory,
+ * 4-byte aligned); otherwise the word is left as it was, so a caller that passes a fresh stamp every
+ * time never has to clear it.  dtype DPWA_F32 / BF16 / F16, the payload aligned to its element;
+ * dpwa_check_finite_mixed: a DPWA_MIXED payload (16-B aligned, the layout's bytes; each segment by its
+ * own type, padding is zeros).  Events as dpwa_average.  DPWA_ERR_ARG, no device touched, for NULL
+ * or misaligned pointers, n < 0, stamp 0, an unknown dtype or an invalid layout. */
+int dpwa_check_finite(int32_t dtype, const void *peer_payload, int64_t n, uint32_t *veto_dev, uint32_t stamp,
+                      dpwa_stream_t stream, void *start_event, void *stop_event);
+int dpwa_check_finite_mixed(const dpwa_layout *layout, const void *peer_payload, uint32_t *veto_dev, uint32_t stamp,
+                            dpwa_stream_t stream, void *start_event, void *stop_event);
 
 /* The per-parameter distance (extension, opt-in): the two sums above for every parameter tensor t of
  * the model, over that tensor's own elements only -- dist2_t = sum (double(q_i) - double(p_i))^2 and
@@ -509,6 +530,28 @@ int dpwa_learner_param_distance(dpwa_learner *l, const dpwa_param_distance_head 
  * finishing step were launched.  A measured round that turned out a ZeroDivision no-op counts here
  * and writes no record: the record's `count` stays 0 until a round has written it. */
 int dpwa_learner_param_distance_rounds(dpwa_learner *l, int64_t *averaged, int64_t *measured);
+/* Skipping a round whose peer snapshot is not finite (off by default, and off every launch is the
+ * launch it was and every result bit-equal).  A gossip network spreads a NaN or an inf as it spreads
+ * everything else: a * q + b * p with a non-finite q is non-finite, and after O(log G) rounds so is
+ * every replica.  With set_finite_check(on != 0) -- nothing is allocated, here or in a round -- every
+ * round of this learner that would average first reads the fetched peer snapshot once more (n*s
+ * bytes, one launch: dpwa_check_finite's pass) on the average's stream, behind the fetch and before
+ * the average and any distance pass.  If an element of it is NaN or +-inf the round is the no-op
+ * round of a ZeroDivision -- parameters untouched, a write-through or resident snapshot receives the
+ * unchanged parameters, clock unchanged, the distance records left alone -- but it is no error:
+ * dpwa_coef.status is DPWA_STATUS_PEER_NONFINITE, the sticky status word stays 0, and the round is
+ * counted (finite_skips: the count since dpwa_learner_create; it waits for the device).  A ZeroDivision
+ * round stays one, whatever the peer holds.  Where it runs: dpwa_learner_average / average_through
+ * (resident and DPWA_MIXED included), once per checking learner before a dispatch of
+ * dpwa_learner_average_many, and before the factor in dpwa_learner_factor, so that dpwa_learner_lerp
+ * skips through the coefficients it reads anyway.  A caller that does the arithmetic itself after
+ * dpwa_learner_factor gets factor 0, and 0 * NaN is NaN: use dpwa_learner_lerp.  The learner's own
+ * parameters are not looked at: a replica that is itself non-finite is not healed, its peers stop
+ * taking from it.  The relay's fused second phase reads no contiguous snapshot: dpwa_learner_relay_phase2
+ * with fuse != 0 on a checking learner is DPWA_ERR_STATE, and so is set_finite_check(on) while a fused
+ * second phase is pending.  dpwa_node_set_finite_check: the same on a bound node's learner. */
+int dpwa_learner_set_finite_check(dpwa_learner *l, int on);
+int dpwa_learner_finite_skips(dpwa_learner *l, uint64_t *count);
 
 /* always != 0: a write-through average never writes the next publish's header ahead; that
  * publish then writes it with the loss given to it (a snapshot served over the wire bridge
@@ -814,6 +857,9 @@ int dpwa_node_update_wait_average_many(dpwa_node *const *nodes, void *const *fla
  * dpwa_learner_resident_params before the call) and relocates the parameters in a round without
  * an average; its split update_wait is refused. */
 int dpwa_node_set_resident(dpwa_node *n, const void *init, dpwa_stream_t stream);
+/* dpwa_learner_set_finite_check on the node's learner (DPWA_ERR_STATE before dpwa_node_bind).  The
+ * scheduler is not told of a skipped round: the fetch outcome was reported before the device looked. */
+int dpwa_node_set_finite_check(dpwa_node *n, int on);
 /* State of the current/last round: fetching flag, fetched peer (-1: none), its publish
  * number, and the picks the last fetch took. */
 int dpwa_node_info(const dpwa_node *n, int *fetching, int *fetch_peer, uint64_t *fetch_version,
