@@ -1037,6 +1037,11 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
     if (peer_version == 0) return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: peer %d has not published", peer_id);
     Endpoint &ep = it->second;
     if (ep.kind == 1 && !is_live(ep.local)) return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: peer %d was destroyed", peer_id);
+    // The non-finite check of a split round ran in dpwa_learner_factor, on the snapshot then in flight: a lerp
+    // with those coefficients against a snapshot that no pass has read could write a NaN the check promises not to
+    if (l->finite_check && l->fetch.factored())
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: a factor is computed and the learner skips non-finite peers "
+                                         "(dpwa_learner_set_finite_check): lerp or cancel first");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
     const int k = (int)((peer_version - 1) % 2);
@@ -1433,6 +1438,10 @@ int dpwa_learner_set_finite_check(dpwa_learner *l, int on)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_set_finite_check: a fused relay second phase is pending "
                                          "(dpwa_learner_relay_phase2 with fuse != 0), which reads no contiguous peer "
                                          "snapshot to check");
+    // (coefficients computed while the check was off come from no pass: the lerp they belong to would go unchecked)
+    if (on && l->fetch.factored())
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_set_finite_check: a factor is computed for the fetch in flight: "
+                                         "lerp or cancel first");
     l->finite_check = on != 0;
     return DPWA_OK;
 }

@@ -337,6 +337,10 @@ static void refresh_status(dpwa_node *n)
 
 static int start_fetch(dpwa_node *n, int flags, dpwa_stream_t stream)
 {
+    if (n->awaiting_lerp) {   // as dpwa_node_publish: a checking learner refuses a fetch over a computed factor
+        dpwa_learner_cancel(n->learner);
+        n->awaiting_lerp = false;
+    }
     n->fetch_started = true;
     n->fetch_peer = -1;
     n->reply_pending = false;

@@ -547,7 +547,11 @@ int dpwa_learner_param_distance_rounds(dpwa_learner *l, int64_t *averaged, int64
  * skips through the coefficients it reads anyway.  A caller that does the arithmetic itself after
  * dpwa_learner_factor gets factor 0, and 0 * NaN is NaN: use dpwa_learner_lerp.  The learner's own
  * parameters are not looked at: a replica that is itself non-finite is not healed, its peers stop
- * taking from it.  The relay's fused second phase reads no contiguous snapshot: dpwa_learner_relay_phase2
+ * taking from it.  The pass of a split round is the factor's, so the snapshot it read must be the one the
+ * lerp averages: on a checking learner dpwa_learner_fetch while a factor is computed and not yet consumed
+ * is DPWA_ERR_STATE (nothing moves; lerp or cancel first), and so is set_finite_check(on) then; with the
+ * check off a second fetch keeps the factor, as before.
+ * The relay's fused second phase reads no contiguous snapshot: dpwa_learner_relay_phase2
  * with fuse != 0 on a checking learner is DPWA_ERR_STATE, and so is set_finite_check(on) while a fused
  * second phase is pending.  dpwa_node_set_finite_check: the same on a bound node's learner. */
 int dpwa_learner_set_finite_check(dpwa_learner *l, int on);

@@ -52,6 +52,10 @@ struct dpwa_learner {
     int peer = -1;
     uint64_t peer_version = 0;
     int pulls = 0, rescue_pulls = 0, averages = 0, relocations = 0;
+    // a learner that skips non-finite peers (fake_check) refuses a fetch over a computed factor, as
+    // learner.cpp's dpwa_learner_fetch does
+    bool check = false, factored = false;
+    int cancels = 0;
 };
 
 extern "C" {
@@ -80,6 +84,20 @@ int fake_lanes(dpwa_learner *l, int cap, int land_after)   // lane cap; polls un
     l->cap = cap < l->lanes ? l->lanes : cap;
     l->land_after = land_after;
     l->polls = 0;
+    return DPWA_OK;
+}
+
+int fake_check(dpwa_learner *l, int on)   // dpwa_learner_set_finite_check
+{
+    if (!l) return DPWA_ERR_ARG;
+    l->check = on != 0;
+    return DPWA_OK;
+}
+
+int fake_cancels(dpwa_learner *l, int *out)
+{
+    if (!l || !out) return DPWA_ERR_ARG;
+    *out = l->cancels;
     return DPWA_OK;
 }
 
@@ -146,6 +164,7 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
 {
     if (!l) return set_error(DPWA_ERR_ARG, "fetch");
     if (peer_version == 0) return set_error(DPWA_ERR_STATE, "fetch: peer %d has not published", peer_id);
+    if (l->check && l->factored) return set_error(DPWA_ERR_STATE, "fetch: a factor is computed: lerp or cancel first");
     const bool stalled = l->stall_next > 0;
     if (stalled) l->stall_next--;
     if (flags & DPWA_FETCH_RESCUE) {
@@ -200,6 +219,8 @@ int dpwa_learner_cancel(dpwa_learner *l)
 {
     if (!l) return set_error(DPWA_ERR_ARG, "cancel");
     l->have_fetch = false;
+    l->factored = false;
+    l->cancels++;
     return DPWA_OK;
 }
 
@@ -208,15 +229,23 @@ static int averaged(dpwa_learner *l)
     if (!l) return set_error(DPWA_ERR_ARG, "average");
     if (!l->have_fetch) return set_error(DPWA_ERR_STATE, "average: no fetch in flight");
     l->have_fetch = false;
+    l->factored = false;
     l->averages++;
     return DPWA_OK;
 }
 
 int dpwa_learner_factor(dpwa_learner *l, double, const double *, dpwa_stream_t)
 {
-    return l && l->have_fetch ? DPWA_OK : set_error(DPWA_ERR_STATE, "factor");
+    if (!l || !l->have_fetch) return set_error(DPWA_ERR_STATE, "factor");
+    if (l->factored) return set_error(DPWA_ERR_STATE, "factor: factor already computed for this fetch");
+    l->factored = true;
+    return DPWA_OK;
 }
-int dpwa_learner_lerp(dpwa_learner *l, void *, dpwa_stream_t) { return averaged(l); }
+int dpwa_learner_lerp(dpwa_learner *l, void *, dpwa_stream_t)
+{
+    if (!l || !l->factored) return set_error(DPWA_ERR_STATE, "lerp: no factor computed for this fetch");
+    return averaged(l);
+}
 int dpwa_learner_average(dpwa_learner *l, void *, double, const double *, dpwa_stream_t) { return averaged(l); }
 int dpwa_learner_average_through(dpwa_learner *l, void *, double, const double *, dpwa_stream_t) { return averaged(l); }
 

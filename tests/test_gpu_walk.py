@@ -5,8 +5,13 @@ model's; then, with the device synchronised, every learner's parameter bits and 
 snapshot slots (header fields and payload, read as a peer reads them: an observer learner fetches the
 slot and is cancelled), dpwa_learner_read_snapshot, the version, the clock, the coefficients, where
 resident parameters are and the distance record (tests/dist_ref.problem, its workspace all zero) are
-the model's -- after a refused call too, which must have changed none of them.  The bar is bit
-equality with the host references (NaN positions coincide), and dist_ref.bound for the two sums.
+the model's -- after a refused call too, which must have changed none of them.  So are what the two
+opt-ins show: dpwa_learner_finite_skips, the sticky status word (read where dpwa_learner_status_word
+points, never polled), dpwa_learner_param_distance_rounds and the per-parameter record (its clock and
+count; each tensor's pair against tests/pdist_ref.reference with dist_ref.bound of that tensor's own
+elements).  The bar is bit equality with the host references (NaN positions coincide), and
+dist_ref.bound for the sums.  A "step" of the model is the caller's own write of its parameters: a copy
+on that learner's stream.
 
 The second pass gives every learner a stream of its own and compares only every SYNC_EVERY calls, so
 that work of several learners is in flight together; before each publish, write-through average and
@@ -94,6 +99,9 @@ class Node:
             self.factor_out = torch.zeros(1, dtype=torch.float64, device=DEV)
         self.slot_ptr = {}
         self.dist_ptr = None
+        word = ctypes.c_void_p()
+        _lib.call("dpwa_learner_status_word", self.h, ctypes.byref(word))
+        self.status_word = ctypes.cast(word.value, ctypes.POINTER(ctypes.c_int32))
 
     def close(self):
         if self.h:
@@ -138,6 +146,7 @@ class Group:
             raise
         self.streams = [torch.cuda.Stream(DEV) for _ in self.nodes] if streams else None
         self.model = W.Model(spec)
+        self.ranges = None         # the dpwa_param_range list of set_param_distance, made at its first use
         self.done = []
         self.pending = []          # outputs of copy_fetched / copy_factor not compared yet
         self.compared = -1         # index of the last call after which the whole state was compared
@@ -219,6 +228,23 @@ class Group:
             return self.c("dpwa_learner_set_distance", N[a[0]].h, int(a[1]))
         if name == "set_header_publish":
             return self.c("dpwa_learner_set_header_publish", N[a[0]].h, int(a[1]))
+        if name == "set_finite_check":
+            return self.c("dpwa_learner_set_finite_check", N[a[0]].h, int(a[1]))
+        if name == "set_param_distance":
+            i, every = a
+            if every == 0:
+                return self.c("dpwa_learner_set_param_distance", N[i].h, None, 0, 1)
+            if self.ranges is None:
+                rs = self.spec.param_ranges()
+                self.ranges = (_lib.ParamRange * len(rs))(*[_lib.ParamRange(off, length, code, 0) for off, length, code in rs])
+            return self.c("dpwa_learner_set_param_distance", N[i].h, self.ranges, len(self.ranges), int(every))
+        if name == "step":
+            i, flat, bits = a
+            raw = torch.from_numpy(np.ascontiguousarray(bits).view(np.uint8))
+            dst = N[i].view(N[i].resident()[0], self.spec.nbytes) if flat == "res" else N[i].flats[flat]
+            with torch.cuda.stream(self.streams[i] if self.streams else torch.cuda.current_stream()):
+                dst.copy_(raw)
+            return W.OK
         if name == "set_resident":
             i = a[0]
             return self.c("dpwa_learner_set_resident", N[i].h, vp(self.ptr(i, a[1] if len(a) > 1 else 0)), self.stream(i))
@@ -326,6 +352,37 @@ class Group:
                 if sp.nbytes:
                     self.check_payload(host(node.view(ptr, sp.nbytes)), l.slots[slot].payload, who + " resident parameters")
             self.compare_distance(i)
+            self.compare_options(i)
+
+    def compare_options(self, i):
+        """What the non-finite check and the per-parameter distance show (the device is synchronised)."""
+        node, l, sp = self.nodes[i], self.model.L[i], self.spec
+        who = "learner %d:" % i
+        skips = ctypes.c_uint64()
+        _lib.call("dpwa_learner_finite_skips", node.h, ctypes.byref(skips))
+        self.check(skips.value == l.skips, who, "finite_skips", skips.value, "expected", l.skips)
+        self.check(node.status_word[0] == l.sticky, who, "the sticky status word is", node.status_word[0], "expected", l.sticky)
+        averaged, measured = ctypes.c_int64(), ctypes.c_int64()
+        _lib.call("dpwa_learner_param_distance_rounds", node.h, ctypes.byref(averaged), ctypes.byref(measured))
+        self.check((averaged.value, measured.value) == l.pd_rounds, who, "param_distance_rounds", averaged.value,
+                   measured.value, "expected", l.pd_rounds)
+        p, count = ctypes.c_void_p(), ctypes.c_int64()
+        rc = self.c("dpwa_learner_param_distance", node.h, ctypes.byref(p), ctypes.byref(count))
+        self.check(rc == (W.ERR_STATE if l.pd is None else W.OK), who, "dpwa_learner_param_distance returned", rc)
+        if l.pd is None:
+            return
+        clock, written, pairs = l.pd
+        lay = sp.param_layout()
+        self.check(count.value == len(pairs), who, "per-parameter tensor count", count.value, "expected", len(pairs))
+        raw = host(node.view(p.value, 16 + 16 * len(pairs)))
+        head = np.frombuffer(raw[:16].tobytes(), dtype=[("clock", "<f8"), ("count", "<i8")])[0]
+        got = np.frombuffer(raw[16:].tobytes(), dtype="<f8").reshape(-1, 2)
+        self.check(same_double(float(head["clock"]), clock) and int(head["count"]) == written, who, "per-parameter record clock, count",
+                   head["clock"], head["count"], "expected", clock, written)
+        for t, (want_d2, want_n2) in enumerate(pairs):
+            for name, g, want in (("dist2", got[t, 0], want_d2), ("norm2", got[t, 1], want_n2)):
+                why = dist_ref.problem(float(g), want, max(lay.elements(t), 1))
+                self.check(why is None, who, "per-parameter record, tensor %d %s:" % (t, name), why)
 
     def compare_slots(self, i):
         """Both slots of learner i as a peer reads them: its observer fetches slot k (a version of that
@@ -372,8 +429,10 @@ class Group:
             want = self.model.apply(op)
             self.done.append(op)
             got = self.call(op)
-            self.check(got == want, "call", op, "returned", got, "(%s)" % self.lib.dpwa_last_error().decode(errors="replace"),
-                       "expected", want, "rule", self.model.rule)
+            # (the library's message belongs to its last refusal: shown only when this call was refused)
+            said = "(%s)" % self.lib.dpwa_last_error().decode(errors="replace") if got != W.OK else ""
+            self.check(got == want, "call", op[:3] if op[0] == "step" else op, "returned", got, said, "expected", want,
+                       "rule", self.model.rule)
             if op[0] in ("copy_fetched", "copy_factor") and got == W.OK:
                 self.pending_want[self.pending[-1]] = self.model.out
             if op[0] == "read_snapshot":
@@ -406,12 +465,26 @@ def run_walk(name, spec, ops, streams=False):
 
 DIRECTED = tuple(W.directed())
 SECOND_PASS_WALKS = tuple(next(w for w in W.WALKS if w[0] == p) for p in W.PROFILES)
+# with the check on every walk runs in the second pass too, the unaligned one included: a pass that lacks its
+# ordering edge to the peer's publish reads the old finite bytes behind the held producer and lets the poison through
 
 
 @pytest.mark.parametrize("walk", W.WALKS, ids=W.walk_id)
 def test_walk(walk):
     spec, ops = W.walk_of(walk)
     run_walk(W.walk_id(walk), spec, ops)
+
+
+@pytest.mark.parametrize("walk", W.CHECK_WALKS, ids=W.walk_id)
+def test_checking_walk(walk):
+    spec, ops = W.walk_of(walk)
+    run_walk(W.walk_id(walk), spec, ops)
+
+
+@pytest.mark.parametrize("walk", W.CHECK_WALKS, ids=W.walk_id)
+def test_checking_walk_on_separate_streams(walk):
+    spec, ops = W.walk_of(walk)
+    run_walk(W.walk_id(walk) + " (separate streams)", spec, ops, streams=True)
 
 
 @pytest.mark.parametrize("name", DIRECTED)

@@ -26,14 +26,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
 
 
-@pytest.fixture(scope="module")
-def node_stress(tmp_path_factory):
+def _build(tmp_path_factory, driver):
+    """node.cpp, the scheduler and the fake learner with tests/native/<driver>.cpp, under the sanitizers."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("node") / "node_stress")
+    exe = str(tmp_path_factory.mktemp("node") / driver)
     srcs = ["dpwa_amd/csrc/node.cpp", "dpwa_amd/csrc/sched.cpp", "dpwa_amd/csrc/trace.cpp",
-            "tests/native/fake_learner.cpp", "tests/native/node_stress.cpp"]
+            "tests/native/fake_learner.cpp", "tests/native/%s.cpp" % driver]
     cmd = [gxx, "-std=c++17", "-O1", "-g", *SAN, "-I", os.path.join(ROOT, "include"),
            *[os.path.join(ROOT, s) for s in srcs], "-o", exe, "-ldl", "-lpthread"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -41,6 +41,22 @@ def node_stress(tmp_path_factory):
         pytest.skip("sanitizer runtime not installed: " + r.stderr[-200:])
     assert r.returncode == 0, r.stderr
     return exe
+
+
+@pytest.fixture(scope="module")
+def node_stress(tmp_path_factory):
+    return _build(tmp_path_factory, "node_stress")
+
+
+def test_a_node_never_fetches_over_a_factor_whose_lerp_was_not_issued(tmp_path_factory):
+    """A learner that skips non-finite peers refuses a fetch over a computed factor (learner.cpp,
+    dpwa_learner_fetch; the fake learner does the same).  After an update_wait without its lerp, a publish
+    abandons that factor, and so does an eager gate before it fetches: tests/native/node_lerp_check.cpp
+    counts the cancels and the pulls."""
+    exe = _build(tmp_path_factory, "node_lerp_check")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "node lerp check ok" in r.stderr, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def _run(exe, G, rounds, seed, fp, fault_pct=0, prefetch=0):

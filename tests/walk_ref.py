@@ -10,6 +10,13 @@ factored), the pending written-through snapshot (for which ``flat``, with or wit
 An operation is a tuple (``OPS`` below); ``Model.apply(op)`` returns the expected return code and
 moves the state, and a refused call moves nothing.
 
+The two opt-ins that keep state between calls are in the model too: the non-finite peer check (its
+switch, the skip counter, the sticky status word, DPWA_STATUS_PEER_NONFINITE in the coefficients) and the
+per-parameter distance (its record, ``every`` and the two host counters).  A walk reaches them only when
+its ``Spec`` asks (``draws``); a learner's parameters are poisoned and healed with the ``step`` op, whose
+bits ``poisoned`` and ``healed`` make from what the model holds.  Whether a payload vetoes comes from
+``tests/finite_ref`` and the per-tensor sums from ``tests/pdist_ref``.
+
 No arithmetic is restated here.  The factor, the status and the clock come from
 ``oracle.policy.factor_and_clock`` as ``tests/factor_ref.evaluate`` reads it; the averaged bits from
 ``tests/forms_ref.lerp`` (``oracle.lerp``, ``tests/f16_ref``) and ``tests/mixed_ref.lerp``; the
@@ -39,7 +46,7 @@ import random
 
 import numpy as np
 
-from tests import dist_ref, factor_ref, mixed_ref
+from tests import dist_ref, factor_ref, finite_ref, mixed_ref, pdist_ref
 from tests import forms_ref as fref
 
 OK, ERR_ARG, ERR_STATE = 0, -1, -3
@@ -49,17 +56,30 @@ FETCH_KINDS = ("ce", "k1", "k512", "zc")      # copy engine, DPWA_PULL_KERNEL wi
 MAIN = ("publish", "publish_reuse", "fetch", "factor", "lerp", "average", "average_through", "cancel", "relocate",
         "write_clock")
 OTHER = ("average_many", "copy_fetched", "copy_factor", "read_snapshot", "set_distance", "set_header_publish",
-         "set_resident", "step")
+         "set_resident", "step", "set_finite_check", "set_param_distance")
 OPS = MAIN + OTHER
 AVERAGING = ("lerp", "average", "average_through", "average_many")
 MIXED_SPEC = (("f32", 261), ("bf16", 521))     # two segments of one 4-KiB block each: 8 KiB
 SIZES = {"f32": 261, "bf16": 521, "f16": 521, "mixed": 8192}   # one 1-KiB span and a ragged tail
 DTYPES = ("f32", "bf16", "f16", "mixed")
+STATUS_ZD, STATUS_SKIPPED = 1, 2               # DPWA_STATUS_ZERO_DIVISION, DPWA_STATUS_PEER_NONFINITE
+
+# The parameter tensors of dpwa_learner_set_param_distance, one fixed list per dtype (elements; pdist_ref lays
+# each on a 256-byte boundary): tensor 0 ends inside the first 1-KiB span, tensor 1 is empty, tensor 2 ends
+# 112 bytes before tensor 3 begins (a gap, like the 16 bytes behind tensor 0), tensor 3 crosses the span
+# boundary and ends with the payload's ragged tail.  A segmented payload holds the same four in each segment.
+PARAM_SIZES = {"f32": (60, 0, 100, 69), "bf16": (120, 0, 200, 137), "f16": (120, 0, 200, 137)}
+GAP_ELEMENT = {"f32": 170, "bf16": 340, "f16": 340}     # byte 680: between tensors 2 and 3
+# Where a walk poisons a payload: name -> (segment dtype or None, element index)
+POISON_AT = {d: {"first": (None, 0), "span-last": (None, finite_ref.SPAN[d] - 1), "tail-last": (None, SIZES[d] - 1),
+                 "gap": (None, GAP_ELEMENT[d])} for d in ("f32", "bf16", "f16")}
+POISON_AT["mixed"] = {"f32-first": ("f32", 0), "bf16-last": ("bf16", 520), "f32-gap": ("f32", GAP_ELEMENT["f32"])}
+POISON_KINDS = ("snan", "qnan", "+inf", "-inf")
 
 # The refusal rules: name -> (return code, file, a fragment of the line that decides it: its condition, or
 # the name of its message).  tests/test_walk_host.py checks that every cited fragment is in the file.
 # (One line of average_prepare decides both average-without-fetch and average-after-factor.)
-H, LC, FH = "include/dpwa_hip.h", "dpwa_amd/csrc/learner.cpp", "dpwa_amd/csrc/fetch.hpp"
+H, LC, FH, MH = "include/dpwa_hip.h", "dpwa_amd/csrc/learner.cpp", "dpwa_amd/csrc/fetch.hpp", "dpwa_amd/csrc/measure.hpp"
 RULES = {
     "factor-without-fetch": (ERR_STATE, LC, '"dpwa_learner_factor: no fetch in flight"'),
     "factor-twice": (ERR_STATE, LC, '"dpwa_learner_factor: factor already computed'),
@@ -78,6 +98,12 @@ RULES = {
     "fetch-slot-never-published": (ERR_STATE, LC, "if (!pl->published[k].noted())"),
     "set-resident-twice": (ERR_STATE, LC, '"dpwa_learner_set_resident: already resident"'),
     "set-resident-late": (ERR_STATE, LC, "if (l->version != 0 || l->fetch.fetched())"),
+    # a checking learner's split round: the pass ran in the factor, on the snapshot then in flight
+    "fetch-over-checked-factor": (ERR_STATE, LC, "if (l->finite_check && l->fetch.factored())"),
+    "set-check-over-factor": (ERR_STATE, LC, "if (on && l->fetch.factored())"),
+    # average_prepare and dpwa_learner_lerp ask Measure::operands_problem behind their state and layout
+    # refusals and before the resident pointer and the slot's readers
+    "param-unaligned": (ERR_ARG, MH, "if (!param_ || aligned16(flat)) return DPWA_OK;"),
     # not refusals: what the model keeps because the code does
     "second-fetch-keeps-factor": (None, FH, "if (phase_ == Phase::None) phase_ = Phase::Fetched;"),
     "write-clock-drops-header": (None, LC, "l->wt_header = false;   // the next header was written from the old clock"),
@@ -85,6 +111,12 @@ RULES = {
     "no-op-round-writes-snapshot": (None, "dpwa_amd/csrc/kernels.hip", "if (MODE == COEF_FUSED && DUAL) {   // no-op round"),
     "many-prepares-all-first": (None, LC, "if (rc) return rc;   // nothing launched yet for this learner"),
     "distance-before-the-average": (None, "dpwa_amd/csrc/measure.hpp", "if (int rc = ms[i].m->before(ms[i].p, ms[i].flat, ms[i].peer, fused, s)) return rc;"),
+    "skip-is-the-no-op-round": (None, "dpwa_amd/csrc/kernels.hip", "if (vetoed && c.status == DPWA_STATUS_OK) {"),
+    "skip-is-no-error": (None, "dpwa_amd/csrc/kernels.hip", "if (fa.status_mirror && c.status == DPWA_STATUS_ZERO_DIVISION) *fa.status_mirror = c.status;"),
+    "many-checks-each-member": (None, LC, "if (int rc = finite_pass(checker[i], b.e[i].fa, b.e[i].peer, s)) return rc;"),
+    "param-round-counted-at-launch": (None, MH, "if (param_) pd_.due = ++pd_.rounds % pd_.every == 0;"),
+    "param-record-only-when-ok": (None, H, "the record is written only when"),
+    "param-on-again-starts-anew": (None, MH, "pd_ = Param{count, workspace_off, record_off, every};"),
 }
 # (resident-not-in-next-slot cannot fire: a resident publish relocates first, which notes the written-through
 # snapshot; it is what the mutant resident-publish-no-relocate runs into)
@@ -102,7 +134,22 @@ MUTANTS = (
     "write-clock-keeps-header",
     "distance-after-the-lerp",          # the record taken from the averaged parameters
     "distance-against-staging",         # an in-place fetch measured against what the last copy left in staging
+    "skip-moves-clock",
+    "skip-writes-whole-record",
+    "skip-writes-param-record",
+    "skip-leaves-snapshot-stale",       # a write-through or resident skipped round does not write the slot
+    "stale-veto",                       # a veto outlives its round: once vetoed, every later checked round is
+    "check-reads-own-params",
+    "zero-division-loses-precedence",
+    "skip-sets-sticky-status",
+    "many-shares-one-veto",
+    "many-checks-first-member-only",
+    "param-every-off-by-one",
+    "param-reset-keeps-counters",
+    "param-record-after-the-lerp",
+    "lerp-after-second-fetch-unchecked",   # the code before this model's fix
 )
+NEW_MUTANTS = MUTANTS[MUTANTS.index("skip-moves-clock"):]
 # how a round that wrote the distance record averaged (Model.measured)
 MEASURING = ("average", "average_through", "lerp", "resident", "many-batched", "many-unbatched", "unaligned")
 
@@ -112,11 +159,14 @@ class Spec:
     behind a 16-byte boundary the flat buffers begin (elements), which learners are resident."""
 
     def __init__(self, dtype, method, value=None, threshold=0.0, n=None, offset=0, resident=(), learners=3, seed=1,
-                 finite=False):
+                 finite=False, draws=()):
         self.dtype, self.method, self.value, self.threshold = dtype, method, value, threshold
         self.n = SIZES[dtype] if n is None else n
         self.offset, self.resident, self.learners, self.seed = offset, tuple(resident), learners, seed
         self.finite = finite          # operands without NaNs and infinities: the distance sums are finite
+        # what a walk draws besides the calls it always drew: "check" (set_finite_check; on finite operands
+        # poisoning and healing steps too), "param" (set_param_distance)
+        self.draws = tuple(draws)
         assert dtype != "mixed" or (offset == 0 and self.n in (0, SIZES["mixed"]))
 
     @property
@@ -197,6 +247,40 @@ class Spec:
             return mixed_ref.same(MIXED_SPEC, np.asarray(got), np.asarray(want)) is None
         return fref.same(self.dtype, np.asarray(got), np.asarray(want))
 
+    def nonfinite(self, payload):
+        """Per element (per byte of a segmented payload): a NaN or an infinity, by finite_ref's rule."""
+        if self.dtype != "mixed":
+            return finite_ref.nonfinite(self.dtype, payload)
+        out = np.zeros(len(payload), bool)
+        for d, off, length, _ in mixed_ref.segments(MIXED_SPEC)[0] if self.n else ():
+            bad = finite_ref.nonfinite(d, np.ascontiguousarray(payload[off:off + length]).view(finite_ref.NUMPY[d]))
+            out[off:off + length] = np.repeat(bad, finite_ref.SIZE[d])
+        return out
+
+    def vetoes(self, payload):
+        """finite_ref's answer for a peer payload (a segmented one: every byte of every segment)."""
+        if self.n == 0:
+            return False
+        if self.dtype != "mixed":
+            return finite_ref.vetoes(self.dtype, payload)
+        return finite_ref.vetoes_mixed(mixed_ref.segments(MIXED_SPEC)[0], payload)
+
+    def param_layout(self):
+        """The parameter tensors as pdist_ref lays them out (PARAM_SIZES)."""
+        assert self.n == SIZES[self.dtype]
+        if self.dtype == "mixed":
+            return pdist_ref.mixed("walk", {d: list(PARAM_SIZES[d]) for d, _ in MIXED_SPEC})
+        return pdist_ref.ragged("walk", self.dtype, list(PARAM_SIZES[self.dtype]))
+
+    def param_ranges(self):
+        """[(byte offset, byte length, dtype code)] for dpwa_learner_set_param_distance."""
+        return [(off, length, fref.CODE[d]) for _, d, off, length in self.param_layout().tensors]
+
+    def param_distance(self, p, q):
+        """((dist2, norm2), ...) per tensor: pdist_ref.reference."""
+        as_bytes = lambda x: np.ascontiguousarray(x).view(np.uint8)                    # noqa: E731
+        return tuple(pdist_ref.reference(self.param_layout(), as_bytes(p), as_bytes(q)))
+
     def distance(self, p, q):
         if self.dtype != "mixed":
             return dist_ref.reference(self.dtype, p, q)
@@ -242,6 +326,14 @@ class Learner:
         self.dist_on = False
         self.dist = None             # the record (dist2, norm2, clock, n) once tracking was ever on
         self.staged = None           # what the last copying fetch left in staging (no caller reads it there)
+        self.check = False           # dpwa_learner_set_finite_check
+        self.skips = 0               # dpwa_learner_finite_skips
+        self.sticky = 0              # the sticky status word (no walk polls it, so it is never cleared)
+        self.vetoed_once = False     # (only the mutant stale-veto reads it)
+        self.pd_on = False           # dpwa_learner_set_param_distance
+        self.pd_every = 1
+        self.pd = None               # the record (clock, count, pairs) once the option was ever on
+        self.pd_rounds = (0, 0)      # dpwa_learner_param_distance_rounds: averaged, measured
 
 
 class Model:
@@ -253,6 +345,8 @@ class Model:
         self.out = None              # what the last copy_fetched / copy_factor / read_snapshot gave
         self.changed = False         # the last averaging call ended OK and changed the parameters
         self.measured = []           # (learner, MEASURING form) of the records the last call wrote
+        self.skipped = []            # (learner, MEASURING form, poison_tags of the snapshot) of the rounds it skipped
+        self.checked = 0             # checked rounds of the last call that averaged
 
     def copy(self):
         return copy.deepcopy(self)
@@ -296,6 +390,34 @@ class Model:
         f, new_clock, a, b = want
         return (f, new_clock, float(a), float(b), 0)
 
+    def _vetoes(self, l, p, q):
+        """Does the pass of a round of learner l veto it?  q: the snapshot read, p: its own parameters."""
+        if not l.check:
+            return False
+        bad = self.spec.vetoes(q)
+        if self.mutant == "check-reads-own-params":
+            bad = bad or self.spec.vetoes(p)
+        if self.mutant == "stale-veto":
+            bad = bad or l.vetoed_once
+        l.vetoed_once = l.vetoed_once or bad
+        return bad
+
+    def _round_coef(self, l, header, loss, vetoed):
+        """fused_factor: the coefficients of a round whose pass said `vetoed`; counts a skip, sets the sticky word."""
+        c = self._coef(l, header, loss)
+        if c[4] == STATUS_ZD:
+            if vetoed and self.mutant == "zero-division-loses-precedence":
+                c = c[:4] + (STATUS_SKIPPED,)
+                l.skips += 1
+            else:
+                l.sticky = STATUS_ZD
+        elif vetoed:
+            c = (0.0, c[1] if self.mutant == "skip-moves-clock" else l.clock[l.cur], 0.0, 1.0, STATUS_SKIPPED)
+            l.skips += 1
+            if self.mutant == "skip-sets-sticky-status":
+                l.sticky = STATUS_SKIPPED
+        return c
+
     def _finish(self, l):
         l.fetch = None
         l.reading = None
@@ -303,20 +425,32 @@ class Model:
     def _record(self, l, p, q, form, after=None):
         """The record of a round that averaged: p and q as they were before it (measure.hpp: the pass runs
         before the average, the tracked kernel sums the operands it loaded)."""
-        if l.dist_on and l.coef[4] == 0:
+        i, status = self.L.index(l), l.coef[4]
+        forms = (form,) + (("unaligned",) if self.spec.offset and not l.resident else ())
+        if status == STATUS_SKIPPED:
+            self.skipped += [(i, f, poison_tags(self.spec, q)) for f in forms]
+        elif status == 0 and l.check:
+            self.checked += 1
+        if l.pd_on:     # Measure::before counts the round that launches, whatever it turns out to be
+            rounds = l.pd_rounds[0] + 1
+            due = (rounds + (1 if self.mutant == "param-every-off-by-one" else 0)) % l.pd_every == 0
+            l.pd_rounds = (rounds, l.pd_rounds[1] + int(due))
+            if due and (status == 0 or (status == STATUS_SKIPPED and self.mutant == "skip-writes-param-record")):
+                pp = after if self.mutant == "param-record-after-the-lerp" and after is not None else p
+                pairs = self.spec.param_distance(pp, q)
+                l.pd = (l.coef[1], len(pairs), pairs)
+        if l.dist_on and (status == 0 or (status == STATUS_SKIPPED and self.mutant == "skip-writes-whole-record")):
             if self.mutant == "distance-after-the-lerp" and after is not None:
                 p = after
             if self.mutant == "distance-against-staging" and not l.fetch.copied and l.staged is not None:
                 q = l.staged
             d2, n2 = self.spec.distance(p, q)
             l.dist = (d2, n2, l.coef[1], self.spec.distance_n())
-            self.measured.append((self.L.index(l), form))
-            if self.spec.offset and not l.resident:
-                self.measured.append((self.L.index(l), "unaligned"))
+            self.measured += [(i, f) for f in forms]
 
     # ------------------------------------------------------------------ the calls
     def apply(self, op):
-        self.rule, self.out, self.changed, self.measured = None, None, False, []
+        self.rule, self.out, self.changed, self.measured, self.skipped, self.checked = None, None, False, [], [], 0
         return getattr(self, "_" + op[0])(*op[1:])
 
     def _step(self, i, flat, bits):
@@ -396,6 +530,8 @@ class Model:
         assert i != j and kind in FETCH_KINDS
         if version == 0:
             return self._refuse("fetch-version-0")
+        if l.check and l.fetch is not None and l.fetch.factored and self.mutant != "lerp-after-second-fetch-unchecked":
+            return self._refuse("fetch-over-checked-factor")
         k = (version - 1) % 2
         if not peer.slots[k].published:
             return self._refuse("fetch-slot-never-published")
@@ -415,8 +551,9 @@ class Model:
             return self._refuse("factor-without-fetch")
         if l.fetch.factored:
             return self._refuse("factor-twice")
-        header, _ = self.source(i)
-        l.coef = self._coef(l, header, loss)
+        header, q = self.source(i)
+        # (whatever flat the lerp will name: the mutant that reads the learner's own parameters reads flat 0)
+        l.coef = self._round_coef(l, header, loss, self._vetoes(l, self.params(i, self.params_key(i, "res" if l.resident else 0)), q))
         l.clock[(l.cur + 1) & 3] = l.coef[1]
         l.cur = (l.cur + 1) & 3
         l.fetch.factored = True
@@ -431,11 +568,13 @@ class Model:
         if l.resident:
             return self._refuse("lerp-resident")
         assert flat != "res"
+        if l.pd_on and self.spec.offset:
+            return self._refuse("param-unaligned")
         _, q = self.source(i)
         p = l.flats[flat]
+        r = self.spec.lerp(p, q, l.coef[0]) if l.coef[4] == 0 else p
+        self._record(l, p, q, "lerp", r)
         if l.coef[4] == 0:
-            r = self.spec.lerp(p, q, l.coef[0])
-            self._record(l, p, q, "lerp", r)
             self.changed = r.tobytes() != p.tobytes()
             l.flats[flat] = r
         if self.mutant != "lerp-keeps-written-through":
@@ -450,6 +589,8 @@ class Model:
             return self._refuse("average-without-fetch")
         if l.fetch.factored:
             return self._refuse("average-after-factor")
+        if l.pd_on and flat != "res" and self.spec.offset:
+            return self._refuse("param-unaligned")
         if l.resident:
             if flat != "res":
                 return self._refuse("resident-average-pointer")
@@ -460,14 +601,14 @@ class Model:
             return self._refuse("slot-still-read")
         return OK
 
-    def _average_commit(self, i, flat, loss, through, form=None):
+    def _average_commit(self, i, flat, loss, through, form=None, vetoed=None):
         l, sp = self.L[i], self.spec
         oop = l.resident
         through = through or oop
         key = self.params_key(i, flat)
         header, q = self.source(i)
         p = self.params(i, key)
-        l.coef = self._coef(l, header, loss)
+        l.coef = self._round_coef(l, header, loss, self._vetoes(l, p, q) if vetoed is None else vetoed)
         r = sp.lerp(p, q, l.coef[0]) if l.coef[4] == 0 else p.copy()
         self._record(l, p, q, form or ("resident" if oop else "average_through" if through else "average"), r)
         self.changed = self.changed or (l.coef[4] == 0 and r.tobytes() != p.tobytes())
@@ -480,7 +621,9 @@ class Model:
                 place = 1 if self.mutant == "ahead-clock-one-place" else 2
                 l.clock[(l.cur + place) & 3] = l.coef[1] + 1.0
                 l.slots[k].header = (l.coef[1] + 1.0, math.nan, l.version + 1, sp.n, sp.code)
-            l.slots[k].payload = r.copy()
+            stale = self.mutant == "skip-leaves-snapshot-stale" and l.coef[4] == STATUS_SKIPPED
+            if not (stale and l.slots[k].payload is not None):
+                l.slots[k].payload = r.copy()
             if oop:
                 l.res_slot = k
         if not oop:
@@ -520,11 +663,20 @@ class Model:
         def form_of(e):
             return (bool(e[3]) or self.L[e[0]].resident, self.L[e[0]].resident)
         batchable = [e for e in entries if self.spec.dtype != "mixed" and (self.L[e[0]].resident or not self.spec.offset)]
+        # each checking member's pass reads that member's own snapshot, before anything of the dispatch
+        vetoed = {}
+        for i, flat, _, _ in entries:
+            vetoed[i] = self._vetoes(self.L[i], self.params(i, self.params_key(i, flat)), self.source(i)[1])
+        checking = [e[0] for e in entries if self.L[e[0]].check]
+        if self.mutant == "many-shares-one-veto" and any(vetoed[i] for i in checking):
+            vetoed.update({i: True for i in checking})
+        if self.mutant == "many-checks-first-member-only":
+            vetoed.update({i: False for i in checking[1:]})
         for e in entries:
             i, flat, loss, through = e
             shared = sum(1 for o in batchable if form_of(o) == form_of(e))
             form = "many-unbatched" if e not in batchable else "many-batched" if shared > 1 else "many-alone"
-            self._average_commit(i, flat, loss, bool(through), form)
+            self._average_commit(i, flat, loss, bool(through), form, vetoed[i])
         return OK
 
     def _cancel(self, i):
@@ -567,6 +719,26 @@ class Model:
             l.dist = (0.0, 0.0, 0.0, 0)
         return OK
 
+    def _set_finite_check(self, i, on):
+        l = self.L[i]
+        if on and l.fetch is not None and l.fetch.factored and self.mutant != "lerp-after-second-fetch-unchecked":
+            return self._refuse("set-check-over-factor")
+        l.check = bool(on)
+        return OK
+
+    def _set_param_distance(self, i, every):
+        """every == 0: count = 0, which switches the option off and leaves the record and the counters."""
+        l = self.L[i]
+        if every == 0:
+            l.pd_on = False
+            return OK
+        count = len(self.spec.param_ranges())
+        l.pd_on, l.pd_every = True, every
+        l.pd = (0.0, 0, ((0.0, 0.0),) * count)
+        if self.mutant != "param-reset-keeps-counters":
+            l.pd_rounds = (0, 0)
+        return OK
+
     def _set_header_publish(self, i, always):
         self.L[i].header_on_publish = bool(always)
         return OK
@@ -581,7 +753,9 @@ class Model:
             out.append((tuple(f.tobytes() for f in l.flats), slots, l.version, bits(l.clock[l.cur]),
                         tuple(bits(x) for x in l.coef[:4]) + (l.coef[4],),
                         l.res_slot if l.resident else -1,
-                        None if l.dist is None else tuple(bits(x) for x in l.dist[:3]) + (l.dist[3],)))
+                        None if l.dist is None else tuple(bits(x) for x in l.dist[:3]) + (l.dist[3],),
+                        l.check, l.skips, l.sticky, l.pd_rounds,
+                        None if l.pd is None else (bits(l.pd[0]), l.pd[1], tuple((bits(a), bits(b)) for a, b in l.pd[2]))))
         o = self.out
         if isinstance(o, np.ndarray):
             o = o.tobytes()
@@ -604,6 +778,45 @@ def header_same(got, want):
     """Header fields as moves_ref / relay_ref compare them: clock and loss as doubles (a NaN loss is
     "a NaN"), version, n and dtype as integers."""
     return header_key(got) == header_key(want)
+
+
+# ---------------------------------------------------------------------- poisoning a learner's parameters
+def _element(spec, where):
+    """(dtype, byte offset, numpy type) of the element POISON_AT names."""
+    seg, index = POISON_AT[spec.dtype][where]
+    if seg is None:
+        return spec.dtype, index * spec.elem, spec.numpy
+    off = next(off for d, off, _, _ in mixed_ref.segments(MIXED_SPEC)[0] if d == seg)
+    return seg, off + index * finite_ref.SIZE[seg], finite_ref.NUMPY[seg]
+
+
+def poisoned(m, i, flat, where, kind):
+    """Learner i's current parameter bits (of `flat`, or "res") with the element POISON_AT[dtype][where]
+    replaced by finite_ref.BAD's `kind`: what a ("step", i, flat, bits) writes to poison it."""
+    spec = m.spec
+    d, byte, np_t = _element(spec, where)
+    out = m.params(i, m.params_key(i, flat)).copy()
+    raw = out.view(np.uint8)
+    raw[byte:byte + finite_ref.SIZE[d]] = np.array([finite_ref.BAD[d][kind]], dtype=np_t).view(np.uint8)
+    return out
+
+
+def healed(m, i, flat):
+    """The same bits with every NaN and infinity replaced by what the learner began with there."""
+    cur = m.params(i, m.params_key(i, flat))
+    return np.where(m.spec.nonfinite(cur), m.spec.operands(i)[0], cur).astype(m.spec.numpy)
+
+
+def poison_tags(spec, q):
+    """((position, kind), ...): the named elements of payload q that hold one of finite_ref.BAD's patterns."""
+    if spec.n != SIZES[spec.dtype]:
+        return ()
+    out, raw = [], np.ascontiguousarray(q).view(np.uint8)
+    for where in POISON_AT[spec.dtype]:
+        d, byte, np_t = _element(spec, where)
+        got = int(raw[byte:byte + finite_ref.SIZE[d]].view(np_t)[0])
+        out += [(where, kind) for kind, pattern in finite_ref.BAD[d].items() if got == pattern]
+    return tuple(out)
 
 
 # ---------------------------------------------------------------------- running a list of calls
@@ -636,22 +849,62 @@ WALK_LENGTH = 150
 REFUSAL_SHARE = 0.35       # how often a draw the model refuses is kept (the walks stay well under a quarter)
 
 
-def profile_spec(dtype, profile, offset=0, n=None, seed=1, finite=False):
+def profile_spec(dtype, profile, offset=0, n=None, seed=1, finite=False, draws=()):
     method, value = PROFILE_METHOD[profile]
     resident = {"resident": (0, 1, 2), "mix": (1,)}.get(profile, ())
-    return Spec(dtype, method, value, 0.0, n=n, offset=offset, resident=resident, seed=seed, finite=finite)
+    return Spec(dtype, method, value, 0.0, n=n, offset=offset, resident=resident, seed=seed, finite=finite, draws=draws)
 
 
 def setup_ops(spec):
     """What a walk begins with: the resident learners made so; on finite operands every learner tracks the
     distance from the start (the walk still switches it off and on)."""
     return [("set_resident", i) for i in spec.resident] + \
-           [("set_distance", i, 1) for i in range(spec.learners) if spec.finite]
+           [("set_distance", i, 1) for i in range(spec.learners) if spec.finite] + \
+           [("set_finite_check", i, 1) for i in range(spec.learners) if "check" in spec.draws] + \
+           [("set_param_distance", i, 2) for i in range(spec.learners) if "param" in spec.draws]
+
+
+NEW_SHARE = 0.22           # of the draws of a walk whose spec asks for the newer calls (Spec.draws)
+EVERY = (0, 1, 2, 3)
+POISON_WEIGHT, HEAL_WEIGHT = 3.0, 5.0
+CHECK_WALK_LENGTH = 165
+
+
+def _draw_new(rng, m):
+    """One of the calls Spec.draws asks for.  Most of the time every learner checks; a learner's parameters
+    are poisoned now and then (one element of POISON_AT, one of POISON_KINDS) and healed soon after, so that
+    most rounds still average.  A resident learner's parameters are stepped only while they lie in the slot of
+    its next publish, which no peer reads."""
+    sp = m.spec
+    i = rng.randrange(sp.learners)
+    l = m.L[i]
+    flat = "res" if l.resident else 0
+    w = {}
+    if "check" in sp.draws:
+        w["set_finite_check"] = 0.3 if l.check else 4.0
+        if sp.finite and (not l.resident or (l.res_slot == m._next_slot(l) and not m._still_read(i, l.res_slot))):
+            dirty = sp.vetoes(m.params(i, m.params_key(i, flat)))
+            # (a resident learner is seldom where it may be stepped: it is poisoned more readily there)
+            w["heal" if dirty else "poison"] = HEAL_WEIGHT if dirty else POISON_WEIGHT * (6 if l.resident else 1)
+    if "param" in sp.draws:
+        w["set_param_distance"] = 0.8
+    names = sorted(w)
+    name = rng.choices(names, [w[k] for k in names])[0]
+    if name == "set_finite_check":
+        return ("set_finite_check", i, int(not l.check))
+    if name == "set_param_distance":
+        return ("set_param_distance", i, rng.choice(EVERY))
+    if name == "heal":
+        return ("step", i, flat, healed(m, i, flat))
+    return ("step", i, flat, poisoned(m, i, flat, rng.choice(sorted(POISON_AT[sp.dtype])), rng.choice(POISON_KINDS)))
 
 
 def _draw(rng, m, profile):
-    """One candidate call, drawn from the state: mostly what the loop would do next, sometimes not."""
+    """One candidate call, drawn from the state: mostly what the loop would do next, sometimes not.  (A spec
+    that asks for none of the newer calls draws exactly what it always drew.)"""
     sp = m.spec
+    if sp.draws and rng.random() < NEW_SHARE:
+        return _draw_new(rng, m)
     i = rng.randrange(sp.learners)
     l = m.L[i]
     peers = [j for j in range(sp.learners) if j != i]
@@ -714,10 +967,10 @@ def _draw(rng, m, profile):
     return table[rng.choices(names, [w[k] for k in names])[0]]()
 
 
-def walk(seed, dtype, profile, length=WALK_LENGTH, offset=0, finite=False):
+def walk(seed, dtype, profile, length=WALK_LENGTH, offset=0, finite=False, draws=()):
     """(spec, ops): `length` calls drawn with random.Random from the model's current state.  The model
     is asked beforehand whether a drawn call is legal; a refused one is kept REFUSAL_SHARE of the time."""
-    spec = profile_spec(dtype, profile, offset, finite=finite)
+    spec = profile_spec(dtype, profile, offset, finite=finite, draws=draws)
     rng = random.Random("%s/%s/%d/%d" % (profile, dtype, offset, seed))
     m = Model(spec)
     ops = setup_ops(spec)
@@ -743,13 +996,30 @@ WALKS = tuple((p, d, o, 1, False) for p in PROFILES for d in DTYPES for o in ((0
     ("mix", "mixed", 0, 2, True), ("mix", "f32", 1, 2, True))
 
 
+# (..., what the walk draws besides): the walks with the non-finite check on.  Finite operands, poisoned and
+# healed as the walk goes, one walk per profile and one unaligned (where the per-parameter option, which
+# refuses unaligned parameters, stays off); one walk draws both options and set_distance together.  (The seeds
+# are the first with which the model meets tests/test_walk_host.py's conditions with some room.)  The last
+# one runs on the hard bit patterns, where nearly every snapshot holds a NaN or an infinity and nearly every
+# checked round is skipped: the long run of consecutive vetoes that a veto outliving its round would hide in.
+CHECK_WALKS = (
+    ("plain", "f32", 0, 4, True, ("check",)), ("through", "bf16", 0, 9, True, ("check",)),
+    ("resident", "f16", 0, 11, True, ("check",)), ("mix", "mixed", 0, 32, True, ("check",)),
+    ("mix", "f32", 1, 3, True, ("check",)), ("through", "f32", 0, 9, True, ("check", "param")),
+    ("mix", "bf16", 0, 3, False, ("check",)))
+ALL_HARD = CHECK_WALKS[-1]
+
+
 def walk_id(w):
-    return "%s-%s-%s-seed%d%s" % (w[0], w[1], "aligned" if w[2] == 0 else "off%d" % w[2], w[3], "-finite" if w[4] else "")
+    return "%s-%s-%s-seed%d%s%s" % (w[0], w[1], "aligned" if w[2] == 0 else "off%d" % w[2], w[3], "-finite" if w[4] else "",
+                                    "".join("-" + d for d in w[5]) if len(w) > 5 else "")
 
 
 def walk_of(w):
-    """(spec, ops) of an entry of WALKS."""
-    return walk(w[3], w[1], w[0], offset=w[2], finite=w[4])
+    """(spec, ops) of an entry of WALKS or CHECK_WALKS."""
+    if len(w) == 5:
+        return walk(w[3], w[1], w[0], offset=w[2], finite=w[4])
+    return walk(w[3], w[1], w[0], length=CHECK_WALK_LENGTH, offset=w[2], finite=w[4], draws=w[5])
 
 
 # ---------------------------------------------------------------------- directed sequences
@@ -897,11 +1167,158 @@ def directed():
         ("average_many", ((0, 0, 0.5, 0), (1, 0, 0.5, 1))), ("average_many", ((1, 0, 0.5, 0), (0, 0, 0.5, 1))),
         ("fetch", 1, 0, 1, "zc"), ("average_through", 1, 0, 0.5), (R, 1, 0, 0.5), (R, 0, 0, 0.5)])
     seqs["every-pair"] = _pair_ops()
+    seqs.update(_checked_sequences())
+    return seqs
+
+
+class _Script:
+    """A sequence written against the model's state, for the steps that poison or heal what a learner holds."""
+
+    def __init__(self, spec):
+        self.spec, self.m, self.ops = spec, Model(spec), []
+
+    def do(self, *ops):
+        for op in ops:
+            self.m.apply(op)
+            self.ops.append(op)
+
+    def poison(self, i, flat, where, kind):
+        self.do(("step", i, flat, poisoned(self.m, i, flat, where, kind)))
+
+    def heal(self, i, flat):
+        self.do(("step", i, flat, healed(self.m, i, flat)))
+
+    def serve(self, j, where, kind):
+        """Learner j publishes what it holds (version 1, finite), then the same with one element poisoned
+        (version 2): both stay fetchable while it publishes nothing more."""
+        self.do(("publish", j, 0, 0.5))
+        self.poison(j, 0, where, kind)
+        self.do(("publish", j, 0, 0.5))
+
+    def done(self):
+        return self.spec, self.ops
+
+
+def _skip_every_form(dtype, where, kind):
+    """A skipped round and then a finite one in every averaging form, both distance records on: learner 2
+    serves (version 1 finite, version 2 poisoned), learner 0 averages from its flat buffer, learner 1 is
+    resident.  The dispatch of two is batched for one element type and two launches for a segmented payload."""
+    s = _Script(profile_spec(dtype, "mix", finite=True))
+    s.do(("set_resident", 1))
+    for i in (0, 1):
+        s.do(("set_finite_check", i, 1), ("set_distance", i, 1), ("set_param_distance", i, 1))
+    s.serve(2, where, kind)
+    s.do(("publish", 0, 0, 1.0), ("publish", 1, "res", 1.0))
+    for v, kind_ in ((2, "ce"), (1, "ce")):
+        s.do(("fetch", 0, 2, v, kind_), ("average", 0, 0, 0.5))
+    for v in (2, 1):
+        s.do(("fetch", 0, 2, v, "zc"), ("average_through", 0, 0, 0.5), ("publish_reuse", 0, 0, 0.75))
+    for v, kind_ in ((2, "zc"), (1, "k1")):
+        s.do(("fetch", 1, 2, v, kind_), ("average", 1, "res", 0.5), ("publish", 1, "res", 0.75))
+    for v, kind_ in ((2, "k512"), (1, "zc")):
+        s.do(("fetch", 0, 2, v, kind_), ("factor", 0, 0.5), ("lerp", 0, 0))
+    for v in (2, 1):     # learner 2 does not check; its own parameters are the poisoned ones and stay so
+        s.do(("fetch", 0, 2, v, "zc"), ("fetch", 2, 0, s.m.L[0].version, "ce"),
+             ("average_many", ((2, 0, 0.5, 0), (0, 0, 0.5, 0))))
+    s.do(("read_snapshot", 0), ("read_snapshot", 1))
+    return s.done()
+
+
+_CHECKED = []
+
+
+def _checked_sequences():
+    """The sequences for the non-finite check and the per-parameter distance (built once: they poison what
+    the model holds at that point)."""
+    if _CHECKED:
+        return _CHECKED[0]
+    T, P, R = profile_spec, "publish", "publish_reuse"
+    seqs = {}
+    # the veto's stamp: skipped, finite, skipped, finite in a row on learner 0, the check switched off and on
+    # in between; then an average that is prepared (its stamp taken) and refused for a reader of its slot,
+    # between two checked rounds
+    s = _Script(T("f32", "through", finite=True))
+    s.do(("set_finite_check", 0, 1), ("set_distance", 0, 1), (P, 0, 0, 1.0))
+    s.serve(1, "first", "snan")
+    s.do(("fetch", 0, 1, 2, "ce"), ("average", 0, 0, 0.5), ("fetch", 0, 1, 1, "zc"), ("average", 0, 0, 0.5),
+         ("fetch", 0, 1, 2, "zc"), ("average_through", 0, 0, 0.5), ("set_finite_check", 0, 0), ("set_finite_check", 0, 1),
+         ("fetch", 0, 1, 1, "ce"), ("average_through", 0, 0, 0.5), (R, 0, 0, 0.75),
+         ("fetch", 2, 0, 1, "zc"), ("fetch", 0, 1, 2, "zc"), ("average_through", 0, 0, 0.5), ("cancel", 2),
+         ("average_through", 0, 0, 0.5), ("fetch", 0, 1, 1, "k1"), ("average_through", 0, 0, 0.5), (R, 0, 0, 0.5),
+         ("read_snapshot", 0))
+    seqs["veto-stamp"] = s.done()
+    # a second fetch over a checked factor, copied and in place, and switching the check on over an unchecked
+    # one: both refused; with the check off the second fetch keeps the factor as it always has
+    s = _Script(T("bf16", "plain", finite=True))
+    s.do(("set_finite_check", 0, 1), (P, 0, 0, 1.0))
+    s.serve(1, "tail-last", "+inf")
+    s.do(("fetch", 0, 1, 1, "ce"), ("factor", 0, 0.5), ("fetch", 0, 1, 2, "ce"), ("lerp", 0, 0),
+         ("fetch", 0, 1, 1, "zc"), ("factor", 0, 0.5), ("fetch", 0, 1, 2, "zc"), ("lerp", 0, 0),
+         ("set_finite_check", 0, 0), ("fetch", 0, 1, 1, "k1"), ("factor", 0, 0.5), ("set_finite_check", 0, 1),
+         ("fetch", 0, 1, 2, "zc"), ("lerp", 0, 0))
+    s.heal(0, 0)
+    s.do(("set_finite_check", 0, 1), ("fetch", 0, 1, 2, "zc"), ("factor", 0, 0.5), ("set_finite_check", 0, 1),
+         ("lerp", 0, 0), ("fetch", 0, 1, 1, "zc"), ("factor", 0, 0.5), ("lerp", 0, 0))
+    s.poison(1, 0, "gap", "snan")     # (a second poison, in no parameter tensor: the next version is skipped as well)
+    s.do((P, 1, 0, 0.5), ("fetch", 0, 1, 3, "ce"), ("average", 0, 0, 0.5))
+    seqs["second-fetch-checked"] = s.done()
+    seqs["skip-every-form"] = _skip_every_form("f16", "span-last", "qnan")
+    seqs["skip-every-form-segmented"] = _skip_every_form("mixed", "bf16-last", "-inf")
+    # one dispatch of four: learners 0, 1, 2 check and learner 1's snapshot is poisoned; learner 3 does not
+    # check, its snapshot is poisoned too, and it goes non-finite (the documented behaviour)
+    s = _Script(Spec("f16", "constant", 0.3, learners=5, finite=True))
+    for i in (0, 1, 2):
+        s.do(("set_finite_check", i, 1))
+    for i in (0, 1, 2, 3):
+        s.do((P, i, 0, 1.0))
+    s.do(("set_distance", 3, 1), ("set_param_distance", 3, 1))    # the poison lies in no tensor: only the whole-model sums show it
+    s.poison(4, 0, "gap", "-inf")
+    s.do((P, 4, 0, 0.5), ("fetch", 0, 3, 1, "zc"), ("fetch", 1, 4, 1, "ce"), ("fetch", 2, 0, 1, "ce"), ("fetch", 3, 4, 1, "zc"),
+         ("average_many", ((0, 0, 0.5, 0), (1, 0, 0.5, 0), (2, 0, 0.5, 0), (3, 0, 0.5, 0))),
+         ("fetch", 1, 2, 1, "zc"), ("fetch", 2, 4, 1, "zc"), ("average_many", ((2, 0, 0.5, 1), (1, 0, 0.5, 1))))
+    seqs["many-one-poisoned"] = s.done()
+    # a round that is both a ZeroDivision (both clocks 0) and poisoned stays a ZeroDivision and is not counted
+    s = _Script(Spec("f32", "clock", finite=True))
+    s.do(("set_finite_check", 0, 1), ("write_clock", 1, -1.0))
+    s.poison(1, 0, "span-last", "qnan")
+    s.do((P, 1, 0, 0.5), ("fetch", 0, 1, 1, "zc"), ("average", 0, 0, 0.5), ("fetch", 0, 1, 1, "ce"), ("factor", 0, 0.5),
+         ("lerp", 0, 0), ("write_clock", 0, 3.5), ("fetch", 0, 1, 1, "zc"), ("average_through", 0, 0, 0.5))
+    seqs["zero-division-and-poison"] = s.done()
+    # every = 3 over ten rounds, the sixth a skipped one; off, a round, on again (the record and the counters
+    # start anew), off
+    s = _Script(T("f32", "through", finite=True))
+    s.do(("set_finite_check", 0, 1), (P, 0, 0, 1.0))
+    s.serve(1, "tail-last", "snan")
+    s.do(("set_param_distance", 0, 3))
+    for r in range(1, 11):
+        s.do(("fetch", 0, 1, 2 if r == 6 else 1, FETCH_KINDS[r % 4]))
+        s.do(*((("factor", 0, 0.5), ("lerp", 0, 0)) if r % 4 == 1 else (("average_through" if r % 2 else "average", 0, 0, 0.5),)))
+    s.do(("set_param_distance", 0, 0), ("fetch", 0, 1, 1, "zc"), ("average", 0, 0, 0.5), ("set_param_distance", 0, 2),
+         ("fetch", 0, 1, 1, "zc"), ("average", 0, 0, 0.5), ("fetch", 0, 1, 1, "ce"), ("average", 0, 0, 0.5),
+         ("set_param_distance", 0, 0), ("fetch", 0, 1, 1, "ce"), ("average", 0, 0, 0.5))
+    seqs["param-every"] = s.done()
+    # unaligned parameters while the per-parameter option is on: every averaging call refused, nothing counted;
+    # the resident learner's slot is aligned
+    seqs["param-unaligned-refused"] = (T("f32", "mix", offset=1, finite=True), [
+        ("set_resident", 1), ("set_param_distance", 0, 1), ("set_param_distance", 1, 1), (P, 2, 0, 0.5), (P, 1, "res", 1.0),
+        ("fetch", 0, 2, 1, "ce"), ("average", 0, 0, 0.5), ("average_through", 0, 1, 0.5), ("factor", 0, 0.5), ("lerp", 0, 0),
+        ("cancel", 0), ("fetch", 0, 2, 1, "zc"), ("fetch", 1, 2, 1, "zc"), ("average_many", ((1, "res", 0.5, 0), (0, 0, 0.5, 0))),
+        ("average", 1, 0, 0.5), ("average", 1, "res", 0.5), ("set_param_distance", 0, 0), ("average", 0, 0, 0.5),
+        ("fetch", 0, 2, 1, "zc"), ("factor", 0, 0.5), ("lerp", 0, 0)])
+    # a learner whose own parameters are poisoned is not skipped; the peer that fetches it is
+    s = _Script(T("f16", "plain", finite=True))
+    s.do(("set_finite_check", 0, 1), ("set_finite_check", 2, 1), (P, 1, 0, 0.5))
+    s.poison(0, 0, "tail-last", "+inf")
+    s.do(("fetch", 0, 1, 1, "ce"), ("average", 0, 0, 0.5), (P, 0, 0, 1.0), ("fetch", 2, 0, 1, "zc"), ("average", 2, 0, 0.5),
+         ("fetch", 2, 1, 1, "zc"), ("average", 2, 0, 0.5))
+    seqs["own-params-poisoned"] = s.done()
+    _CHECKED.append(seqs)
     return seqs
 
 
 def replay_text(spec, ops):
     """An expression that replays the calls against the model on the host (with tests.walk_ref imported)."""
-    return "walk_ref.run(walk_ref.Spec(%r, %r, %r, %r, n=%d, offset=%d, resident=%r, seed=%d, finite=%r), %r)" % (
-        spec.dtype, spec.method, spec.value, spec.threshold, spec.n, spec.offset, spec.resident, spec.seed, spec.finite,
-        list(ops))
+    plain = [op[:3] + (np.asarray(op[3]).tolist(),) if op[0] == "step" else op for op in ops]     # a step's bits as a list
+    return ("walk_ref.run(walk_ref.Spec(%r, %r, %r, %r, n=%d, offset=%d, resident=%r, seed=%d, finite=%r, learners=%d, "
+            "draws=%r), %r)" % (spec.dtype, spec.method, spec.value, spec.threshold, spec.n, spec.offset, spec.resident,
+                                spec.seed, spec.finite, spec.learners, spec.draws, plain))
