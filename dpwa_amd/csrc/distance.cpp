@@ -129,7 +129,7 @@ int dpwa_measure_distance(int32_t dtype, const void *param, const void *peer_pay
     const size_t es = dtype_size(dtype);
     if (((uintptr_t)param | (uintptr_t)peer_payload) & (es - 1))
         return set_error(DPWA_ERR_ARG, "dpwa_measure_distance: an operand is not aligned to its element size");
-    HIP_TRY(launch_distance(dtype, param, peer_payload, n, (double *)workspace, (hipStream_t)stream));
+    HIP_TRY(launch_distance(Elems{dtype, n, nullptr}, param, peer_payload, (double *)workspace, (hipStream_t)stream));
     HIP_TRY(launch_distance_finish((double *)workspace, out_dev, nullptr, n, (hipStream_t)stream));
     return DPWA_OK;
 }
@@ -142,9 +142,9 @@ int dpwa_measure_distance_mixed(const dpwa_layout *layout, const void *param, co
     if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: %s", why);
     if (!aligned16(param, peer_payload))
         return set_error(DPWA_ERR_ARG, "dpwa_measure_distance_mixed: a segmented payload is 16-byte aligned");
-    const int64_t n = layout_elements(*layout);
-    HIP_TRY(launch_distance_mixed(*layout, param, peer_payload, (double *)workspace, (hipStream_t)stream));
-    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, nullptr, n, (hipStream_t)stream));
+    const Elems e{DPWA_MIXED, layout_bytes(*layout), layout};
+    HIP_TRY(launch_distance(e, param, peer_payload, (double *)workspace, (hipStream_t)stream));
+    HIP_TRY(launch_distance_finish((double *)workspace, out_dev, nullptr, e.elements(), (hipStream_t)stream));
     return DPWA_OK;
 }
 
@@ -161,7 +161,7 @@ int dpwa_check_finite(int32_t dtype, const void *peer_payload, int64_t n, uint32
     if ((uintptr_t)peer_payload & (dtype_size(dtype) - 1))
         return set_error(DPWA_ERR_ARG, "dpwa_check_finite: the payload is not aligned to its element size");
     const CallerTiming timing(start_event, stop_event);
-    HIP_TRY(launch_peer_finite(dtype, peer_payload, n, veto_dev, stamp, (hipStream_t)stream, timing));
+    HIP_TRY(launch_peer_finite(Elems{dtype, n, nullptr}, peer_payload, veto_dev, stamp, (hipStream_t)stream, timing));
     return DPWA_OK;
 }
 
@@ -174,7 +174,8 @@ int dpwa_check_finite_mixed(const dpwa_layout *layout, const void *peer_payload,
     if (!aligned16(peer_payload))
         return set_error(DPWA_ERR_ARG, "dpwa_check_finite_mixed: a segmented payload is 16-byte aligned");
     const CallerTiming timing(start_event, stop_event);
-    HIP_TRY(launch_peer_finite_mixed(*layout, peer_payload, veto_dev, stamp, (hipStream_t)stream, timing));
+    HIP_TRY(launch_peer_finite(Elems{DPWA_MIXED, layout_bytes(*layout), layout}, peer_payload, veto_dev, stamp,
+                               (hipStream_t)stream, timing));
     return DPWA_OK;
 }
 
@@ -198,8 +199,8 @@ int dpwa_average_tracked(int32_t dtype, void *param, const void *peer_slot, int6
     if (aligned16(param, peer, snap_payload)) {
         HIP_TRY(launch_average_tracked(dtype, param, peer, n, fa, snap_payload, false, (double *)workspace, s, timing));
     } else {   // the stand-alone pass, then dpwa_average's own (unaligned) kernel
-        HIP_TRY(launch_distance(dtype, param, peer, n, (double *)workspace, s));
-        HIP_TRY(launch_average(dtype, param, peer, n, fa, snap_payload, s, timing));
+        HIP_TRY(launch_distance(Elems{dtype, n, nullptr}, param, peer, (double *)workspace, s));
+        HIP_TRY(launch_average(Elems{dtype, n, nullptr}, param, peer, fa, snap_payload, s, timing));
     }
     HIP_TRY(launch_distance_finish((double *)workspace, out_dev, coef_dev, n, s));
     return DPWA_OK;

@@ -1385,6 +1385,8 @@ static_assert(launches_as_itself<Lerp64Policies, kFitPolicy, kProductPolicy>() &
 // Workgroups of one 16-byte item per lane over n elements; the last span may be empty
 // (range-checked).
 template <class Ops> static int64_t span_grid(int64_t n, int block) { return (n / Ops::PER) / block + 1; }
+// Workgroups of the grid-stride kernels for operands that are not 16-B aligned.
+static dim3 unaligned_grid(int64_t n) { return dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)); }
 
 template <class Ops, int MODE, bool DUAL>
 static hipError_t launch_mode(void *param, const void *peer, int64_t n, const LerpArgs &args, hipStream_t s,
@@ -1392,8 +1394,7 @@ static hipError_t launch_mode(void *param, const void *peer, int64_t n, const Le
 {
     if (!aligned16(param) || !aligned16(peer) || !aligned16(args.snap)) {
         // (callers time only the aligned product kernel; an unaligned launch is not timed)
-        return launch(k_lerp_unaligned<Ops, MODE, DUAL>, dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)),
-                      dim3(kBlock), s, nullptr, param, peer, n, args);
+        return launch(k_lerp_unaligned<Ops, MODE, DUAL>, unaligned_grid(n), dim3(kBlock), s, nullptr, param, peer, n, args);
     }
     return Choice<256, 64, 128, 512>::with(lerp_block(), [&](auto block) {
         constexpr int BLOCK = decltype(block)::value;
@@ -1405,12 +1406,18 @@ static hipError_t launch_mode(void *param, const void *peer, int64_t n, const Le
     });
 }
 
-static hipError_t launch_any(int32_t dtype, int mode, void *param, const void *peer, int64_t n, const LerpArgs &args,
-                             hipStream_t s, const LaunchTiming *t = nullptr)
+// (a segmented payload's k_lerp_mixed launches, behind with_segments below)
+static hipError_t launch_any_mixed(const Elems &e, int mode, bool oop, void *param, const void *peer, const LerpArgs &args,
+                                   hipStream_t s, const LaunchTiming *t);
+
+static hipError_t launch_any(const Elems &e, int mode, void *param, const void *peer, const LerpArgs &args, hipStream_t s,
+                             const LaunchTiming *t = nullptr)
 {
+    if (e.segmented()) return launch_any_mixed(e, mode, false, param, peer, args, s, t);
+    const int64_t n = e.n;
     if (n < 0) return hipErrorInvalidValue;
     if (n == 0 && mode != COEF_FUSED) return hipSuccess;
-    return with_ops(dtype, [&](auto ops) {
+    return with_ops(e.dtype, [&](auto ops) {
         using Ops = decltype(ops);
         if (mode == COEF_HOST) return launch_mode<Ops, COEF_HOST, false>(param, peer, n, args, s, t);
         if (mode == COEF_DEV) return launch_mode<Ops, COEF_DEV, false>(param, peer, n, args, s, t);
@@ -1419,26 +1426,28 @@ static hipError_t launch_any(int32_t dtype, int mode, void *param, const void *p
     });
 }
 
-hipError_t launch_lerp(int32_t dtype, void *param, const void *peer, int64_t n, const dpwa_coef *coef, float a,
-                       float b, hipStream_t s)
+hipError_t launch_lerp(const Elems &e, void *param, const void *peer, const dpwa_coef *coef, float a, float b,
+                       hipStream_t s)
 {
     LerpArgs args{};
     args.a = a;
     args.b = b;
     args.coef = coef;
-    return launch_any(dtype, coef ? COEF_DEV : COEF_HOST, param, peer, n, args, s);
+    return launch_any(e, coef ? COEF_DEV : COEF_HOST, param, peer, args, s);
 }
 
-hipError_t launch_average(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa, void *snap,
-                          hipStream_t s, const LaunchTiming *timing, bool oop)
+hipError_t launch_average(const Elems &e, void *param, const void *peer, const FusedArgs &fa, void *snap, hipStream_t s,
+                          const LaunchTiming *timing, bool oop)
 {
     LerpArgs args{};
     args.fused = fa;
     args.snap = snap;
-    if (!oop) return launch_any(dtype, COEF_FUSED, param, peer, n, args, s, timing);
+    if (!oop) return launch_any(e, COEF_FUSED, param, peer, args, s, timing);
+    if (e.segmented()) return launch_any_mixed(e, COEF_FUSED, true, param, peer, args, s, timing);
     // resident: 16-B aligned slot payloads only, one-wave workgroups
+    const int64_t n = e.n;
     if (n < 0 || (!snap && n > 0) || !aligned16(param) || !aligned16(peer) || !aligned16(snap)) return hipErrorInvalidValue;
-    return with_ops(dtype, [&](auto ops) {
+    return with_ops(e.dtype, [&](auto ops) {
         using Ops = decltype(ops);
         return ResidentPolicies::with(lerp_policy(), [&](auto policy) {
             return launch(k_lerp<Ops, COEF_FUSED, true, kStreamBlock, decltype(policy)::value, true>,
@@ -1470,13 +1479,12 @@ const char *layout_problem(const dpwa_layout &layout, int64_t total_bytes)
     return nullptr;
 }
 
-template <int MODE, bool DUAL, bool OOP>
-static hipError_t launch_mixed(const dpwa_layout &layout, void *param, const void *peer, const LerpArgs &args,
-                               hipStream_t s, const LaunchTiming *timing)
+// The launch of a segmented payload, one 1-KiB span per workgroup: run(total bytes, grid, the segments' table).
+// Refused: `operands_bad` (the caller's null or misaligned pointers), no layout, an invalid one, too many spans.
+template <class Run> static hipError_t with_segments(const Elems &e, bool operands_bad, Run &&run)
 {
-    if (layout_problem(layout, -1) || !param || !peer || !aligned16(param) || !aligned16(peer) || !aligned16(args.snap) ||
-        (DUAL && !args.snap))
-        return hipErrorInvalidValue;
+    if (operands_bad || !e.layout || layout_problem(*e.layout, -1)) return hipErrorInvalidValue;
+    const dpwa_layout &layout = *e.layout;
     SegTable t;
     for (int i = 0; i < DPWA_LAYOUT_MAX_SEGMENTS; ++i) {
         t.begin[i] = i < layout.count ? layout.seg[i].byte_offset : INT64_MAX;
@@ -1485,32 +1493,33 @@ static hipError_t launch_mixed(const dpwa_layout &layout, void *param, const voi
     const int64_t total = layout_bytes(layout);
     const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
     if (g > 0x7fffffffLL) return hipErrorInvalidValue;
-    // (resident: the product policy, as the single-dtype resident kernels without the knob)
-    return BySizePolicies::with(OOP ? kProductPolicy : lerp_policy(total), [&](auto policy) {
-        constexpr int P = OOP ? kProductPolicy : decltype(policy)::value;
-        return launch(k_lerp_mixed<MODE, DUAL, P, OOP>, dim3((uint32_t)g), dim3(kStreamBlock), s, timing, param, peer,
-                      total, args, t);
+    return run(total, dim3((uint32_t)g), t);
+}
+// (a segmented payload's operand: there, and 16-B aligned)
+static bool absent_or_unaligned(const void *p) { return !p || !aligned16(p); }
+
+template <int MODE, bool DUAL, bool OOP>
+static hipError_t launch_mixed(const Elems &e, void *param, const void *peer, const LerpArgs &args, hipStream_t s,
+                               const LaunchTiming *timing)
+{
+    const bool bad = absent_or_unaligned(param) || absent_or_unaligned(peer) || !aligned16(args.snap) || (DUAL && !args.snap);
+    return with_segments(e, bad, [&](int64_t total, dim3 grid, const SegTable &t) {
+        // (resident: the product policy, as the single-dtype resident kernels without the knob)
+        return BySizePolicies::with(OOP ? kProductPolicy : lerp_policy(total), [&](auto policy) {
+            constexpr int P = OOP ? kProductPolicy : decltype(policy)::value;
+            return launch(k_lerp_mixed<MODE, DUAL, P, OOP>, grid, dim3(kStreamBlock), s, timing, param, peer, total, args, t);
+        });
     });
 }
 
-hipError_t launch_lerp_mixed(const dpwa_layout &layout, void *param, const void *peer, const dpwa_coef *coef,
-                             hipStream_t s)
+static hipError_t launch_any_mixed(const Elems &e, int mode, bool oop, void *param, const void *peer, const LerpArgs &args,
+                                   hipStream_t s, const LaunchTiming *t)
 {
-    if (!coef) return hipErrorInvalidValue;
-    LerpArgs args{};
-    args.coef = coef;
-    return launch_mixed<COEF_DEV, false, false>(layout, param, peer, args, s, nullptr);
-}
-
-hipError_t launch_average_mixed(const dpwa_layout &layout, void *param, const void *peer, const FusedArgs &fa,
-                                void *snap, hipStream_t s, const LaunchTiming *timing, bool oop)
-{
-    LerpArgs args{};
-    args.fused = fa;
-    args.snap = snap;
-    if (oop) return launch_mixed<COEF_FUSED, true, true>(layout, param, peer, args, s, timing);
-    if (snap) return launch_mixed<COEF_FUSED, true, false>(layout, param, peer, args, s, timing);
-    return launch_mixed<COEF_FUSED, false, false>(layout, param, peer, args, s, timing);
+    if (mode == COEF_HOST) return hipErrorInvalidValue;   // (a segmented lerp reads its coefficients on the device)
+    if (mode == COEF_DEV) return launch_mixed<COEF_DEV, false, false>(e, param, peer, args, s, t);
+    if (oop) return launch_mixed<COEF_FUSED, true, true>(e, param, peer, args, s, t);
+    if (args.snap) return launch_mixed<COEF_FUSED, true, false>(e, param, peer, args, s, t);
+    return launch_mixed<COEF_FUSED, false, false>(e, param, peer, args, s, t);
 }
 
 // ---------------------------------------------------------------- distance launches
@@ -1538,35 +1547,24 @@ hipError_t launch_average_tracked(int32_t dtype, void *param, const void *peer, 
     });
 }
 
-hipError_t launch_distance(int32_t dtype, const void *param, const void *peer, int64_t n, double *acc, hipStream_t s)
+hipError_t launch_distance(const Elems &e, const void *param, const void *peer, double *acc, hipStream_t s)
 {
-    if (n < 0 || !acc) return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
-    return with_ops(dtype, [&](auto ops) {
-        using Ops = decltype(ops);
-        if (!aligned16(param) || !aligned16(peer))
-            return launch(k_distance_unaligned<Ops>, dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)), dim3(kBlock),
-                          s, nullptr, param, peer, n, acc);
-        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
-        return launch(k_distance<Ops>, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, nullptr,
-                      param, peer, n, acc);
-    });
-}
-
-hipError_t launch_distance_mixed(const dpwa_layout &layout, const void *param, const void *peer, double *acc,
-                                 hipStream_t s)
-{
-    if (layout_problem(layout, -1) || !param || !peer || !acc || !aligned16(param) || !aligned16(peer))
-        return hipErrorInvalidValue;
-    SegTable t;
-    for (int i = 0; i < DPWA_LAYOUT_MAX_SEGMENTS; ++i) {
-        t.begin[i] = i < layout.count ? layout.seg[i].byte_offset : INT64_MAX;
-        t.dtype[i] = i < layout.count ? layout.seg[i].dtype : layout.seg[0].dtype;
+    if (!acc) return hipErrorInvalidValue;
+    if (const int64_t n = e.n; !e.segmented()) {
+        if (n <= 0) return n < 0 ? hipErrorInvalidValue : hipSuccess;
+        return with_ops(e.dtype, [&](auto ops) {
+            using Ops = decltype(ops);
+            if (!aligned16(param) || !aligned16(peer))
+                return launch(k_distance_unaligned<Ops>, unaligned_grid(n), dim3(kBlock), s, nullptr, param, peer, n, acc);
+            if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+            return launch(k_distance<Ops>, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, nullptr,
+                          param, peer, n, acc);
+        });
     }
-    const int64_t total = layout_bytes(layout);
-    const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
-    if (g > 0x7fffffffLL) return hipErrorInvalidValue;
-    return launch(k_distance_mixed, dim3((uint32_t)g), dim3(kStreamBlock), s, nullptr, param, peer, total, t, acc);
+    const bool bad = absent_or_unaligned(param) || absent_or_unaligned(peer);
+    return with_segments(e, bad, [&](int64_t total, dim3 grid, const SegTable &t) {
+        return launch(k_distance_mixed, grid, dim3(kStreamBlock), s, nullptr, param, peer, total, t, acc);
+    });
 }
 
 hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
@@ -1614,40 +1612,28 @@ static int finite_aux()
 }
 using FiniteLoads = Choice<0, kAuxStream>;
 
-hipError_t launch_peer_finite(int32_t dtype, const void *peer, int64_t n, uint32_t *veto, uint32_t stamp, hipStream_t s,
+hipError_t launch_peer_finite(const Elems &e, const void *peer, uint32_t *veto, uint32_t stamp, hipStream_t s,
                               const LaunchTiming *timing)
 {
-    if (n < 0 || !veto || stamp == 0 || ((uintptr_t)veto & 3)) return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
-    return with_ops(dtype, [&](auto ops) {
-        using Ops = decltype(ops);
-        if (!aligned16(peer))
-            return launch(k_peer_finite_unaligned<Ops>, dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)), dim3(kBlock),
-                          s, timing, peer, n, veto, stamp);
-        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
-        return FiniteLoads::with(finite_aux(), [&](auto aux) {
-            return launch(k_peer_finite<Ops, decltype(aux)::value>, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)),
-                          dim3(kStreamBlock), s, timing, peer, n, veto, stamp);
+    if (!veto || stamp == 0 || ((uintptr_t)veto & 3)) return hipErrorInvalidValue;
+    if (const int64_t n = e.n; !e.segmented()) {
+        if (n <= 0) return n < 0 ? hipErrorInvalidValue : hipSuccess;
+        return with_ops(e.dtype, [&](auto ops) {
+            using Ops = decltype(ops);
+            if (!aligned16(peer))
+                return launch(k_peer_finite_unaligned<Ops>, unaligned_grid(n), dim3(kBlock), s, timing, peer, n, veto, stamp);
+            if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+            return FiniteLoads::with(finite_aux(), [&](auto aux) {
+                return launch(k_peer_finite<Ops, decltype(aux)::value>, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)),
+                              dim3(kStreamBlock), s, timing, peer, n, veto, stamp);
+            });
         });
-    });
-}
-
-hipError_t launch_peer_finite_mixed(const dpwa_layout &layout, const void *peer, uint32_t *veto, uint32_t stamp,
-                                    hipStream_t s, const LaunchTiming *timing)
-{
-    if (layout_problem(layout, -1) || !peer || !aligned16(peer) || !veto || stamp == 0 || ((uintptr_t)veto & 3))
-        return hipErrorInvalidValue;
-    SegTable t;
-    for (int i = 0; i < DPWA_LAYOUT_MAX_SEGMENTS; ++i) {
-        t.begin[i] = i < layout.count ? layout.seg[i].byte_offset : INT64_MAX;
-        t.dtype[i] = i < layout.count ? layout.seg[i].dtype : layout.seg[0].dtype;
     }
-    const int64_t total = layout_bytes(layout);
-    const int64_t g = total / (kStreamBlock * 16);   // exact: whole 4-KiB segments
-    if (g > 0x7fffffffLL) return hipErrorInvalidValue;
-    return FiniteLoads::with(finite_aux(), [&](auto aux) {
-        return launch(k_peer_finite_mixed<decltype(aux)::value>, dim3((uint32_t)g), dim3(kStreamBlock), s, timing, peer, total,
-                      t, veto, stamp);
+    return with_segments(e, absent_or_unaligned(peer), [&](int64_t total, dim3 grid, const SegTable &t) {
+        return FiniteLoads::with(finite_aux(), [&](auto aux) {
+            return launch(k_peer_finite_mixed<decltype(aux)::value>, grid, dim3(kStreamBlock), s, timing, peer, total, t, veto,
+                          stamp);
+        });
     });
 }
 

@@ -36,6 +36,20 @@ inline int64_t layout_elements(const dpwa_layout &layout)
     return n;
 }
 
+// What a launch averages, measures or checks: `n` elements of one dtype, or (DPWA_MIXED, "segmented") `n` bytes
+// whose `layout` says which 4-KiB segments hold which dtype.  A segmented payload runs the k_*_mixed kernels:
+// every 1-KiB span takes the element op of the segment it lies in, and param / peer / snap are non-null and
+// 16-B aligned.  Those rules broken, a segmented payload without its layout, an invalid layout (layout_problem)
+// and an unknown dtype are hipErrorInvalidValue to every launch that takes one.
+struct Elems {
+    int32_t dtype;
+    int64_t n;
+    const dpwa_layout *layout;   // of a DPWA_MIXED payload (null until it is known), else unused
+    bool segmented() const { return dtype == DPWA_MIXED; }
+    int64_t bytes() const { return segmented() ? n : n * (int64_t)dtype_size(dtype); }
+    int64_t elements() const { return segmented() ? layout_elements(*layout) : n; }
+};
+
 // Inputs/outputs of the device factor computation (dpwa.py:139-155).  clock_in and
 // clock_out may alias only for the one-thread factor kernel.
 struct FusedArgs {
@@ -65,9 +79,10 @@ struct FusedArgs {
     uint64_t *skips;
 };
 
-// Lerp over n elements; coefficients from `coef` (device) or, when coef is null, from (a, b).
-hipError_t launch_lerp(int32_t dtype, void *param, const void *peer, int64_t n, const dpwa_coef *coef,
-                       float a, float b, hipStream_t s);
+// Lerp over the payload; coefficients from `coef` (device) or, when coef is null, from (a, b) -- a single dtype
+// only: a segmented payload needs `coef`.
+hipError_t launch_lerp(const Elems &e, void *param, const void *peer, const dpwa_coef *coef, float a, float b,
+                       hipStream_t s);
 
 // Optional timing of one launch: HIP records the kernel's own begin/end in the two events
 // (hipExtLaunchKernelGGL), so the figure excludes the dispatch gaps an event pair around the
@@ -78,43 +93,31 @@ struct LaunchTiming {
 
 // Fused factor + lerp (one launch); a non-null `snap` also receives the result.  `oop` (the
 // resident form): the result goes to `snap` only and `param` is read, never written.
-hipError_t launch_average(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa,
-                          void *snap, hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
-
-// The averaging kernel of a DPWA_MIXED payload (k_lerp_mixed): every 1-KiB span is averaged with the
-// element op of the segment it lies in.  param / peer / snap 16-B aligned, the layout valid
-// (layout_problem), else hipErrorInvalidValue.  lerp_mixed: the coefficients from `coef` (device);
-// average_mixed: the fused average, `snap` and `oop` as launch_average.
-hipError_t launch_lerp_mixed(const dpwa_layout &layout, void *param, const void *peer, const dpwa_coef *coef,
-                             hipStream_t s);
-hipError_t launch_average_mixed(const dpwa_layout &layout, void *param, const void *peer, const FusedArgs &fa,
-                                void *snap, hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
+hipError_t launch_average(const Elems &e, void *param, const void *peer, const FusedArgs &fa, void *snap,
+                          hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
 
 // The distance to the peer (dpwa_distance, include/dpwa_hip.h; kernels.hip "distance to the peer").
 // `acc`: kDistanceWorkspaceBytes of device memory, zero before the first use; every finish leaves
 // it zero again.
 //   average_tracked   launch_average with the sums added by the same kernel (k_lerp_tracked):
 //                     16-B aligned operands and a single dtype only, else hipErrorInvalidValue
-//   distance(_mixed)  the stand-alone pass over (param, peer payload); any element alignment
+//   distance          the stand-alone pass over (param, peer payload); any element alignment for a single
+//                     dtype
 //   distance_finish   sums the accumulators into *out when the round averaged (`coef` null, or its
 //                     status OK; the record's clock is coef->new_clock, 0 without a coef)
 constexpr int64_t kDistanceWorkspaceBytes = 128 << 10;
 hipError_t launch_average_tracked(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa,
                                   void *snap, bool oop, double *acc, hipStream_t s,
                                   const LaunchTiming *timing = nullptr);
-hipError_t launch_distance(int32_t dtype, const void *param, const void *peer, int64_t n, double *acc, hipStream_t s);
-hipError_t launch_distance_mixed(const dpwa_layout &layout, const void *param, const void *peer, double *acc,
-                                 hipStream_t s);
+hipError_t launch_distance(const Elems &e, const void *param, const void *peer, double *acc, hipStream_t s);
 hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
                                   const LaunchTiming *timing = nullptr);
 
 // The non-finite peer check (kernels.hip "non-finite peer check"): one read of the peer payload; a
 // lane that finds a NaN or an inf stores `stamp` (non-zero) into *veto (device memory, 4-B aligned).
 // Any element alignment for a single dtype; a segmented payload is 16-B aligned.
-hipError_t launch_peer_finite(int32_t dtype, const void *peer, int64_t n, uint32_t *veto, uint32_t stamp, hipStream_t s,
+hipError_t launch_peer_finite(const Elems &e, const void *peer, uint32_t *veto, uint32_t stamp, hipStream_t s,
                               const LaunchTiming *timing = nullptr);
-hipError_t launch_peer_finite_mixed(const dpwa_layout &layout, const void *peer, uint32_t *veto, uint32_t stamp,
-                                    hipStream_t s, const LaunchTiming *timing = nullptr);
 
 // The distance to the peer for every parameter tensor (dpwa_param_range, include/dpwa_hip.h;
 // kernels.hip "distance to the peer, per tensor").  The device table has one ParamEntry per

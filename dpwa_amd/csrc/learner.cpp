@@ -481,10 +481,10 @@ static char *slot_payload(const dpwa_learner *l, int k)
     return l->slot_mem.ptr + (size_t)k * l->slot_stride + kPayloadOff;
 }
 
-// What the learner averages, as its measurements see it.
+// What the learner averages, as its launches and its measurements see it.
 static Payload payload(const dpwa_learner *l)
 {
-    return Payload{l->dtype, l->n, l->layout_digest ? &l->layout : nullptr, &l->ctl->coef};
+    return Payload{{l->dtype, l->n, l->layout_digest ? &l->layout : nullptr}, &l->ctl->coef};
 }
 
 int64_t dpwa::now_ns()
@@ -506,7 +506,7 @@ static int lerp_entry(const char *fn, int32_t dtype, void *param, const void *pe
 {
     if (n < 0 || (n > 0 && (!param || !peer || (!factor && !coef_dev)))) return set_error(DPWA_ERR_ARG, "%s: bad arguments", fn);
     const float f = factor ? (float)*factor : 0.f, g = factor ? (float)(1.0 - *factor) : 0.f;
-    HIP_TRY(launch_lerp(dtype, param, peer, n, factor ? nullptr : coef_dev, f, g, (hipStream_t)stream));
+    HIP_TRY(launch_lerp(Elems{dtype, n, nullptr}, param, peer, factor ? nullptr : coef_dev, f, g, (hipStream_t)stream));
     return DPWA_OK;
 }
 
@@ -571,8 +571,8 @@ int dpwa_average(int32_t dtype, void *param, const void *peer_slot, int64_t n, c
         return set_error(DPWA_ERR_ARG, "dpwa_average: a DPWA_MIXED payload needs its layout (dpwa_average_mixed)");
     if (int rc = check_method(cfg, "dpwa_average")) return rc;
     const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
-    HIP_TRY(launch_average(dtype, param, (const char *)peer_slot + kPayloadOff, n, fa, snap_payload, (hipStream_t)stream,
-                           CallerTiming(start_event, stop_event)));
+    HIP_TRY(launch_average(Elems{dtype, n, nullptr}, param, (const char *)peer_slot + kPayloadOff, fa, snap_payload,
+                           (hipStream_t)stream, CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -612,8 +612,8 @@ int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_
         return set_error(DPWA_ERR_ARG, "dpwa_average_mixed: a segmented payload is 16-byte aligned");
     if (int rc = check_method(cfg, "dpwa_average_mixed")) return rc;
     const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
-    HIP_TRY(launch_average_mixed(*layout, param, (const char *)peer_slot + kPayloadOff, fa, snap_payload,
-                                 (hipStream_t)stream, CallerTiming(start_event, stop_event)));
+    HIP_TRY(launch_average(Elems{DPWA_MIXED, layout_bytes(*layout), layout}, param, (const char *)peer_slot + kPayloadOff,
+                           fa, snap_payload, (hipStream_t)stream, CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -1099,8 +1099,7 @@ static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev
 static int finite_pass(dpwa_learner *l, const FusedArgs &fa, const void *peer, hipStream_t s)
 {
     if (!fa.veto) return DPWA_OK;
-    if (l->dtype == DPWA_MIXED) HIP_TRY(launch_peer_finite_mixed(l->layout, peer, &l->ctl->finite_veto, fa.stamp, s));
-    else HIP_TRY(launch_peer_finite(l->dtype, peer, l->n, &l->ctl->finite_veto, fa.stamp, s));
+    HIP_TRY(launch_peer_finite(payload(l), peer, &l->ctl->finite_veto, fa.stamp, s));
     return DPWA_OK;
 }
 
@@ -1139,11 +1138,7 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     if (int rc = l->measure.operands_problem("dpwa_learner_lerp", flat)) return rc;
     const Measured m{&l->measure, payload(l), flat, l->fetch.source().ptr + kPayloadOff, nullptr};
     int rc = measured_average(&m, 1, s, [&]() -> int {
-        if (l->dtype == DPWA_MIXED) {
-            HIP_TRY(launch_lerp_mixed(l->layout, flat, m.peer, &l->ctl->coef, s));
-        } else {
-            HIP_TRY(launch_lerp(l->dtype, flat, m.peer, l->n, &l->ctl->coef, 0.f, 0.f, s));
-        }
+        HIP_TRY(launch_lerp(m.p, flat, m.peer, m.p.coef, 0.f, 0.f, s));
         return DPWA_OK;
     });
     if (rc) return rc;
@@ -1164,7 +1159,6 @@ struct AvgPlan {
     bool relay = false;           // the relay's phase 2 fused into this average (k_lerp_relay)
     bool write_through = false;
     bool oop = false;             // resident: the result goes to `snap` only
-    bool mixed = false;           // a segmented payload (k_lerp_mixed): a launch of its own
     int snap_slot = -1;
 };
 
@@ -1177,7 +1171,6 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
         return set_error(DPWA_ERR_ARG, "dpwa_learner_average: a segmented payload is 16-byte aligned");
     if (int rc = l->measure.operands_problem("dpwa_learner_average", flat)) return rc;
     p = AvgPlan();
-    p.mixed = l->dtype == DPWA_MIXED;
     if (l->resident) {   // read where the parameters are (the published slot), write the next slot
         if (flat != slot_payload(l, l->res_slot))
             return set_error(DPWA_ERR_ARG, "resident learner: average the parameters where they are "
@@ -1244,17 +1237,16 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
     // (the unaligned launch_average is not timed; p.relay: relay_phase2 refuses to defer for a
     // segmented payload or a measuring learner)
-    const LaunchTiming *timing = p.mixed || p.relay || aligned16(p.flat) ? take_timing(l) : nullptr;
+    const Payload e = payload(l);
+    const LaunchTiming *timing = e.segmented() || p.relay || aligned16(p.flat) ? take_timing(l) : nullptr;
     if (int rc = finite_pass(l, p.fa, p.peer, s)) return rc;   // (never with p.relay: relay_phase2 refuses)
-    const Measured m{&l->measure, payload(l), p.flat, p.peer, p.snap, &p.fa, p.oop, timing};
+    const Measured m{&l->measure, e, p.flat, p.peer, p.snap, &p.fa, p.oop, timing};
     return measured_average(&m, 1, s, [&]() -> int {
-        if (p.mixed) {
-            HIP_TRY(launch_average_mixed(l->layout, p.flat, p.peer, p.fa, p.snap, s, timing, p.oop));
-        } else if (p.relay) {
+        if (p.relay) {   // (never a segmented payload: relay_phase2 refuses)
             HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
                                          timing, p.oop));
         } else {
-            HIP_TRY(launch_average(l->dtype, p.flat, p.peer, l->n, p.fa, p.snap, s, timing, p.oop));
+            HIP_TRY(launch_average(e, p.flat, p.peer, p.fa, p.snap, s, timing, p.oop));
         }
         return DPWA_OK;
     });
@@ -1272,9 +1264,9 @@ static int average_impl(dpwa_learner *l, void *flat, double loss, const double *
 
 // Can plan p join a batched dispatch (k_lerp_batch)?  Contiguous source, 16-B aligned operands, one
 // element type (a segmented payload is not batched).
-static bool batchable(const AvgPlan &p)
+static bool batchable(const dpwa_learner *l, const AvgPlan &p)
 {
-    return !p.relay && !p.mixed && aligned16(p.flat, p.peer, p.snap);
+    return !p.relay && !payload(l).segmented() && aligned16(p.flat, p.peer, p.snap);
 }
 
 // Launches the batchable plans in groups of the same (dtype, write-through), up to
@@ -1289,7 +1281,7 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
         dpwa_learner *la = ls[ia];
         const AvgPlan &pa = plans[ia];
         done[a] = 1;
-        if (!batchable(pa)) {
+        if (!batchable(la, pa)) {
             int rc = average_launch(la, pa, s);
             if (rc) return rc;
             continue;
@@ -1311,7 +1303,7 @@ static int launch_plans(dpwa_learner *const *ls, const AvgPlan *plans, const int
         add(la, pa);
         for (int c = a + 1; c < count && b.count < kMaxAvgBatch; ++c) {
             const int ic = idx[c];
-            if (done[c] || !batchable(plans[ic]) || ls[ic]->dtype != la->dtype ||
+            if (done[c] || !batchable(ls[ic], plans[ic]) || ls[ic]->dtype != la->dtype ||
                 plans[ic].write_through != pa.write_through || plans[ic].oop != pa.oop)
                 continue;
             if (!timing) timing = take_timing(ls[ic]);
@@ -1404,7 +1396,7 @@ static int average_many_impl(const char *fn, int32_t dtype, const dpwa_average_d
     const CallerTiming timing(start_event, stop_event);
     if (oop && count == 1) {   // one resident average: the single kernel, as a resident learner runs it
         const AvgEntry &e = b.e[0];
-        HIP_TRY(launch_average(dtype, e.param, e.peer, e.n, e.fa, e.snap, (hipStream_t)stream, timing, true));
+        HIP_TRY(launch_average(Elems{dtype, e.n, nullptr}, e.param, e.peer, e.fa, e.snap, (hipStream_t)stream, timing, true));
         return DPWA_OK;
     }
     HIP_TRY(launch_average_batch(dtype, dual, b, (hipStream_t)stream, timing, oop));

@@ -20,17 +20,12 @@ int param_ranges_problem(const char *fn, const dpwa_param_range *ranges, int64_t
 int64_t param_table(const dpwa_param_range *ranges, int64_t count, std::vector<ParamEntry> *out);
 void param_sizes(const dpwa_param_range *ranges, int64_t count, dpwa_param_sizes &z);
 
-// What a learner averages, and where its round's coefficients land.
-struct Payload {
-    int32_t dtype;
-    int64_t n;
-    const dpwa_layout *layout;   // of a DPWA_MIXED payload: null until it is set
+// What a learner averages (as every launch takes it: Elems, kernels.hpp), and where its round's coefficients land.
+struct Payload : Elems {
     const dpwa_coef *coef;
-    int64_t bytes() const { return dtype == DPWA_MIXED ? n : n * (int64_t)dtype_size(dtype); }
-    int64_t elements() const { return dtype == DPWA_MIXED ? layout_elements(*layout) : n; }
     int need_layout(const char *fn) const
     {
-        if (dtype != DPWA_MIXED || layout) return DPWA_OK;
+        if (!segmented() || layout) return DPWA_OK;
         return set_error(DPWA_ERR_STATE, "%s: a DPWA_MIXED learner has no layout yet (dpwa_learner_set_layout)", fn);
     }
 };
@@ -98,7 +93,7 @@ public:
     // type and, like a batched dispatch, aligned16 operands)?
     bool fused(const Payload &p, const void *flat, const void *peer, const void *snap) const
     {
-        return whole_ && p.dtype != DPWA_MIXED && aligned16(flat, peer, snap);
+        return whole_ && !p.segmented() && aligned16(flat, peer, snap);
     }
 
     // Before the average: counts the round, then the passes that are due (none for a fused whole-model record).
@@ -109,10 +104,7 @@ public:
             HIP_TRY(launch_param_distance(flat, peer, p.bytes(), table(), pd_.count, param_acc(), s));
             ++pd_.measured;
         }
-        if (whole_ && !fused) {
-            if (p.dtype == DPWA_MIXED) HIP_TRY(launch_distance_mixed(*p.layout, flat, peer, acc(), s));
-            else HIP_TRY(launch_distance(p.dtype, flat, peer, p.n, acc(), s));
-        }
+        if (whole_ && !fused) HIP_TRY(launch_distance(p, flat, peer, acc(), s));
         return DPWA_OK;
     }
 

@@ -1,5 +1,5 @@
 // measure_check.cpp -- dpwa_amd/csrc/measure.hpp (Measure, measured_average) against recording stand-ins of
-// everything it calls: six launch_* functions of kernels.hpp, the three host rules of distance.cpp, six HIP
+// everything it calls: five launch_* functions of kernels.hpp, the three host rules of distance.cpp, six HIP
 // runtime calls and set_error.  No HIP runtime is linked: the calls land in the log below, and every case
 // asserts the exact log.  The "launch the average" callables here stand for the three sites of learner.cpp
 // (dpwa_learner_lerp, average_launch, the batched branch of launch_plans) and log 'A' / 'L' / 'B'.
@@ -19,7 +19,7 @@ using namespace dpwa;
 namespace {
 
 struct Call {
-    std::string op;                   // P Pf D Dm F T, or what an average callable logs
+    std::string op;                   // P Pf D F T, or what an average callable logs
     const void *a, *b, *c, *d;        // the pointers, in the launch's own order (see the stand-ins)
     int64_t n;                        // n / bytes
     int64_t k;                        // count / dtype
@@ -102,13 +102,10 @@ hipError_t launch_param_distance_finish(double *acc, const ParamEntry *table, in
     if (timing) abort();
     return record({"Pf", acc, table, out, nullptr, 0, count, coef, s});
 }
-hipError_t launch_distance(int32_t dtype, const void *param, const void *peer, int64_t n, double *acc, hipStream_t s)
+// d: the layout of a segmented payload (k DPWA_MIXED, n its bytes), null for a single dtype
+hipError_t launch_distance(const Elems &e, const void *param, const void *peer, double *acc, hipStream_t s)
 {
-    return record({"D", param, peer, acc, nullptr, n, dtype, nullptr, s});
-}
-hipError_t launch_distance_mixed(const dpwa_layout &layout, const void *param, const void *peer, double *acc, hipStream_t s)
-{
-    return record({"Dm", param, peer, acc, &layout, 0, DPWA_MIXED, nullptr, s});
+    return record({"D", param, peer, acc, e.layout, e.n, e.dtype, nullptr, s});
 }
 hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
                                   const LaunchTiming *timing)
@@ -200,8 +197,8 @@ const dpwa_layout &mixed_layout()
     return y;
 }
 
-Payload single(int32_t dtype = DPWA_F32, int who = 0) { return Payload{dtype, N, nullptr, &g_coef[who]}; }
-Payload mixed() { return Payload{DPWA_MIXED, 12288, &mixed_layout(), &g_coef[0]}; }
+Payload single(int32_t dtype = DPWA_F32, int who = 0) { return Payload{{dtype, N, nullptr}, &g_coef[who]}; }
+Payload mixed() { return Payload{{DPWA_MIXED, 12288, &mixed_layout()}, &g_coef[0]}; }
 
 // "launch the average": logs `op` with the member's operands, as a site's own launch would receive them
 struct Average {
@@ -308,12 +305,12 @@ int main()
         d.b = peer;
         expect("whole: lerp = D L F", {d, {"L", flat, peer, nullptr, nullptr, N, DPWA_BF16, p.coef, S}, F});
 
-        // 3. DPWA_MIXED: the mixed pass, and the finish counts the element slots of the segments
+        // 3. DPWA_MIXED: the pass gets the layout, and the finish counts the element slots of the segments
         const Payload x = mixed();
         check("whole: mixed", average(m, x, flat, peer, snap) == DPWA_OK);
-        expect("whole: mixed = Dm A F(5120)", {{"Dm", flat, peer, b.acc(), &mixed_layout(), 0, DPWA_MIXED, nullptr, S},
-                                               {"A", flat, peer, snap, nullptr, 12288, DPWA_MIXED, x.coef, S},
-                                               {"F", b.acc(), b.rec(), nullptr, nullptr, 1024 + 2048 + 2048, 0, x.coef, S}});
+        expect("whole: mixed = D A F(5120)", {{"D", flat, peer, b.acc(), &mixed_layout(), 12288, DPWA_MIXED, nullptr, S},
+                                              {"A", flat, peer, snap, nullptr, 12288, DPWA_MIXED, x.coef, S},
+                                              {"F", b.acc(), b.rec(), nullptr, nullptr, 1024 + 2048 + 2048, 0, x.coef, S}});
 
         // 9. off and on again keeps the buffer
         check("whole: off", m.set_whole("fn", false, false) == DPWA_OK && !m.whole() && m.record() == b.rec());
@@ -345,11 +342,11 @@ int main()
         Call Pm = P;
         Pm.n = 12288;   // a mixed payload's n is its bytes
         check("both: mixed", average(m, x, flat, peer, snap) == DPWA_OK);
-        expect("both: mixed = P Dm A F Pf", {Pm,
-                                             {"Dm", flat, peer, b.acc(), &mixed_layout(), 0, DPWA_MIXED, nullptr, S},
-                                             {"A", flat, peer, snap, nullptr, 12288, DPWA_MIXED, x.coef, S},
-                                             {"F", b.acc(), b.rec(), nullptr, nullptr, 5120, 0, x.coef, S},
-                                             Pf});
+        expect("both: mixed = P D A F Pf", {Pm,
+                                            {"D", flat, peer, b.acc(), &mixed_layout(), 12288, DPWA_MIXED, nullptr, S},
+                                            {"A", flat, peer, snap, nullptr, 12288, DPWA_MIXED, x.coef, S},
+                                            {"F", b.acc(), b.rec(), nullptr, nullptr, 5120, 0, x.coef, S},
+                                            Pf});
         // 6. the split path, both on: P D L F Pf
         check("both: lerp", lerp(m, p, flat, peer) == DPWA_OK);
         expect("both: lerp = P D L F Pf", {P,
@@ -448,7 +445,7 @@ int main()
                                                   !m.param() && g_error == "dpwa_learner_set_param_distance" + sentence);
         check("refuse: every = 0", m.set_param("fn", kRanges, kCount, 0, p, false) == DPWA_ERR_ARG && !m.param() &&
                                        g_error == "fn: every = 0, it must be >= 1");
-        const Payload no_layout{DPWA_MIXED, 12288, nullptr, &g_coef[0]};
+        const Payload no_layout{{DPWA_MIXED, 12288, nullptr}, &g_coef[0]};
         check("refuse: no layout yet", m.set_param("fn", kRanges, kCount, 1, no_layout, false) == DPWA_ERR_STATE && !m.param() &&
                                            g_error == "fn: a DPWA_MIXED learner has no layout yet (dpwa_learner_set_layout)");
         check("refuse: switching off with a relay pending is fine", m.set_whole("fn", false, true) == DPWA_OK);

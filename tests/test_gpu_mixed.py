@@ -4,7 +4,8 @@ factor-then-lerp path, and DpwaPyTorchAdapter on models with fp32 norms in a bf1
 its three forms, alone (self-peer) and as two co-resident learners -- every averaged segment and
 parameter against the host reference of its dtype (tests/mixed_ref.py: oracle.lerp for float32 and
 bfloat16, torch-CPU eager for float16, and torch-CPU eager tensor by tensor end to end; never the
-library or torch on the device).  Then what is refused.
+library or torch on the device).  Then what is refused, and a one-segment layout against the
+single-dtype entries (average, finite check, distance).
 
 Bar: bit-equal, NaN positions coinciding.  All shapes are tiny: a segment is at most three 4-KiB
 blocks, i.e. twelve one-wave spans."""
@@ -20,7 +21,9 @@ from dpwa_amd.flat import c_layout
 from dpwa_amd.group import LocalGroup
 from dpwa_amd.learner import Learner
 from oracle import policy as opolicy
+from tests import dist_ref
 from tests import mixed_ref as ref
+from tests.test_gpu_distance import check_record, fresh_record, read_record, workspace
 from tests.test_gpu_f16 import FUSED
 from tests.test_gpu_kernels import average_slot, ptr, stream
 from tests.test_gpu_self_peer import write_self_cfg
@@ -450,3 +453,101 @@ def test_a_single_dtype_model_binds_as_before(tmp_path):
     assert h.dtype == _lib.BF16 and h.n == ad.flat.numel and v.value == 1
     ad.update_wait(1.0)
     ad.connection.close()
+
+
+# ---------------------------------------------------------------- 5. one segment is the single-dtype call
+@functools.lru_cache(maxsize=None)
+def seam_operands(d, nbytes):
+    """(param bits, peer bits) of `nbytes` of dtype d: N(0,1), -0 meeting the smallest subnormal in the
+    first element and the largest finite value meeting +0 in the last.  Made once, read-only."""
+    n = nbytes // ref.SIZE[d]
+    rng = np.random.default_rng(nbytes + ref.CODE[d])
+    p, q = dist_ref.to_bits(d, rng.standard_normal(n)), dist_ref.to_bits(d, rng.standard_normal(n))
+    hard = ref.HARD[d]
+    p[0], q[0] = hard[1], hard[2]
+    p[-1], q[-1] = hard[7], hard[0]
+    p.setflags(write=False)
+    q.setflags(write=False)
+    return p, q
+
+
+def average_single(d, n, p, slot, case, snap):
+    """average_mixed's twin through dpwa_average."""
+    method, value, thr, my_clock, _, loss, _ = case
+    clock = torch.tensor([my_clock, -1.0], dtype=torch.float64, device=DEV)
+    coef = torch.zeros(32, dtype=torch.uint8, device=DEV)
+    cfg = _lib.Interp(opolicy.METHODS[method], 0, float(value or 0.0), float(thr))
+    _lib.call("dpwa_average", ref.CODE[d], ptr(p), ptr(slot), n, ctypes.byref(cfg), ptr(clock), float(loss), ptr(coef),
+              ptr(snap) if snap is not None else None, stream(), None, None)
+    torch.cuda.synchronize()
+    return _lib.Coef.from_buffer_copy(coef.cpu().numpy().tobytes()), clock[1].item()
+
+
+@pytest.mark.parametrize("nbytes", [4096, 8192])
+@pytest.mark.parametrize("d", ref.ORDER)
+def test_a_single_segment_is_the_single_dtype_call(d, nbytes):
+    """A layout of one segment (one and two 4-KiB blocks: 4 and 8 spans) through the three _mixed
+    entries against the single-dtype entries with n = bytes / size, on copies of the same operands.
+    The average, plain and write-through: parameters, snapshot payload, dpwa_coef and clock bit-equal
+    to each other and to the host reference of the dtype and the oracle policy.  The finite check,
+    without a non-finite element and with +inf in the peer's last element: both veto words are what
+    the host expects.  The distance: both within tests/dist_ref.py's bound of its fsum reference."""
+    n = nbytes // ref.SIZE[d]
+    spec = [(d, n)]
+    lay, total = layout_of(spec)
+    assert total == nbytes and len(lay) == 1
+    p_bits, q_bits = seam_operands(d, nbytes)
+    p_h, q_h = p_bits.view(np.uint8), q_bits.view(np.uint8)
+    case = FUSED[1]
+    method, value, thr, my_clock, peer_clock, loss, peer_loss = case
+    f, new_clock = opolicy.factor_and_clock(method, value, thr, my_clock, peer_clock, loss, peer_loss)
+    want = ref.lerp(spec, p_h, q_h, f)
+    for write_through in (False, True):
+        left = []
+        for mixed in (True, False):
+            p, p_whole = on_device(p_h)
+            slot = average_slot(tens(q_h).to(DEV), peer_clock, peer_loss)
+            snap, snap_whole = on_device(np.full(total, 0x55, dtype=np.uint8)) if write_through else (None, None)
+            c, got_clock = average_mixed(lay, p, slot, case, snap) if mixed else average_single(d, n, p, slot, case, snap)
+            what = (d, nbytes, write_through, "mixed" if mixed else "single")
+            assert ref.same(spec, host(p), want) is None, (what, ref.same(spec, host(p), want))
+            assert c.status == 0 and c.factor == f and c.a == np.float32(f) and c.b == np.float32(1.0 - f), what
+            assert got_clock == new_clock == c.new_clock, what
+            assert guard_intact(p_whole) and np.array_equal(host(slot[OFF:]), q_h), what
+            if write_through:
+                assert ref.same(spec, host(snap), want) is None and guard_intact(snap_whole), what
+            left.append((host(p).tobytes(), host(snap).tobytes() if write_through else None, bytes(c), got_clock))
+        assert left[0] == left[1], (d, nbytes, write_through, "the two entries leave different bytes")
+
+    clean = tens(q_h).to(DEV)
+    q_inf = np.array(q_bits)
+    q_inf[-1] = ref.HARD[d][9]
+    poisoned = tens(q_inf.view(np.uint8)).to(DEV)
+    sentinel, stamp = 0x5a5a5a5a, 0x9e3779b9
+    words = torch.full((4,), sentinel, dtype=torch.int32, device=DEV)
+    for i, (buf, mixed) in enumerate(((clean, True), (clean, False), (poisoned, True), (poisoned, False))):
+        word = ctypes.c_void_p(words.data_ptr() + 4 * i)
+        if mixed:
+            _lib.call("dpwa_check_finite_mixed", ctypes.byref(c_layout(lay)), ptr(buf), word, stamp, stream(), None, None)
+        else:
+            _lib.call("dpwa_check_finite", ref.CODE[d], ptr(buf), n, word, stamp, stream(), None, None)
+    torch.cuda.synchronize()
+    assert words.cpu().numpy().view(np.uint32).tolist() == [sentinel, sentinel, stamp, stamp], (d, nbytes)
+
+    # (the largest finite value's square hides every other term under the bound: once more without it)
+    p_small = np.array(p_bits)
+    p_small[-1] = ref.HARD[d][1]
+    for name, pb in (("hard", p_bits), ("no-huge", p_small)):
+        want_dist = dist_ref.reference(d, pb, q_bits)
+        p, q = tens(pb.view(np.uint8)).to(DEV), tens(q_h).to(DEV)
+        for mixed in (True, False):
+            rec = fresh_record()
+            if mixed:
+                _lib.call("dpwa_measure_distance_mixed", ctypes.byref(c_layout(lay)), ptr(p), ptr(q), ptr(workspace()),
+                          ptr(rec), stream())
+            else:
+                _lib.call("dpwa_measure_distance", ref.CODE[d], ptr(p), ptr(q), n, ptr(workspace()), ptr(rec), stream())
+            torch.cuda.synchronize()
+            check_record(read_record(rec), want_dist, n, 0.0, (d, nbytes, name, "mixed" if mixed else "single"))
+        assert np.array_equal(host(p), pb.view(np.uint8)) and np.array_equal(host(q), q_h)
+    assert not bool(workspace().any()), "both entries leave the accumulators zero"
