@@ -271,7 +271,133 @@ def run(shared, rank, world, only=None):
     return done
 
 
-def rank_main(rank, world, shared, only=None):
+# ---------------------------------------------------------------- payloads beyond 2^32 bytes
+def attach_big(shared, rank, world, lr):
+    """Enables the relay on `lr` and maps every other rank's slots and relay buffer.  Allocations this
+    large are chunks shared as file descriptors: each rank serves its own (dpwa_amd/group.py's
+    _FdServer, as DistGroup.on_bind does) and says where on the board, in the header's place."""
+    import struct
+
+    from dpwa_amd import _lib
+    from dpwa_amd.group import _FdServer, _fetch_fds
+    _lib.call("dpwa_learner_relay_enable", lr.handle, world, rank)
+    buf = ctypes.create_string_buffer(HANDLE)
+    _lib.call("dpwa_learner_relay_handle", lr.handle, buf, HANDLE)
+    slot_fds, slot_chunk = lr.export_fds(0)
+    relay_fds, relay_chunk = lr.export_fds(1)
+    server = _FdServer(slot_fds + relay_fds, world - 1) if (slot_fds or relay_fds) else None
+    address = server.address.encode() if server else b""
+    fmt = "<6q64s"
+    shared.put(rank, 0, lr.ipc_handle())
+    shared.put(rank, HANDLE, buf.raw)
+    shared.put(rank, 2 * HANDLE, struct.pack(fmt, len(address), len(slot_fds), slot_chunk, len(relay_fds), relay_chunk,
+                                             os.getpid(), address))
+    try:
+        shared.wait()
+        infos = {r: struct.unpack(fmt, shared.get(r, 2 * HANDLE, struct.calcsize(fmt))) for r in range(world) if r != rank}
+        if server is not None:
+            server.allow(info[5] for info in infos.values())
+        for r, (alen, ns, cs, nr, cr, _, addr) in infos.items():
+            fds = _fetch_fds(addr[:alen].decode(), ns + nr) if alen else []
+            try:
+                if ns:
+                    lr.attach_fds(r, shared.get(r, 0, HANDLE), fds[:ns], cs)
+                else:
+                    lr.attach_ipc(r, shared.get(r, 0, HANDLE))
+                blob = ctypes.create_string_buffer(shared.get(r, HANDLE, HANDLE), HANDLE)
+                if nr:
+                    arr = (ctypes.c_int * nr)(*fds[ns:])
+                    _lib.call("dpwa_learner_relay_attach_fds", lr.handle, r, r, blob, HANDLE, arr, nr, cr)
+                else:
+                    _lib.call("dpwa_learner_relay_attach", lr.handle, r, r, blob, HANDLE)
+            finally:
+                for fd in fds:
+                    os.close(fd)
+    except BaseException:
+        if server is not None:
+            server.abort()
+            server.thread.join(5)
+            for fd in server.fds:
+                os.close(fd)
+            server.fds = []
+        raise
+    if server is not None:
+        server.finish()
+    shared.wait()                       # every rank has attached
+
+
+def run_big(shared, rank, world, forms):
+    """tests/test_gpu_big.py's relay case: a bf16 payload of big_ref.N elements (a stripe border beyond
+    byte 2^31, the second stripe across byte 2^32), picks big_ref.RELAY_PICKS, one round per form with a
+    fresh learner: the staged payload (gathered form) and the averaged parameters against big_ref's
+    model, window by window and, on the device, element by element."""
+    import torch
+
+    from dpwa_amd import _lib
+    from dpwa_amd.devview import device_tensor
+    from dpwa_amd.learner import Learner
+    from oracle import policy as opolicy
+    from tests import big_ref
+    from tests import test_gpu_big as big
+    assert world == big_ref.RELAY_WORLD
+    dev = torch.device("cuda", 0)
+    pl = big_ref.relayed()
+    n = big_ref.N["bf16"]
+    pick = big_ref.RELAY_PICKS[rank]
+    mine, peer = big_ref.learner(pl, rank), big_ref.learner(pl, pick)
+    done = 0
+    for form in forms:
+        what = "relay beyond 2^32 bytes, form %s, rank %d picks %d" % (form, rank, pick)
+        lr = Learner(dev, n, TORCH["bf16"], big.CFG)
+        attach_big(shared, rank, world, lr)
+        sh, sp, side = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.call("dpwa_learner_pointers", lr.handle, None, None, ctypes.byref(sh), ctypes.byref(sp))
+        staging = device_tensor(sp.value, pl.nbytes, torch.uint8, dev)
+        _lib.call("dpwa_learner_side_stream", lr.handle, ctypes.byref(side))
+        side = torch.cuda.ExternalStream(side.value, device=dev)
+        picks = torch.tensor(big_ref.RELAY_PICKS, dtype=torch.int32, device=dev)
+        flat = big.Buffer(pl, mine)
+        _lib.call("dpwa_learner_publish", lr.handle, flat.ptr, 0.5 + rank, None, big.stream())
+        staging.fill_(big_ref.RELAY_FILL)
+        torch.cuda.synchronize()
+        shared.wait()
+        _lib.call("dpwa_learner_relay_wait", lr.handle, big.stream())
+        _lib.call("dpwa_learner_relay_phase1", lr.handle, ctypes.c_void_p(picks.data_ptr()), 1, big_ref.RELAY_BLOCKS,
+                  big.stream())
+        side.synchronize()
+        shared.wait()
+        _lib.call("dpwa_learner_relay_phase2", lr.handle, ctypes.c_void_p(picks.data_ptr()), pick, 1, big_ref.RELAY_BLOCKS,
+                  0 if form == "gather" else 1)
+        _lib.call("dpwa_learner_average", lr.handle, flat.ptr, 0.5 + rank, None, big.stream())
+        torch.cuda.synchronize()
+        want = big_ref.relay_model(pl, mine, peer, form)
+        big.expect(flat, want["param"], (what, "the averaged parameters"), const=big_ref.lerp_const(mine, peer))
+        got, first = big.outcome(staging, pl, peer.const if form == "gather" else
+                                 {"bf16": int(np.full(2, big_ref.RELAY_FILL, dtype=np.uint8).view(np.uint16)[0])})
+        if form == "gather":
+            failed = big_ref.failures(pl, got, want["staged"], exact_bytes=True)
+            assert not failed, (what, "the staged payload", failed, got.stray, first)
+        else:                           # the fused form gathers nothing
+            assert got.stray == 0 and all((w == big_ref.RELAY_FILL).all() for _, _, w in got.windows), (
+                what, "the staging buffer was written", got.stray, first)
+        _, clock = opolicy.factor_and_clock("constant", big_ref.FACTOR, 0.0, 1.0, 1.0, 0.5 + rank, 0.5 + pick)
+        assert lr.read_clock() == clock, (what, "the clock", lr.read_clock(), clock)
+        head, hdr, v = np.zeros(4096, dtype=np.uint8), ctypes.create_string_buffer(ref.HEADER), ctypes.c_uint64()
+        _lib.call("dpwa_learner_read_snapshot", lr.handle, hdr, ctypes.c_void_p(head.ctypes.data), head.nbytes, ctypes.byref(v))
+        assert v.value == 1 and differing(head, mine.bytes(0, 4096)) is None, (what, "this rank's snapshot changed")
+        shared.wait()                   # nobody reads this rank's slots or relay buffer any more
+        del flat, staging
+        lr.close()
+        torch.cuda.empty_cache()
+        done += 1
+    return done
+
+
+def big_rank_main(rank, world, shared, forms=None):
+    rank_main(rank, world, shared, forms, run=run_big)
+
+
+def rank_main(rank, world, shared, only=None, run=run):
     """Process entry: exit status 0, or 1 after a report ("failed", text) -- 2 when another rank broke
     the barrier first."""
     status, report = 0, None

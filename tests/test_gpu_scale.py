@@ -77,6 +77,10 @@ def test_full_size_gossip_round(tmp_path, n, dtype):
             t[s:e] = torch.randn(e - s, device=DEV, generator=g).to(dtype)
         flats.append(t)
     win = [slice(0, 1 << 20), slice(n // 2, n // 2 + 4099), slice(n - (1 << 20) - 3, n)]
+    # 4099 elements straddling byte 2^31, every byte 2^32 * k and elements 2^31 and 2^32, where the size reaches them
+    size = t.element_size()
+    lines = {(1 << 31) // size} | {(k << 32) // size for k in range(1, (n * size >> 32) + 1)} | {1 << 31, 1 << 32}
+    win += [slice(c - 2049, c + 2050) for c in sorted(lines) if c + 2050 <= n]
     before = [[f[w].clone() for w in win] for f in flats]
     conns = [DpwaConnection(nm, str(cfg), seed=1 + i, group=group) for i, nm in enumerate(["A", "B"])]
     for c, f in zip(conns, flats):
@@ -91,6 +95,13 @@ def test_full_size_gossip_round(tmp_path, n, dtype):
         p, q = before[0][k], before[1][k]
         want = 0.5 * q + (1 - 0.5) * p                                    # torch eager, same device
         assert torch.equal(flats[0][w].view(iv), want.view(iv))
+        got = flats[0][w].view(iv).cpu().numpy()                          # and the host oracle
+        if dtype == torch.bfloat16:
+            host = olerp.lerp_bf16(p.view(iv).cpu().numpy().view(np.uint16), q.view(iv).cpu().numpy().view(np.uint16), 0.5)
+            assert olerp.bits_equal(got.view(np.uint16), host), (k, w)
+        else:
+            host = olerp.lerp_f32(p.cpu().numpy(), q.cpu().numpy(), 0.5)
+            assert olerp.bits_equal(got.view(np.float32), host), (k, w)
     for c in conns:
         assert c.clock == 1.0
         c.close()
