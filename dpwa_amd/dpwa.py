@@ -471,6 +471,9 @@ class DpwaConnection:
         self._sent = None           # resident: (parameters tensor, its version) at update_send
         # transport of copying fetches: "copy" (hipMemcpyAsync) or "kernel[:blocks]"
         self._pull = pull if pull is not None else os.environ.get("DPWA_PULL", "copy")
+        # created with a relay pull: the relay buffers are made at the bind even if set_pull has chosen
+        # another transport for the first rounds by then (set_pull's promise about such a connection)
+        self._relay_created = self._pull.partition(":")[0] in RELAY_PULLS
         self._out = ctypes.c_int()
         self._out_ref = ctypes.byref(self._out)
         self._f_update_send = lib.dpwa_node_update_send
@@ -858,7 +861,8 @@ class DpwaConnection:
             _lib.call("dpwa_learner_set_param_distance", self._learner.handle, arr, len(self._param_ranges),
                       self._distance_every)
             self._param_distance = ParameterDistances(self._learner, [r[0] for r in self._param_ranges], where)
-        if self._pull.partition(":")[0] in RELAY_PULLS:
+        if self._pull.partition(":")[0] in RELAY_PULLS or \
+                (self._relay_created and getattr(self._group, "relay_capable", False)):
             if not hasattr(self._group, "relay_blocks"):
                 raise ValueError("the relay pull needs a DistGroup (one learner per rank)")
             self._group.relay_blocks = 1     # allocate + exchange the relay buffers in on_bind
@@ -870,7 +874,8 @@ class DpwaConnection:
         """Transport of copying fetches: 'copy' (hipMemcpyAsync on the side stream),
         'kernel[:blocks]' (pull kernel), 'relay[:blocks]' (DistGroup only, multi-link
         two-phase relay; the connection must have been created with a relay pull so the
-        relay buffers exist) or 'relay-avg[:blocks]' (the same relay with its second phase
+        relay buffers exist -- they do even if this was called with another transport before
+        the first update_send) or 'relay-avg[:blocks]' (the same relay with its second phase
         fused into the average: the averaging kernel reads the peer's stripes where the first
         phase left them).  Every rank must switch between the same two rounds."""
         kind, _, blocks = mode.partition(":")

@@ -218,6 +218,7 @@ class DistGroup:
     """One learner per rank; see the module docstring."""
     eager_fetch = True
     zero_copy = False
+    relay_capable = True         # lock-step rounds: the relay pulls are available
 
     def __init__(self, nodes, name, process_group=None):
         import torch.distributed as dist
@@ -384,6 +385,7 @@ class AsyncDistGroup(DistGroup):
     the reference's RxThread Lock (conn.py:76-79, 109-110) -- and a rank that has closed or
     died answers as a refused connection (conn.py:253-256).  The copy and kernel pulls and
     write-through snapshots are supported; the relay needs lock-step rounds."""
+    relay_capable = False
 
     def __init__(self, nodes, name, process_group=None, publish_timeout_ms=None):
         super().__init__(nodes, name, process_group)
