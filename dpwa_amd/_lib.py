@@ -95,6 +95,17 @@ class ParamSizes(ctypes.Structure):
                 ("record_bytes", ctypes.c_int64), ("max_rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+CONSENSUS_MAX = 8            # DPWA_CONSENSUS_MAX
+
+
+class ConsensusRecord(ctypes.Structure):
+    """dpwa_consensus_record: the 128-byte record of a group's consensus."""
+    _fields_ = [("norm2", ctypes.c_double), ("spread2", ctypes.c_double),
+                ("member_spread2", ctypes.c_double * CONSENSUS_MAX), ("n", ctypes.c_int64),
+                ("members", ctypes.c_int32), ("reserved", ctypes.c_int32), ("version", ctypes.c_uint64),
+                ("pad", ctypes.c_uint64 * 3)]
+
+
 PARAM_ALIGN = 256            # DPWA_PARAM_ALIGN
 PARAM_HEAD_BYTES = 16        # dpwa_param_distance_head {double clock; int64 count}; 16-byte pairs follow
 
@@ -149,6 +160,10 @@ SIGNATURES = {
     "dpwa_learner_param_distance_rounds": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     "dpwa_check_finite": [_i32, _vp, _i64, _vp, ctypes.c_uint32, _vp, _vp, _vp],
     "dpwa_check_finite_mixed": [ctypes.POINTER(Layout), _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp],
+    "dpwa_consensus_workspace": [ctypes.POINTER(_i64)],
+    "dpwa_consensus": [_i32, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_consensus_mixed": [ctypes.POINTER(Layout), _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_learner_consensus": [_vp, ctypes.POINTER(_i32), _int, _u64, _vp, _vp, _vp],
     "dpwa_learner_set_finite_check": [_vp, _int],
     "dpwa_learner_finite_skips": [_vp, ctypes.POINTER(_u64)],
     "dpwa_node_set_finite_check": [_vp, _int],

@@ -365,6 +365,16 @@ class DpwaPyTorchAdapter:
         read the device record and synchronise with the stream that averaged; ``.tensor()`` does not."""
         return self._conn.last_distance
 
+    def consensus(self, out=None, distance=True, members=None):
+        """``DpwaConnection.consensus`` for the model (device transport): the returned object also has
+        ``parameters()`` -> ``{name: tensor}``, views of the mean with the parameters' shapes and
+        dtypes, and ``load_into(module)``, which copies them into a model of the same structure."""
+        if type(self._conn) is not DpwaConnection:
+            from ..consensus import WIRE
+            raise ValueError(WIRE)
+        from ..consensus import ModelConsensus
+        return ModelConsensus(self._conn.consensus(out, distance, members), self._flat)
+
     @property
     def connection(self):
         return self._conn

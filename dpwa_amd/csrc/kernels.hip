@@ -2295,4 +2295,267 @@ hipError_t launch_store_u64(uint64_t *p, uint64_t v, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- consensus of a group
+// Opt-in and read-only (include/dpwa_hip.h dpwa_consensus): the element-wise mean of U = 1..8 published
+// snapshots and how far the members are from it, in one pass that reads every source once.  For
+// every element, the members in the order given:
+//   s = ((x_0 + x_1) + ...) + x_{U-1}     each operand widened exactly to fp64, fp64 adds
+//   m = s * r                             r = 1.0 / U formed once by the host: a multiply, no division
+//   out = f32(m)                          v_cvt_f32_f64, RNE, subnormals kept; a 16-bit payload then
+//                                         rounds that fp32 value RNE with the converts OpsBF16 / OpsF16
+//                                         use -- two roundings, on purpose
+//   norm2 += m * m      spread2_i += (x_i - m) * (x_i - m)      against the fp64 m, all in fp64
+// group_span's shape: one-wave workgroups over an exact grid of 1-KiB spans, all U 16-byte loads
+// issued first (`nt`: every byte is read once), one 16-byte store of the mean (`sc1`, as a
+// snapshot store); lanes past the end load zeros, whose mean is zero and which add 0 to every sum;
+// the ragged tail of a single-dtype payload element by element in workgroup 0.  TRACK: the wave
+// sums its U + 1 partial sums with the butterfly and lanes 0..U add them with ONE fp64 atomic
+// instruction into the 128-byte row `span mod kDistAccs` of the workspace -- norm2 first, then
+// spread2_0.. -- which k_consensus_finish sums in a fixed order and leaves zero.  STORE off:
+// nothing is stored to any payload.
+struct ConsensusArgs {
+    const void *src[kMaxConsensus];
+    void *out;      // STORE
+    double *acc;    // TRACK
+    double r;
+};
+
+// element e of a lane's 16-byte item / one element of the tail, widened exactly to fp64
+__device__ __forceinline__ double cons_elem(OpsF32, u32x4 v, int e) { return (double)__uint_as_float(v[e]); }
+__device__ __forceinline__ double cons_elem(OpsBF16, u32x4 v, int e)
+{
+    return (double)((e & 1) ? bf_hi(v[e >> 1]) : bf_lo(v[e >> 1]));
+}
+__device__ __forceinline__ double cons_elem(OpsF16, u32x4 v, int e)
+{
+    const uint32_t w = v[e >> 1];   // (a value of its own: a bit_cast of the vector's element read word 0 for every e)
+    const f16x2v h = __builtin_bit_cast(f16x2v, w);
+    return (double)((e & 1) ? h.y : h.x);
+}
+__device__ __forceinline__ double cons_elem_s(OpsF32, float x) { return (double)x; }
+__device__ __forceinline__ double cons_elem_s(OpsBF16, uint16_t x) { return (double)bf_lo(x); }
+__device__ __forceinline__ double cons_elem_s(OpsF16, uint16_t x) { return (double)__builtin_bit_cast(_Float16, x); }
+
+// the fp32 means of an item as the payload's type
+__device__ __forceinline__ u32x4 cons_pack(OpsF32, const float *f)
+{
+    return u32x4{__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3])};
+}
+__device__ __forceinline__ u32x4 cons_pack(OpsBF16, const float *f)
+{
+    return u32x4{pk_bf16(f[0], f[1]), pk_bf16(f[2], f[3]), pk_bf16(f[4], f[5]), pk_bf16(f[6], f[7])};
+}
+__device__ __forceinline__ u32x4 cons_pack(OpsF16, const float *f)
+{
+    return u32x4{pk_f16(f[0], f[1]), pk_f16(f[2], f[3]), pk_f16(f[4], f[5]), pk_f16(f[6], f[7])};
+}
+__device__ __forceinline__ float cons_pack_s(OpsF32, float f) { return f; }
+__device__ __forceinline__ uint16_t cons_pack_s(OpsBF16, float f) { return (uint16_t)(pk_bf16(f, 0.0f) & 0xffffu); }
+__device__ __forceinline__ uint16_t cons_pack_s(OpsF16, float f) { return (uint16_t)(pk_f16(f, 0.0f) & 0xffffu); }
+
+// One element: the members' values in order -> the fp32 mean; TRACK: its terms into the lane's sums.
+template <int U, bool TRACK>
+__device__ __forceinline__ float cons_one(const double (&x)[U], double r, double &n2, double (&sp)[U])
+{
+    double s = x[0];
+#pragma unroll
+    for (int i = 1; i < U; ++i) s = s + x[i];
+    const double m = s * r;
+    if constexpr (TRACK) {
+        n2 = n2 + m * m;
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            const double d = x[i] - m;
+            sp[i] = sp[i] + d * d;
+        }
+    }
+    return (float)m;
+}
+
+// A lane's item of every member -> the item of the mean, its elements in order.
+template <class Ops, int U, bool TRACK>
+__device__ __forceinline__ u32x4 cons_item(const u32x4 (&v)[U], double r, double &n2, double (&sp)[U])
+{
+    float f[Ops::PER];
+#pragma unroll
+    for (int e = 0; e < Ops::PER; ++e) {
+        double x[U];
+#pragma unroll
+        for (int i = 0; i < U; ++i) x[i] = cons_elem(Ops{}, v[i], e);
+        f[e] = cons_one<U, TRACK>(x, r, n2, sp);
+    }
+    return cons_pack(Ops{}, f);
+}
+
+// The wave's U + 1 sums into the row of `span`: one atomic instruction, lane 0 adding norm2 and
+// lane 1 + i member i's spread2 (a select over registers by the lane, no indexed access).
+template <int U>
+__device__ __forceinline__ void cons_commit(double *acc, uint32_t span, double n2, double (&sp)[U])
+{
+    static_assert(U + 1 <= kDistAccStride, "the sums of one span share a row");
+    const int lane = threadIdx.x & 63;
+    double v = wave_sum(n2);
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const double t = wave_sum(sp[i]);
+        v = lane == i + 1 ? t : v;
+    }
+    if (lane <= U) unsafeAtomicAdd(acc + (size_t)(span % kDistAccs) * kDistAccStride + lane, v);
+}
+
+template <class Ops, int U, bool STORE, bool TRACK>
+__global__ __launch_bounds__(kStreamBlock) void k_consensus(ConsensusArgs a, int64_t n)
+{
+    using S = typename Ops::S;
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t vbytes = n / Ops::PER * 16;
+    const int64_t off = (int64_t)blockIdx.x * SPAN;
+    const int lane_off = threadIdx.x * 16;
+    u32x4 v[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j)   // all loads first
+        v[j] = span_load<u32x4>(span_rsrc<SPAN>(a.src[j], off, vbytes), lane_off);
+    __builtin_amdgcn_sched_barrier(0);   // (left alone, the scheduler issues the 8th load behind the first seven's adds)
+    [[maybe_unused]] double n2 = 0.0, sp[U];
+#pragma unroll
+    for (int i = 0; i < U; ++i) sp[i] = 0.0;
+    const u32x4 mean = cons_item<Ops, U, TRACK>(v, a.r, n2, sp);
+    if constexpr (STORE) span_store<u32x4>(span_rsrc<SPAN>(a.out, off, vbytes), lane_off, mean);
+    const int64_t tail = n / Ops::PER * Ops::PER;
+    if (blockIdx.x == 0 && threadIdx.x < n - tail) {
+        const int64_t j = tail + threadIdx.x;
+        double x[U];
+#pragma unroll
+        for (int i = 0; i < U; ++i) x[i] = cons_elem_s(Ops{}, reinterpret_cast<const S *>(a.src[i])[j]);
+        const float f = cons_one<U, TRACK>(x, a.r, n2, sp);
+        if constexpr (STORE) reinterpret_cast<S *>(a.out)[j] = cons_pack_s(Ops{}, f);
+    }
+    if constexpr (TRACK) cons_commit<U>(a.acc, blockIdx.x, n2, sp);
+}
+
+// The same span code over a segmented payload: the span's element type is its segment's, looked up
+// from the span's byte offset after the loads were issued (as k_lerp_mixed); no ragged tail;
+// padding bytes are zeros in every member, whose mean is zero and which add 0.
+template <int U, bool STORE, bool TRACK>
+__global__ __launch_bounds__(kStreamBlock) void k_consensus_mixed(ConsensusArgs a, int64_t total, SegTable segs)
+{
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t off = (int64_t)blockIdx.x * SPAN;
+    const int lane_off = threadIdx.x * 16;
+    u32x4 v[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) v[j] = span_load<u32x4>(span_rsrc<SPAN>(a.src[j], off, total), lane_off);
+    __builtin_amdgcn_sched_barrier(0);   // (left alone, the scheduler issues the 8th load behind the first seven's adds)
+    [[maybe_unused]] double n2 = 0.0, sp[U];
+#pragma unroll
+    for (int i = 0; i < U; ++i) sp[i] = 0.0;
+    const int32_t dtype = seg_dtype(segs, off);
+    u32x4 mean;
+    if (dtype == DPWA_F32) mean = cons_item<OpsF32, U, TRACK>(v, a.r, n2, sp);
+    else if (dtype == DPWA_BF16) mean = cons_item<OpsBF16, U, TRACK>(v, a.r, n2, sp);
+    else mean = cons_item<OpsF16, U, TRACK>(v, a.r, n2, sp);
+    if constexpr (STORE) span_store<u32x4>(span_rsrc<SPAN>(a.out, off, total), lane_off, mean);
+    if constexpr (TRACK) cons_commit<U>(a.acc, blockIdx.x, n2, sp);
+}
+
+// Finishing (one workgroup behind the pass on the same stream, as k_distance_finish): lane i loads
+// and zeroes row i, the sums are taken in a fixed order -- the butterfly inside each wave, then the
+// waves in order, then spread2 over the members in order -- and the record is written whole.
+constexpr int kConsensusSums = kMaxConsensus + 1;
+
+__global__ __launch_bounds__(kDistFinishBlock) void k_consensus_finish(double *__restrict__ acc,
+                                                                       dpwa_consensus_record *__restrict__ out, int64_t n,
+                                                                       int32_t members, uint64_t version)
+{
+    __shared__ double s_sum[kConsensusSums][kDistFinishBlock / 64];
+    double *a = acc + (size_t)threadIdx.x * kDistAccStride;
+    double v[kConsensusSums];
+#pragma unroll
+    for (int k = 0; k < kConsensusSums; ++k) v[k] = __hip_atomic_load(a + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int k = 0; k < kConsensusSums; ++k) __hip_atomic_store(a + k, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int k = 0; k < kConsensusSums; ++k) {
+        const double t = wave_sum(v[k]);
+        if ((threadIdx.x & 63) == 0) s_sum[k][threadIdx.x >> 6] = t;
+    }
+    __syncthreads();
+    __shared__ double s_total[kConsensusSums];
+    if (threadIdx.x < kConsensusSums) {   // lane k: sum k over the waves in order
+        double t = s_sum[threadIdx.x][0];
+        for (int w = 1; w < kDistFinishBlock / 64; ++w) t = t + s_sum[threadIdx.x][w];
+        s_total[threadIdx.x] = threadIdx.x <= (unsigned)members ? t : 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double spread2 = s_total[1];
+    out->member_spread2[0] = spread2;
+    for (int i = 1; i < kMaxConsensus; ++i) {
+        out->member_spread2[i] = s_total[1 + i];
+        if (i < members) spread2 = spread2 + s_total[1 + i];
+    }
+    out->norm2 = s_total[0];
+    out->spread2 = spread2;
+    out->n = n;
+    out->members = members;
+    out->reserved = 0;
+    out->version = version;
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(out->pad) / sizeof(out->pad[0])); ++k) out->pad[k] = 0;
+}
+
+// The bytes [p, p + bytes) and [q, q + bytes) share one.
+static bool overlaps(const void *p, const void *q, int64_t bytes)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + (uintptr_t)bytes && b < a + (uintptr_t)bytes;
+}
+
+hipError_t launch_consensus(const Elems &e, const void *const *src, int count, double r, void *out, double *acc,
+                            bool remote, hipStream_t s, const LaunchTiming *timing)
+{
+    if (count < 1 || count > kMaxConsensus || !src || (!out && !acc) || !aligned16(out, acc)) return hipErrorInvalidValue;
+    if (!e.segmented() && (e.n < 0 || !is_float_dtype(e.dtype))) return hipErrorInvalidValue;
+    if (e.segmented() && (!e.layout || layout_problem(*e.layout, -1))) return hipErrorInvalidValue;
+    const int64_t bytes = e.segmented() ? layout_bytes(*e.layout) : e.bytes();
+    ConsensusArgs a{};
+    for (int i = 0; i < count; ++i) {
+        if (absent_or_unaligned(src[i]) || (out && (src[i] == out || overlaps(src[i], out, bytes)))) return hipErrorInvalidValue;
+        a.src[i] = src[i];
+    }
+    a.out = out;
+    a.acc = acc;
+    a.r = r;
+    const bool store = out != nullptr, track = acc != nullptr;
+    const auto acquire = [&] {   // (after every refusal: a refused launch queues nothing)
+        if (remote) hipLaunchKernelGGL(k_acquire_system, dim3(256), dim3(64), 0, s);
+    };
+    return Choice<1, 2, 3, 4, 5, 6, 7, 8>::with(count, [&](auto members) {
+        constexpr int U = decltype(members)::value;
+        if (e.segmented())
+            return with_segments(e, false, [&](int64_t total, dim3 grid, const SegTable &t) {
+                acquire();
+                return launch(store ? (track ? k_consensus_mixed<U, true, true> : k_consensus_mixed<U, true, false>)
+                                    : k_consensus_mixed<U, false, true>,
+                              grid, dim3(kStreamBlock), s, timing, a, total, t);
+            });
+        if (e.n == 0) return hipSuccess;
+        return with_ops(e.dtype, [&](auto ops) {
+            using Ops = decltype(ops);
+            if (span_grid<Ops>(e.n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+            acquire();
+            return launch(store ? (track ? k_consensus<Ops, U, true, true> : k_consensus<Ops, U, true, false>)
+                                : k_consensus<Ops, U, false, true>,
+                          dim3((uint32_t)span_grid<Ops>(e.n, kStreamBlock)), dim3(kStreamBlock), s, timing, a, e.n);
+        });
+    });
+}
+
+hipError_t launch_consensus_finish(double *acc, dpwa_consensus_record *out, int64_t n, int members, uint64_t version,
+                                   hipStream_t s, const LaunchTiming *timing)
+{
+    if (!acc || !out || members < 1 || members > kMaxConsensus || n < 0) return hipErrorInvalidValue;
+    return launch(k_consensus_finish, dim3(1), dim3(kDistFinishBlock), s, timing, acc, out, n, members, version);
+}
+
 }  // namespace dpwa

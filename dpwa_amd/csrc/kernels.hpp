@@ -113,6 +113,21 @@ hipError_t launch_distance(const Elems &e, const void *param, const void *peer, 
 hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
                                   const LaunchTiming *timing = nullptr);
 
+// The consensus of a group (dpwa_consensus, include/dpwa_hip.h; kernels.hip "consensus of a group"):
+// the element-wise mean of `count` (1..kMaxConsensus) payloads src[0..count), summed in that order
+// in fp64 and scaled by `r` (the host's 1.0 / count), stored into `out` (null: measure only), and
+// with `acc` (null: the mean only; kDistanceWorkspaceBytes, zero before the first use, left zero by
+// the finish) the sums norm2 and spread2_i.  `remote`: some source is another GPU's memory -- the
+// launch is preceded by the system-scope acquire of launch_pull.  hipErrorInvalidValue, nothing
+// queued: a count outside 1..8, a null or not 16-B aligned pointer, `out` overlapping a source,
+// neither `out` nor `acc`.  There is no unaligned form.
+//   consensus_finish   sums the rows into *out (members = count of the pass) and zeroes them
+constexpr int kMaxConsensus = 8;
+hipError_t launch_consensus(const Elems &e, const void *const *src, int count, double r, void *out, double *acc,
+                            bool remote, hipStream_t s, const LaunchTiming *timing = nullptr);
+hipError_t launch_consensus_finish(double *acc, dpwa_consensus_record *out, int64_t n, int members, uint64_t version,
+                                   hipStream_t s, const LaunchTiming *timing = nullptr);
+
 // The non-finite peer check (kernels.hip "non-finite peer check"): one read of the peer payload; a
 // lane that finds a NaN or an inf stores `stamp` (non-zero) into *veto (device memory, 4-B aligned).
 // Any element alignment for a single dtype; a segmented payload is 16-B aligned.

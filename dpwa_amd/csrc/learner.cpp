@@ -474,6 +474,10 @@ struct dpwa_learner {
     bool finite_check = false;
     uint32_t finite_stamp = 0;
     HostWord<int32_t> status;           // pinned mirror of coef.status for non-blocking polls
+    // the consensus of a group (dpwa_learner_consensus): its accumulator rows, made and zeroed at the
+    // first call that measures; where its last pass ran, for whoever rewrites a slot it read
+    DevBuf consensus_rows;
+    StreamMark consensus_read;
 };
 
 static char *slot_payload(const dpwa_learner *l, int k)
@@ -710,6 +714,10 @@ static int wait_slot_readers(dpwa_learner *l, int k, hipStream_t s)
         if (r->fetch.consumed_mark().crosses(s)) {
             DeviceGuard rg(r->device);
             HIP_TRY(r->fetch.consumed_mark().order(s));
+        }
+        if (r->consensus_read.crosses(s)) {   // (never noted by a learner that never called dpwa_learner_consensus)
+            DeviceGuard rg(r->device);
+            HIP_TRY(r->consensus_read.order(s));
         }
     }
     l->readers[k].clear();
@@ -2051,6 +2059,92 @@ int dpwa_learner_poll_status(dpwa_learner *l, int *done, int32_t *status)
     volatile int32_t *w = l->status.host();
     *status = *w;
     if (*status != DPWA_STATUS_OK) *w = DPWA_STATUS_OK;
+    return DPWA_OK;
+}
+
+// The consensus of this learner and attached peers over the published slots of `version`
+// (include/dpwa_hip.h).  Read-only: no clock, slot, fetch or record of any learner changes.  What it
+// reads is ordered as a zero-copy fetch's source is: behind a local peer's publish mark (RAW), and
+// registered as a reader of the peer's slot, so that the publish or write-through average that
+// rewrites it orders its stream behind this pass (WAR: the learner's consensus_read mark).
+int dpwa_learner_consensus(dpwa_learner *l, const int32_t *peer_ids, int count, uint64_t version, void *out,
+                           dpwa_consensus_record *record_dev, dpwa_stream_t stream)
+{
+    const char *fn = "dpwa_learner_consensus";
+    if (!l || !peer_ids) return set_error(DPWA_ERR_ARG, "%s: NULL argument", fn);
+    if (count < 1 || count > DPWA_CONSENSUS_MAX)
+        return set_error(DPWA_ERR_ARG, "%s: %d members (1..%d)", fn, count, DPWA_CONSENSUS_MAX);
+    if ((!out && !record_dev) || !aligned16(out) || ((uintptr_t)record_dev & 7))
+        return set_error(DPWA_ERR_ARG, "%s: neither out nor a record, or a misaligned one", fn);
+    if (version == 0) return set_error(DPWA_ERR_STATE, "%s: nothing published", fn);
+    if (int rc = need_layout(l, fn)) return rc;
+    if (l->relay_deferred)
+        return set_error(DPWA_ERR_STATE, "%s: a fused relay phase is pending (no contiguous snapshot exists)", fn);
+    const int k = (int)((version - 1) % 2);
+    const void *src[DPWA_CONSENSUS_MAX];
+    dpwa_learner *owner[DPWA_CONSENSUS_MAX];
+    bool remote = false;
+    for (int i = 0; i < count; ++i) {
+        const int id = peer_ids[i];
+        owner[i] = nullptr;
+        if (id == -1) {
+            owner[i] = l;
+        } else {
+            auto it = l->peers.find(id);
+            if (it == l->peers.end()) return set_error(DPWA_ERR_ARG, "%s: peer %d not attached", fn, id);
+            const Endpoint &ep = it->second;
+            if (ep.kind == 1) {
+                if (!is_live(ep.local)) return set_error(DPWA_ERR_STATE, "%s: peer %d was destroyed", fn, id);
+                if (ep.local->n != l->n || ep.local->dtype != l->dtype || ep.local->layout_digest != l->layout_digest)
+                    return set_error(DPWA_ERR_ARG, "%s: peer %d holds another n, dtype or layout", fn, id);
+                if (ep.device != l->device)
+                    return set_error(DPWA_ERR_ARG, "%s: peer %d is a learner of this process on device %d, not %d", fn, id,
+                                     ep.device, l->device);
+                owner[i] = ep.local;
+            } else {
+                if (ep.n != l->n || ep.dtype != l->dtype)   // (its layout digest was compared when it was attached)
+                    return set_error(DPWA_ERR_ARG, "%s: peer %d holds another n or dtype", fn, id);
+                src[i] = ep.base + (size_t)k * (size_t)ep.slot_stride + kPayloadOff;
+                remote = true;
+            }
+        }
+        if (dpwa_learner *o = owner[i]) {
+            if (o->version != version)
+                return set_error(DPWA_ERR_STATE, "%s: member %d (peer %d) is at version %llu, not %llu", fn, i, id,
+                                 (unsigned long long)o->version, (unsigned long long)version);
+            if (!o->published[k].noted()) return set_error(DPWA_ERR_STATE, "%s: peer %d slot %d never published", fn, id, k);
+            src[i] = slot_payload(o, k);
+        }
+        for (int j = 0; j < i; ++j)
+            if (src[j] == src[i]) return set_error(DPWA_ERR_ARG, "%s: members %d and %d name the same slot", fn, j, i);
+    }
+    const Payload p = payload(l);
+    for (int i = 0; i < count; ++i) {
+        const uintptr_t a = (uintptr_t)src[i], o = (uintptr_t)out;
+        if (out && a < o + l->payload_bytes && o < a + l->payload_bytes)
+            return set_error(DPWA_ERR_ARG, "%s: out overlaps member %d's slot", fn, i);
+    }
+    DeviceGuard dg(l->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (record_dev && !l->consensus_rows.h) {   // the first call that measures; never again
+        HIP_TRY(l->consensus_rows.alloc((size_t)kDistanceWorkspaceBytes));
+        HIP_TRY(hipMemset(l->consensus_rows.h, 0, (size_t)kDistanceWorkspaceBytes));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    for (int i = 0; i < count; ++i) {
+        dpwa_learner *o = owner[i];
+        if (!o) continue;
+        HIP_TRY(o->published[k].order(s));   // RAW
+        std::lock_guard<std::mutex> g(o->readers_mu);
+        auto &rv = o->readers[k];
+        if (std::find(rv.begin(), rv.end(), l) == rv.end()) rv.push_back(l);
+    }
+    double *rows = record_dev ? (double *)l->consensus_rows.h : nullptr;
+    HIP_TRY(launch_consensus(p, src, count, 1.0 / (double)count, out, rows, remote, s));
+    if (record_dev) HIP_TRY(launch_consensus_finish(rows, record_dev, p.elements(), count, version, s));
+    // WAR: whoever rewrites a slot read here finds this learner among the slot's readers and orders its
+    // stream behind this mark (wait_slot_readers), whatever the learner's fetches do to theirs meanwhile.
+    l->consensus_read.note(s);
     return DPWA_OK;
 }
 

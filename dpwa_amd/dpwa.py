@@ -728,6 +728,25 @@ class DpwaConnection:
             return 0
         return int(self._learner.finite_skips())
 
+    def consensus(self, out=None, distance=True, members=None):
+        """The group's consensus model and consensus distance (extension, opt-in, read-only;
+        dpwa_amd/consensus.py): the element-wise mean of the snapshots this node and its peers
+        published in the current round -- the model to evaluate and save -- and how far the members
+        are from it, by one kernel pass over the published slots.  Valid between this connection's
+        update_send of a round and its next update_send.  Returns a :class:`Consensus`.
+
+        Members are this node and every bound peer in YAML node order, each slot once (a self-peer
+        entry is this node); ``members=[names]`` restricts the set; at most 8.  ``out``: a tensor
+        to receive the mean (default: a new one; ``False``: measure only); ``distance=False``: the
+        mean only.  In a LocalGroup every member must be on this learner's device and have
+        published this round (ValueError names the one that has not); in a lock-step DistGroup
+        (pulls 'copy', 'kernel', 'relay') every rank reads the mapped slots behind the round's
+        barrier and gets the same bits.  ValueError: free-running ranks (AsyncDistGroup),
+        ``pull='relay-avg'``, the wire transport, more than 8 members.  The call changes no
+        parameter, slot, clock, scheduler state or distance record."""
+        from .consensus import consensus
+        return consensus(self, out, distance, members)
+
     def synchronize(self):
         """Waits for the device and raises a deferred ZeroDivisionError, if any."""
         if self._learner is not None:

@@ -31,6 +31,8 @@ import torch
 
 from . import _lib
 
+CONSENSUS_PEER_BASE = 1 << 20     # learner peer ids of LocalGroup.consensus_sources (node index added)
+
 
 def _address(node):
     """(host, port) of a YAML node entry as the reference dials it (conn.py:250); localhost
@@ -45,6 +47,7 @@ class LocalGroup:
     follows (worth it when peers live on other GPUs of this process; lock-step semantics are
     unchanged).  zero_copy=False makes same-device fetches copy into staging too."""
     eager_fetch = False
+    consensus_refusal = None     # why conn.consensus() is not available in this group (None: it is)
     _registry = {}
     _lock = threading.Lock()
 
@@ -111,6 +114,55 @@ class LocalGroup:
 
     def on_bind(self, conn):
         pass
+
+    def consensus_sources(self, conn, wanted=None):
+        """The members of ``conn.consensus()``: ``[(node name, learner peer id)]`` for this node (id -1)
+        and every peer entry that reaches a member of this process, in YAML node order, each slot once
+        (an entry at this node's own address is this node).  `wanted`: node names that restrict the
+        set.  Every member must share the learner's device and have published its version: ValueError
+        names the one that does not.  Peers are attached to the learner under ids of their own
+        (CONSENSUS_PEER_BASE + node index), beside the ids the node's fetches use."""
+        learner = conn._learner
+        known = [node["name"] for node in conn.nodes]
+        if wanted is not None:
+            wanted = list(wanted)
+            for w in wanted:
+                if w not in known:
+                    raise ValueError("consensus(members=...): %r is not a node of the config" % (w,))
+        attached = conn.__dict__.setdefault("_consensus_attached", {})
+        seen, out = set(), []
+        for i, name in enumerate(known):
+            if wanted is not None and name not in wanted:
+                continue
+            owner = conn if name == conn.name else self._server(conn.peers[conn._peer_index[name]])
+            if owner is None:
+                if wanted is not None:
+                    raise ValueError("consensus(): member %r is not bound in this process" % name)
+                continue
+            if id(owner) in seen:
+                continue
+            seen.add(id(owner))
+            if owner is conn:
+                out.append((conn.name, -1))
+                continue
+            other = owner._learner
+            if other is None or other.version != learner.version:
+                raise ValueError("consensus(): member %r has published version %d, this node version %d"
+                                 % (owner.name, 0 if other is None else other.version, learner.version))
+            if other.device != learner.device:
+                raise ValueError("consensus(): member %r is on %s, this node on %s (members on several devices of "
+                                 "one process are not supported)" % (owner.name, other.device, learner.device))
+            pid = CONSENSUS_PEER_BASE + i
+            known_as = attached.get(pid)          # the Learner object attached under pid, while it lives
+            if known_as is None or known_as() is not other:
+                try:
+                    _lib.call("dpwa_learner_attach_local", learner.handle, pid, other.handle)
+                except _lib.DpwaError as e:       # another n, dtype or layout
+                    raise ValueError("consensus(): member %r cannot be averaged with this node: %s"
+                                     % (owner.name, e)) from None
+                attached[pid] = weakref.ref(other)
+            out.append((owner.name, pid))
+        return out
 
     def after_publish(self, conn):
         pass
@@ -219,6 +271,7 @@ class DistGroup:
     eager_fetch = True
     zero_copy = False
     relay_capable = True         # lock-step rounds: the relay pulls are available
+    consensus_refusal = None
 
     def __init__(self, nodes, name, process_group=None):
         import torch.distributed as dist
@@ -311,6 +364,26 @@ class DistGroup:
             self._side = torch.cuda.ExternalStream(side.value, device=dev)
             self.relay_ready = True
 
+    def consensus_sources(self, conn, wanted=None):
+        """The members of ``conn.consensus()`` in lock-step rounds: every rank, in YAML node order
+        (rank == node index), through the slots mapped in on_bind (peer k of the learner; this rank
+        -1).  No collective: the round's barrier has ordered every rank's publish of this version,
+        and the read runs on the round's stream, ahead of the barrier in front of the publish that
+        rewrites the slot.  Every rank that calls it with the same members gets the same
+        bits."""
+        known = [node["name"] for node in conn.nodes]
+        if wanted is not None:
+            wanted = list(wanted)
+            for w in wanted:
+                if w not in known:
+                    raise ValueError("consensus(members=...): %r is not a node of the config" % (w,))
+        out = []
+        for i, name in enumerate(known):
+            if wanted is not None and name not in wanted:
+                continue
+            out.append((name, -1 if i == self.rank else conn._peer_node_index.index(i)))
+        return out
+
     def barrier(self, device):
         """Stream-ordered on RCCL (the current stream waits; the host does not)."""
         if self.backend == "nccl":
@@ -392,6 +465,9 @@ class AsyncDistGroup(DistGroup):
         self.board = None
         # a publish waits for a slow reader at most this long (the reference blocks forever)
         self.publish_timeout_ms = int(publish_timeout_ms if publish_timeout_ms is not None else 600_000)
+
+    consensus_refusal = ("consensus() needs lock-step rounds (a LocalGroup, or a DistGroup: gossip 'lockstep'): "
+                         "free-running ranks have no common version to average")
 
     def on_bind(self, conn):
         if getattr(conn, "_pull", "copy").partition(":")[0] in ("relay", "relay-avg") or self.relay_blocks:

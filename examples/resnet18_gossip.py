@@ -83,9 +83,16 @@ def main(argv=None):
                     help="skip (and count) a round whose peer snapshot holds a NaN or an inf, so that one replica that "
                          "overflowed does not spread through the gossip (skip_nonfinite_peer=True); the count is "
                          "printed at the end")
+    ap.add_argument("--consensus", action="store_true",
+                    help="print the group's relative consensus distance every 100 steps and save the consensus model "
+                         "(the mean of the replicas' snapshots, adapter.consensus()) as a state_dict at the end; "
+                         "several ranks need --gossip lockstep")
+    ap.add_argument("--consensus-out", default=None, help="where --consensus saves (default: a temporary directory)")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.consensus and world > 1 and args.gossip != "lockstep":      # (said by every rank, before any starts)
+        ap.error("--consensus with several ranks needs --gossip lockstep: free-running ranks have no common version")
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dev = torch.device("cuda", local % torch.cuda.device_count())
@@ -129,6 +136,10 @@ def main(argv=None):
             if gossip:
                 for i, a in enumerate(adapters):
                     a.update_send(losses[i])       # a device tensor: no host sync
+                if args.consensus and step % 100 == 0 and rank == 0:     # (this read waits for the device)
+                    c = adapters[0].consensus(out=False)
+                    print("step %d, version %d: relative consensus distance of %d replicas %.3g"
+                          % (step, c.version, len(c.members), c.relative), file=sys.stderr)
             if not args.resident:                  # the reference's order (README.md:18-29)
                 for i in range(len(mine)):
                     losses[i] = train_step(i)
@@ -167,6 +178,19 @@ def main(argv=None):
         t = torch.tensor([t_plain, t_gossip], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         t_plain, t_gossip = t.tolist()
+    if args.consensus:                  # one more publish, so that every replica's final parameters are a snapshot
+        for i, a in enumerate(adapters):
+            a.update_send(2.3)
+        if rank == 0:
+            c = adapters[0].consensus()
+            state = {k: v.detach().clone() for k, v in nets[0].state_dict().items()}     # buffers: replica 0's
+            state.update({k: v.clone() for k, v in c.parameters().items()})
+            path = args.consensus_out or os.path.join(tempfile.mkdtemp(), "resnet18_consensus.pt")
+            torch.save(state, path)
+            print("consensus of %s: distance %.3g, relative %.3g, saved to %s"
+                  % (", ".join(c.members), c.distance, c.relative, path), file=sys.stderr)
+        for i, a in enumerate(adapters):    # the round's end: the fetch the publish started is waited for
+            a.update_wait(2.3)
     if rank == 0:
         print(json.dumps({
             "model": "ResNet-18 (CIFAR, 11,173,962 params), synthetic batch %d" % args.batch_size,
@@ -179,6 +203,10 @@ def main(argv=None):
             "final_clock": adapters[0].connection.clock,
             "nonfinite_skips": [a.nonfinite_skips for a in adapters] if args.skip_nonfinite else None,
         }))
+    if world > 1:       # no rank frees its slots while another may still be reading them (the consensus pass, a pull)
+        import torch.distributed as dist
+        torch.cuda.synchronize()
+        dist.barrier()
     for a in adapters:
         a.connection.close()
 

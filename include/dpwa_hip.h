@@ -41,7 +41,9 @@ extern "C" {
  * Still 11, by additions only: skipping a round whose peer snapshot is not finite
  * (DPWA_STATUS_PEER_NONFINITE, a new value of dpwa_coef.status) -- dpwa_check_finite,
  * dpwa_check_finite_mixed, dpwa_learner_set_finite_check, dpwa_learner_finite_skips,
- * dpwa_node_set_finite_check. */
+ * dpwa_node_set_finite_check.
+ * Still 11, by additions only: the consensus of a group (dpwa_consensus_record) --
+ * dpwa_consensus_workspace, dpwa_consensus, dpwa_consensus_mixed, dpwa_learner_consensus. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -265,6 +267,47 @@ int dpwa_check_finite(int32_t dtype, const void *peer_payload, int64_t n, uint32
                       dpwa_stream_t stream, void *start_event, void *stop_event);
 int dpwa_check_finite_mixed(const dpwa_layout *layout, const void *peer_payload, uint32_t *veto_dev, uint32_t stamp,
                             dpwa_stream_t stream, void *start_event, void *stop_event);
+
+/* The consensus of a group (extension, opt-in, read-only; no reference interface): the element-wise
+ * mean of `count` (1..DPWA_CONSENSUS_MAX) payloads of one dtype and n -- the model a gossip run
+ * evaluates and saves -- and the group's consensus distance, in ONE pass that reads every payload once
+ * ((count + 1) * n * s bytes with the store, no temporaries).  For every element j, the members in the
+ * order given:
+ *   s = ((x_0[j] + x_1[j]) + ...) + x_{count-1}[j]   each operand widened exactly to fp64, fp64 adds
+ *   m = s * r                                        r = the fp64 1.0 / count, formed once on the host
+ *   out[j] = f32(m), round to nearest even, subnormals kept; a bf16 / fp16 payload then rounds that fp32
+ *            value to nearest even once more (two roundings, as documented, not one from fp64)
+ *   norm2 = sum m^2      member_spread2[i] = sum (x_i[j] - m)^2      spread2 = sum_i member_spread2[i]
+ * all in fp64 against the fp64 m (not the stored mean).  The consensus distance is sqrt(spread2 / count).
+ * The means are bit-exact; the sums are added across workgroups as dpwa_distance's are, so they are
+ * reproducible to the same summation bound and not bit-exact from run to run.
+ *   out NULL                        measure only: nothing is stored to any payload
+ *   workspace and record_dev NULL   the mean only (both or neither)
+ * workspace: dpwa_consensus_workspace() bytes (= dpwa_distance_workspace()), 16-B aligned, zero before the
+ * first use, left zero by every call.  record_dev: 8-B aligned device memory, written whole.  `version`
+ * in the record is 0 from the stateless entries.  Payloads and out are 16-B aligned (there is no unaligned
+ * form); out may not overlap a payload.  dpwa_consensus_mixed: a DPWA_MIXED payload (`layout` in place of
+ * dtype and n; every segment with its own type's rounding; padding bytes are zeros in every member, their
+ * mean is zero and they add 0; record n = the element slots of the segments).  Events as dpwa_average
+ * (they time the pass, not the finishing step).  DPWA_ERR_ARG, nothing queued: a count outside
+ * 1..DPWA_CONSENSUS_MAX, a NULL or misaligned pointer, out overlapping a payload, n < 0, an unknown dtype,
+ * an invalid layout, neither out nor a record, a workspace without a record or the reverse. */
+#define DPWA_CONSENSUS_MAX 8
+typedef struct dpwa_consensus_record {
+    double norm2;
+    double spread2;
+    double member_spread2[DPWA_CONSENSUS_MAX];   /* in the order of the payloads; 0 beyond `members` */
+    int64_t n;
+    int32_t members;
+    int32_t reserved;
+    uint64_t version;
+    uint64_t pad[3];
+} dpwa_consensus_record;
+int dpwa_consensus_workspace(int64_t *bytes);
+int dpwa_consensus(int32_t dtype, const void *const *payloads, int count, int64_t n, void *out, void *workspace,
+                   dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
+int dpwa_consensus_mixed(const dpwa_layout *layout, const void *const *payloads, int count, void *out, void *workspace,
+                         dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
 
 /* The per-parameter distance (extension, opt-in): the two sums above for every parameter tensor t of
  * the model, over that tensor's own elements only -- dist2_t = sum (double(q_i) - double(p_i))^2 and
@@ -556,6 +599,27 @@ int dpwa_learner_param_distance_rounds(dpwa_learner *l, int64_t *averaged, int64
  * second phase is pending.  dpwa_node_set_finite_check: the same on a bound node's learner. */
 int dpwa_learner_set_finite_check(dpwa_learner *l, int on);
 int dpwa_learner_finite_skips(dpwa_learner *l, uint64_t *count);
+/* The consensus of a group of learners (dpwa_consensus above) over the published snapshots of publish
+ * number `version`: the slot (version - 1) % 2 of `l` and of the named attached peers, in the order
+ * given; peer_id -1 stands for `l` itself.  Peers may be local learners of l's device or IPC / fd-mapped
+ * ones.  out (NULL: measure only): the mean, device memory of the payload's bytes, 16-B aligned, no slot.
+ * record_dev (NULL: the mean only): written whole, with `version`.  The accumulator rows belong to the
+ * learner: allocated and zeroed by the first call that measures, never inside a later one.  Read-only: no
+ * parameter, slot, clock, fetch or distance record of any learner changes, and a learner that never calls
+ * it launches what it launched before.
+ * Ordering: the launch follows the local members' publishes through their publish marks, and this learner
+ * is registered as a reader of their slots exactly as a zero-copy fetch registers it, so the publish or
+ * write-through average that rewrites a slot waits for the read.  Mapped members are not ordered here: in
+ * a lock-step group the round's barrier has ordered every rank's publish `version`, and a launch on the
+ * round's stream precedes the barrier in front of any rank's publish version + 2, which is what rewrites
+ * the slot; the pass is preceded by a system-scope acquire.
+ * DPWA_ERR_ARG: a count outside 1..DPWA_CONSENSUS_MAX, an unknown peer, a peer whose n, dtype or layout
+ * digest differs, a local peer on another device, the same slot named twice (a self-peer and -1), neither
+ * out nor a record, out misaligned or overlapping a member's slot.  DPWA_ERR_STATE: `l` or a local peer
+ * whose current version is not `version`, version 0, a DPWA_MIXED learner without its layout, a learner
+ * with a fused relay phase pending (no contiguous snapshot exists). */
+int dpwa_learner_consensus(dpwa_learner *l, const int32_t *peer_ids, int count, uint64_t version, void *out,
+                           dpwa_consensus_record *record_dev, dpwa_stream_t stream);
 
 /* always != 0: a write-through average never writes the next publish's header ahead; that
  * publish then writes it with the loss given to it (a snapshot served over the wire bridge
