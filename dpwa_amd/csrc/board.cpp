@@ -8,10 +8,11 @@
 // without any collective on the data path:
 //
 //   * one POSIX shared-memory block per node set (all ranks of a node), mapped by every
-//     rank and registered with HIP so a stream can write into it;
-//   * version[p]   -- the newest *complete* snapshot of publisher p.  Written by p's stream
-//                     (a one-wave release-store kernel) after the publish kernel and its
-//                     system-scope release, so a reader never sees a version before its bytes;
+//     rank; a stream writes into it through a host function enqueued on it (the block is
+//     plain shared memory: nothing of it is pinned or mapped for the device);
+//   * version[p]   -- the newest *complete* snapshot of publisher p.  Stored by a host function
+//                     on p's stream, which runs once the publish kernel and its system-scope
+//                     release are complete, so a reader never sees a version before its bytes;
 //   * reading[p][r] -- the version of p that reader r is pulling (0 = none).  Set by r's
 //                     host before the pull is enqueued, cleared by r's side stream after
 //                     the pull has landed;
@@ -36,6 +37,7 @@
 // release of the acquisition that set them.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -51,7 +53,6 @@
 #include <vector>
 
 #include "common.hpp"
-#include "kernels.hpp"
 
 using namespace dpwa;
 
@@ -100,16 +101,11 @@ struct dpwa_board {
     BoardHead *head = nullptr;
     NodeRec *nodes = nullptr;
     uint64_t *reading = nullptr;   // [publisher * world + reader]
-    char *dev_base = nullptr;      // device alias of `base` once registered
-    int device = -1;
+    int device = -1;               // whose streams store into the block (dpwa_board_register)
+    std::atomic<int> queued{0};    // stream-ordered stores enqueued and not yet run
     // per publisher: the event recorded after our last stream-ordered release of its mark
     std::vector<hipEvent_t> released;
     std::vector<char> release_pending;
-
-    uint64_t *dev(const void *host_ptr) const
-    {
-        return (uint64_t *)(dev_base + ((const char *)host_ptr - base));
-    }
 
     bool alive(int r) const
     {
@@ -120,16 +116,46 @@ struct dpwa_board {
     }
 };
 
-// Stream-ordered store into the board: a one-wave kernel (a release store at system scope)
-// by default; DPWA_BOARD_WRITE=value uses hipStreamWriteValue64 instead (comparison).
-static hipError_t stream_store(uint64_t *dev_ptr, uint64_t v, hipStream_t s)
+// Stream-ordered store into the board: a host function on the stream, run by the runtime once
+// everything enqueued before it is complete (its writes visible to every device and the host).
+namespace {
+
+struct QueuedStore {
+    uint64_t *word;
+    uint64_t value;
+    std::atomic<int> *queued;
+};
+
+void run_store(void *arg)
 {
-    static const bool write_value = [] {
-        const char *e = getenv("DPWA_BOARD_WRITE");
-        return e && std::string(e) == "value";
-    }();
-    if (write_value) return hipStreamWriteValue64(s, dev_ptr, v, 0);
-    return launch_store_u64(dev_ptr, v, s);
+    QueuedStore *q = (QueuedStore *)arg;
+    store(q->word, q->value);
+    q->queued->fetch_sub(1, std::memory_order_release);
+    delete q;
+}
+
+}  // namespace
+
+// Not under stream capture: a captured host function would free its QueuedStore at the first
+// replay and store a stale value at every later one.
+static hipError_t stream_store(dpwa_board *b, uint64_t *word, uint64_t v, hipStream_t s)
+{
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(s, &capture);
+    if (e != hipSuccess) return e;
+    if (capture != hipStreamCaptureStatusNone) return hipErrorStreamCaptureUnsupported;
+    QueuedStore *q = new (std::nothrow) QueuedStore{word, v, &b->queued};
+    if (!q) return hipErrorOutOfMemory;
+    // relaxed: the only reader of a non-zero count, dpwa_board_close, runs on a thread that
+    // enqueues (a board has one owner), so it sees this add in program order; the callback's
+    // release pairs with close's acquire
+    b->queued.fetch_add(1, std::memory_order_relaxed);
+    e = hipLaunchHostFunc(s, run_store, q);
+    if (e != hipSuccess) {
+        b->queued.fetch_sub(1, std::memory_order_relaxed);
+        delete q;
+    }
+    return e;
 }
 
 extern "C" {
@@ -205,7 +231,7 @@ int dpwa_board_close(dpwa_board *b)
                std::chrono::steady_clock::now() - t0 < std::chrono::seconds(10))
             std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
-    if (b->dev_base) {
+    if (b->device >= 0) {
         int prev = 0;
         (void)hipGetDevice(&prev);
         (void)hipSetDevice(b->device);
@@ -214,8 +240,17 @@ int dpwa_board_close(dpwa_board *b)
                 (void)hipEventSynchronize(ev);
                 (void)hipEventDestroy(ev);
             }
-        (void)hipHostUnregister(b->base);
         (void)hipSetDevice(prev);
+    }
+    // Stores still queued on a stream write into the block: they land first, within 10 s of their
+    // own.  A stream that never gets there keeps the block and the board (leaked, not unmapped
+    // under a store), and the caller is told.
+    const auto q0 = std::chrono::steady_clock::now();
+    while (b->queued.load(std::memory_order_acquire) != 0) {
+        if (std::chrono::steady_clock::now() - q0 > std::chrono::seconds(10))
+            return set_error(DPWA_ERR_STATE, "dpwa_board_close: %d stream-ordered stores never ran; the board stays mapped",
+                             b->queued.load(std::memory_order_acquire));
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
     munmap(b->base, b->bytes);
     delete b;
@@ -225,16 +260,10 @@ int dpwa_board_close(dpwa_board *b)
 int dpwa_board_register(dpwa_board *b, int device)
 {
     if (!b) return set_error(DPWA_ERR_ARG, "dpwa_board_register: NULL board");
-    if (b->dev_base) return DPWA_OK;
-    int prev = 0;
-    HIP_TRY(hipGetDevice(&prev));
-    HIP_TRY(hipSetDevice(device));
-    hipError_t e = hipHostRegister(b->base, b->bytes, hipHostRegisterMapped);
-    void *d = nullptr;
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&d, b->base, 0);
-    (void)hipSetDevice(prev);
-    if (e != hipSuccess) return set_error(DPWA_ERR_HIP, "dpwa_board_register: %s", hipGetErrorString(e));
-    b->dev_base = (char *)d;
+    if (b->device >= 0) return DPWA_OK;
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return set_error(DPWA_ERR_ARG, "dpwa_board_register: no device %d", device);
     b->device = device;
     b->released.assign((size_t)b->world, nullptr);
     b->release_pending.assign((size_t)b->world, 0);
@@ -309,8 +338,8 @@ int dpwa_board_release(dpwa_board *b, int r, dpwa_stream_t stream, int host)
         store(mark, (uint64_t)0);
         return DPWA_OK;
     }
-    if (!b->dev_base) return set_error(DPWA_ERR_STATE, "dpwa_board_release: board not registered with a device");
-    HIP_TRY(stream_store(b->dev(mark), 0, (hipStream_t)stream));
+    if (b->device < 0) return set_error(DPWA_ERR_STATE, "dpwa_board_release: board not registered with a device");
+    HIP_TRY(stream_store(b, mark, 0, (hipStream_t)stream));
     if (!b->released[r]) {
         int prev = 0;
         HIP_TRY(hipGetDevice(&prev));
@@ -373,8 +402,8 @@ int dpwa_board_advertise(dpwa_board *b, uint64_t version, dpwa_stream_t stream, 
         store(v, version);
         return DPWA_OK;
     }
-    if (!b->dev_base) return set_error(DPWA_ERR_STATE, "dpwa_board_advertise: board not registered with a device");
-    HIP_TRY(stream_store(b->dev(v), version, (hipStream_t)stream));
+    if (b->device < 0) return set_error(DPWA_ERR_STATE, "dpwa_board_advertise: board not registered with a device");
+    HIP_TRY(stream_store(b, v, version, (hipStream_t)stream));
     return DPWA_OK;
 }
 

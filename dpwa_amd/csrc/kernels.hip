@@ -2281,20 +2281,6 @@ hipError_t launch_stream_mix(const StreamMixArgs &a, hipStream_t s, const Launch
     });
 }
 
-// One 64-bit word into (host-mapped) memory after everything before it on the stream: a
-// system-scope release store, so the bytes written before it are visible first.  Used by
-// the gossip board (board.cpp) for versions and read marks.
-__global__ void k_store_u64(uint64_t *p, uint64_t v)
-{
-    if (threadIdx.x == 0) __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-hipError_t launch_store_u64(uint64_t *p, uint64_t v, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_store_u64, dim3(1), dim3(64), 0, s, p, v);
-    return hipGetLastError();
-}
-
 // ---------------------------------------------------------------- consensus of a group
 // Opt-in and read-only (include/dpwa_hip.h dpwa_consensus): the element-wise mean of U = 1..8 published
 // snapshots and how far the members are from it, in one pass that reads every source once.  For

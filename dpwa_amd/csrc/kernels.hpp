@@ -257,9 +257,6 @@ hipError_t launch_window_roll(const char *old, const char *cur, int64_t nbytes, 
 // bytes were written by an earlier kernel, read by other devices).
 hipError_t launch_release_system(hipStream_t s);
 
-// A system-scope release store of one 64-bit word after the work already on `s`.
-hipError_t launch_store_u64(uint64_t *p, uint64_t v, hipStream_t s);
-
 // What the stateless entry points (learner.cpp, distance.cpp) share; `fn` names the entry in messages.
 // The caller's begin/end events as a launch's timing argument: NULL when none were given.
 struct CallerTiming {

@@ -944,10 +944,12 @@ int dpwa_node_info(const dpwa_node *n, int *fetching, int *fetch_peer, uint64_t 
 /* name: "/..." (shm_open); create != 0 on exactly one rank, before the others open. */
 int dpwa_board_open(dpwa_board **out, const char *name, int world, int rank, int create);
 int dpwa_board_unlink(const char *name);
-/* marks this rank closed (peers see a refused connection) and unmaps */
+/* marks this rank closed (peers see a refused connection) and unmaps; DPWA_ERR_STATE, the
+ * board left mapped, if stream-ordered stores are still queued after 10 s */
 int dpwa_board_close(dpwa_board *b);
-/* hipHostRegister the block for stream writes from `device` (needed before a device
- * advertise/release) */
+/* names the device whose streams advertise and release (needed before a stream-ordered
+ * advertise/release: those are host functions enqueued on the stream, so the block itself
+ * needs no registration with HIP) */
 int dpwa_board_register(dpwa_board *b, int device);
 /* DPWA_PEER_DOWN / NO_STATE / READY for rank r */
 int dpwa_board_status(dpwa_board *b, int r, int32_t *status);
@@ -955,7 +957,8 @@ int dpwa_board_status(dpwa_board *b, int r, int32_t *status);
 int dpwa_board_read(dpwa_board *b, int r, uint64_t *version, uint64_t *reading_by_me, int32_t *alive);
 /* reader: a version of r that r will not overwrite until released (0 = never published) */
 int dpwa_board_acquire(dpwa_board *b, int r, uint64_t *version);
-/* reader: clear the read mark on r after the work on `stream` (host != 0: now) */
+/* reader: clear the read mark on r after the work on `stream` (host != 0: now).  Like
+ * dpwa_board_advertise, DPWA_ERR_HIP on a stream that is being captured into a graph. */
 int dpwa_board_release(dpwa_board *b, int r, dpwa_stream_t stream, int host);
 /* publisher: wait until publish `next` may rewrite its slot (timeout_ms < 0: forever) */
 int dpwa_board_publish_wait(dpwa_board *b, uint64_t next, int timeout_ms);

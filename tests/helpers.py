@@ -1,6 +1,9 @@
 """Shared helpers for the test-suite (fixture loading, outcome replay)."""
+import functools
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 
@@ -24,6 +27,28 @@ def num(x):
 
 def hexf(s):
     return float.fromhex(s)
+
+
+# ---- fd-shared (hipMemCreate) snapshot slots: does this machine import them? ---------------------
+@functools.lru_cache(maxsize=None)
+def fd_sharing_refusal():
+    """None where an exported hipMemCreate chunk can be imported again (what slots of 1.5 GiB and more, or
+    any with DPWA_VMM=1, are shared by), else the runtime's refusal.  Asked once per session of two processes
+    of their own (tests/fd_probe.py: an exporter and an importer), so that a refusal leaves no HIP error
+    behind in this one.  Anything but that refusal counts as support: the tests then run and say more."""
+    probe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fd_probe.py")
+    p = subprocess.run([sys.executable, probe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       timeout=120)
+    return (p.stdout.strip().splitlines() or ["no message"])[-1] if p.returncode == 3 else None
+
+
+def need_fd_sharing():
+    """First line of a test whose subject is fd-shared slots (or slots too large for a hipIpc handle)."""
+    refusal = fd_sharing_refusal()
+    if refusal is not None:
+        import pytest
+        pytest.skip("hipMemImportFromShareableHandle is not supported here, so device memory cannot be shared "
+                    "as fds (%s)" % refusal)
 
 
 class AttemptReplay:

@@ -29,8 +29,6 @@ int set_error(int code, const char *fmt, ...)
     std::fputc('\n', stderr);
     return code;
 }
-// stream-ordered board stores are device work; this test only uses the host forms
-hipError_t launch_store_u64(uint64_t *, uint64_t, hipStream_t) { return hipErrorInvalidValue; }
 }  // namespace dpwa
 
 #define CHECK(c)                                                                    \

@@ -14,6 +14,7 @@ import torch.multiprocessing as mp
 
 from oracle.async_check import AsyncRuns
 from tests import dist_worker
+from tests import helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -142,5 +143,6 @@ def test_async_write_through_bf16(tmp_path):
 
 def test_async_write_through_vmm_shared_slots(tmp_path, monkeypatch):
     """The free-running board over fd-shared (hipMemCreate) snapshot slots, DPWA_VMM=1."""
+    helpers.need_fd_sharing()
     monkeypatch.setenv("DPWA_VMM", "1")
     test_async_write_through_snapshots(tmp_path, 3, "copy", "clock")

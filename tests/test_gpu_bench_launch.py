@@ -10,6 +10,8 @@ import sys
 
 import pytest
 
+from tests import helpers
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +62,7 @@ def _bench(tmp_path, extra_env=None, args=ARGS):
 
 
 def test_self_launched_two_ranks_print_one_line(tmp_path):
+    helpers.need_fd_sharing()            # every parity transport true: the fd-shared (+vmm) ones among them
     rc, lines, err = _bench(tmp_path)
     assert rc == 0, err[-3000:]
     out = _line(lines)
@@ -111,6 +114,7 @@ def test_two_ranks_report_scaling_basis_and_a_shared_device_xgmi_line(tmp_path):
 
 def test_injected_transport_failure_is_isolated(tmp_path):
     # the timed rounds run write-through learners (the default publish form): their transport fails
+    helpers.need_fd_sharing()            # the injected failure is the only one: the +vmm transports pass
     rc, lines, err = _bench(tmp_path, {"DPWA_BENCH_INJECT": "lockstep/kernel:256@1:end"})
     assert rc == 0, err[-3000:]          # the timed transport passed: the verified line stands
     assert "parity check FAILED for ['lockstep/kernel:256']" in err

@@ -34,8 +34,8 @@ Which case runs which kernel beyond 2^32 bytes:
   k_window_roll                         test_window_guard
   k_relay_phase1, k_relay_phase2        test_relay (form "gather"; world 2, one process per rank)
   k_lerp_relay (StripeSrc)              test_relay (form "fused")
-Left out: k_factor, k_publish_header, k_store_u64 and the fence kernels (k_acquire_system,
-k_release_system) touch no payload; k_stream_mix is the benchmark's.  k_lerp_batch runs beyond 2^32
+Left out: k_factor, k_publish_header and the fence kernels (k_acquire_system, k_release_system)
+touch no payload; k_stream_mix is the benchmark's.  k_lerp_batch runs beyond 2^32
 bytes in tests/test_gpu_batch.py::test_average_many_beyond_4gib_offsets only.
 
 Wall time on one MI355X, same run and machine: tests/test_gpu_batch.py::
@@ -704,8 +704,9 @@ def test_relay():
     its own, the second stripe crosses byte 2^32."""
     if BROKEN:
         pytest.fail("not run: an earlier test of this module met a HIP error (%s)" % BROKEN[0])
-    from tests import relay_worker
+    from tests import helpers, relay_worker
     from tests.test_gpu_relay import first_failure, run_world
+    helpers.need_fd_sharing()          # slots beyond 2^32 bytes are too large for a hipIpc handle
     torch.cuda.empty_cache()
     reports = run_world(ref.RELAY_WORLD, target=relay_worker.big_rank_main, only=ref.RELAY_FORMS)
     assert first_failure(reports) is None, first_failure(reports)

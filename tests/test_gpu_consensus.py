@@ -27,6 +27,7 @@ from tests import consensus_ref as ref
 from tests import consensus_worker as worker
 from tests import dist_ref as dr
 from tests import dist_worker
+from tests import helpers
 from tests.test_gpu_group_dtypes import free_port, run_job
 from tests.test_gpu_kernels import ptr, stream
 from tests.test_gpu_self_peer import write_self_cfg
@@ -448,6 +449,7 @@ def test_every_ranks_consensus_is_the_model_at_every_round(tmp_path, monkeypatch
     bit-identical to the model over that round's snapshots (so to every other rank's), its sums within
     the bound; `vmm`: fd-shared slots."""
     if vmm:
+        helpers.need_fd_sharing()
         monkeypatch.setenv("DPWA_VMM", "1")
     names = ["w%d" % (g + 1) for g in range(world)]
     cfg = str(tmp_path / "dist.yaml")

@@ -25,6 +25,7 @@ from oracle.async_check import AsyncRuns
 from tests import dist_worker
 from tests import group_dtypes_worker as worker
 from tests import group_ref as ref
+from tests import helpers
 from tests import relay_worker
 
 pytestmark = pytest.mark.gpu
@@ -126,6 +127,7 @@ def test_resident_matches_simulate(tmp_path, kind):
 
 def test_mixed_over_fd_shared_slots(tmp_path, monkeypatch):
     """DPWA_VMM=1: the slots and relay buffers of a segmented payload shared as fds; copy and relay:8."""
+    helpers.need_fd_sharing()
     monkeypatch.setenv("DPWA_VMM", "1")
     lockstep(tmp_path, "vmm", "mixed", 3)
 
@@ -170,6 +172,7 @@ def test_unlike_learners_refuse_each_others_handle(monkeypatch, how):
     of equal layouts attaches, fetches and averages to mixed_ref.lerp.  Once over hipIpc handles, once
     (fresh processes: the variable is read at allocation) over fd-shared slots."""
     if how == "fds":
+        helpers.need_fd_sharing()
         monkeypatch.setenv("DPWA_VMM", "1")
     reports = run_job("refusals-%s" % how, 2, worker.refusals_main, how == "fds")
     assert reports == {0: ("ok", 3), 1: ("ok", 3)}, reports

@@ -13,6 +13,7 @@ import torch.multiprocessing as mp
 from oracle import gossip as ogossip
 from oracle import lerp as olerp
 from tests import dist_worker
+from tests import helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -128,6 +129,7 @@ def test_ipc_gossip_configs3_4_full_size(tmp_path, n, interp, fp, thr, pull):
     multi-process path: two ranks over IPC-mapped slots (byte offsets beyond 2^32), split and
     fused write-through rounds; sampled windows of every round's parameters (head, middle,
     ragged tail) bit-exact against the oracle replaying those windows, clocks and peers exact."""
+    helpers.need_fd_sharing()          # slots of this size are too large for a hipIpc handle
     world, T = 2, 4
     names = ["r%d" % i for i in range(world)]
     cfg = str(tmp_path / "big.yaml")
@@ -218,5 +220,6 @@ def test_ipc_gossip_vmm_shared_slots(tmp_path, monkeypatch, world, interp, fp, t
     """DPWA_VMM=1: the snapshot slots (and relay buffers) are hipMemCreate chunks shared as fds
     over a Unix socket -- the form every allocation of 1.5 GiB and more takes, since
     hipIpcOpenMemHandle does not return above ~2 GiB -- at a small size, against the oracle."""
+    helpers.need_fd_sharing()
     monkeypatch.setenv("DPWA_VMM", "1")
     test_ipc_gossip_matches_oracle(tmp_path, world, interp, fp, thr, pull, n=100_003)
