@@ -120,11 +120,22 @@ struct Pull {
     size_t bytes;
     int mode, blocks;
     bool cross_device;
+    // DPWA_PULL_PACKED (`unpack` set): the peer's packed image of that slot crosses the link in place of the
+    // payload and is expanded on arrival -- `n` elements of `dtype` behind the header, which comes from
+    // `from`.  The learner hands the launch over (launch_pull_unpack): nothing here names a kernel of its own.
+    const char *image = nullptr;
+    int32_t dtype = 0;
+    int64_t n = 0;
+    hipError_t (*unpack)(int32_t dtype, void *payload_out, int64_t n, const void *image, void *header_out,
+                         const void *header, int max_blocks, bool remote, hipStream_t s,
+                         const LaunchTiming *timing) = nullptr;
     // on `stream`, between the events of the fetch-timing pair `ft` when there is one
     int into(char *dst, hipStream_t stream, const LaunchTiming *ft = nullptr) const
     {
         if (ft) HIP_TRY(hipEventRecord(ft->start, stream));
-        if (mode == DPWA_PULL_KERNEL)
+        if (unpack)
+            HIP_TRY(unpack(dtype, dst + DPWA_SLOT_PAYLOAD_OFFSET, n, image, dst, from, blocks, cross_device, stream, nullptr));
+        else if (mode == DPWA_PULL_KERNEL)
             HIP_TRY(launch_pull(dst, from, (int64_t)bytes, blocks, cross_device, stream));
         else
             HIP_TRY(hipMemcpyAsync(dst, from, bytes, hipMemcpyDefault, stream));

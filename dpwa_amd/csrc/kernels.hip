@@ -2544,4 +2544,249 @@ hipError_t launch_consensus_finish(double *acc, dpwa_consensus_record *out, int6
     return launch(k_consensus_finish, dim3(1), dim3(kDistFinishBlock), s, timing, acc, out, n, members, version);
 }
 
+// ---------------------------------------------------------------- packed snapshots
+// Opt-in (include/dpwa_hip.h "packed snapshots", where the codec is fixed to the bit): the publisher
+// keeps an int8 block-scaled image of each snapshot (k_pack), and a puller reads that image instead
+// of the payload and expands it on arrival (k_pull_unpack), so 68 B (fp32) or 132 B (bf16 / fp16)
+// cross the link for every 256 B of payload.
+//
+// How the work is split, both ways: one wave owns one 4-KiB payload block and lane l owns its bytes
+// [64 l, 64 l + 64) -- four 16-byte items -- so the q bytes of a lane are contiguous (16 for fp32, 32
+// for the 16-bit types) and a 256-byte group is exactly the four lanes of a quad.  What a group shares
+// (amax and the non-finite flag on the way in, the scale on the way out) therefore never leaves the
+// quad: two DPP quad_perm moves, no LDS memory and no ds_bpermute.  The payload side goes through
+// buffer descriptors ranged to the payload's whole 16-byte items, as every streaming kernel's: lanes
+// past the end load zeros and their stores are dropped, so slots need not be zero behind the payload.
+// The image side needs no range: both planes are padded to whole blocks.  The ragged item of a payload
+// that is no multiple of 16 bytes is read and written 2 bytes at a time by the one lane that owns it.
+// Both kernels keep one fp32 multiply per lane and element: no packed fp32 instructions (device pass only;
+// the host pass knows no such target feature).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DPWA_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DPWA_NO_PK_F32
+#endif
+constexpr int kPackBlock = 4096;        // payload bytes per wave
+constexpr int kPackLane = 64;           // payload bytes per lane
+constexpr int kPackScales = kPackBlock / 256;   // groups, and scales, per block
+static_assert(kPackBlock == kStreamBlock * kPackLane && kPackLane == 4 * 16, "a lane owns four 16-byte items");
+
+// Bit casts as builtins: the two kernels carry a target attribute, and a helper of another feature set (the
+// HIP headers' __float_as_uint, bf_lo above) is not inlined into them but called.
+__device__ __forceinline__ uint32_t pk_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+__device__ __forceinline__ float pk_float(uint32_t w) { return __builtin_bit_cast(float, w); }
+
+// One 16-byte item widened exactly to fp32, elements in payload order, and fp32 values rounded back to one.
+__device__ __forceinline__ void pack_widen(OpsF32, u32x4 v, float *x)
+{
+    x[0] = pk_float(v.x), x[1] = pk_float(v.y), x[2] = pk_float(v.z), x[3] = pk_float(v.w);
+}
+__device__ __forceinline__ void pack_widen(OpsBF16, u32x4 v, float *x)
+{
+    x[0] = pk_float(v.x << 16), x[1] = pk_float(v.x & 0xffff0000u), x[2] = pk_float(v.y << 16);
+    x[3] = pk_float(v.y & 0xffff0000u), x[4] = pk_float(v.z << 16), x[5] = pk_float(v.z & 0xffff0000u);
+    x[6] = pk_float(v.w << 16), x[7] = pk_float(v.w & 0xffff0000u);
+}
+__device__ __forceinline__ void pack_widen(OpsF16, u32x4 v, float *x)
+{
+    const float2v a = unpk_f16(v.x), b = unpk_f16(v.y), c = unpk_f16(v.z), d = unpk_f16(v.w);
+    x[0] = a.x, x[1] = a.y, x[2] = b.x, x[3] = b.y, x[4] = c.x, x[5] = c.y, x[6] = d.x, x[7] = d.y;
+}
+__device__ __forceinline__ u32x4 pack_narrow(OpsF32, const float *x)
+{
+    return u32x4{pk_bits(x[0]), pk_bits(x[1]), pk_bits(x[2]), pk_bits(x[3])};
+}
+__device__ __forceinline__ u32x4 pack_narrow(OpsBF16, const float *x)
+{
+    return u32x4{pk_bf16(x[0], x[1]), pk_bf16(x[2], x[3]), pk_bf16(x[4], x[5]), pk_bf16(x[6], x[7])};
+}
+__device__ __forceinline__ u32x4 pack_narrow(OpsF16, const float *x)
+{
+    return u32x4{pk_f16(x[0], x[1]), pk_f16(x[2], x[3]), pk_f16(x[4], x[5]), pk_f16(x[6], x[7])};
+}
+
+// The unsigned maximum over the four lanes of a quad, the same in all four: lane ^ 1 then lane ^ 2,
+// quad_perm [1,0,3,2] and [2,3,0,1].  Every lane of the wave is active where this is called.
+__device__ __forceinline__ uint32_t quad_umax(uint32_t v)
+{
+    uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
+    v = v > o ? v : o;
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
+    return v > o ? v : o;
+}
+
+// Where the ragged item of a payload lies for the wave of block `off`: the lane and the item of that lane
+// (ragged_at), or lane -1 when the block has none.  Uniform.
+struct Ragged {
+    int lane, item, bytes;
+};
+__device__ __forceinline__ Ragged ragged_at(int64_t off, int64_t nbytes)
+{
+    const int64_t at = (nbytes & ~(int64_t)15) - off;
+    const int rem = (int)(nbytes & 15);
+    if (!rem || at < 0 || at >= kPackBlock) return Ragged{-1, 0, 0};
+    return Ragged{(int)at / kPackLane, ((int)at % kPackLane) / 16, rem};
+}
+
+// q = clamp(rint(x * inv), -127, 127) as the low byte of the result.
+__device__ __forceinline__ uint32_t pack_q(float x, float inv)
+{
+    float r = __builtin_rintf(x * inv);   // v_rndne_f32
+    r = __builtin_fminf(__builtin_fmaxf(r, -127.0f), 127.0f);
+    return (uint32_t)(int)r & 0xffu;
+}
+
+template <class Ops>
+DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pack(const char *__restrict__ payload, int64_t nbytes,
+                                                       char *__restrict__ q_plane, float *__restrict__ scales)
+{
+    constexpr int PER = Ops::PER;          // elements of a 16-byte item
+    constexpr int QB = 4 * PER;            // q bytes of a lane
+    const int lane = threadIdx.x;
+    const int64_t off = (int64_t)blockIdx.x * kPackBlock;
+    const __amdgpu_buffer_rsrc_t r = span_rsrc<kPackBlock>(payload, off, nbytes & ~(int64_t)15);
+    // the payload was just written by the publish or the average: the default cache policy
+    u32x4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = span_load<u32x4, 0>(r, lane * kPackLane + j * 16);
+    const Ragged rg = ragged_at(off, nbytes);
+    if (rg.lane == lane) {
+        const uint16_t *p = reinterpret_cast<const uint16_t *>(payload + (nbytes & ~(int64_t)15));
+        uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+            if (2 * i < rg.bytes) w[i / 2] |= (uint32_t)p[i] << (16 * (i & 1));
+        const u32x4 t{w[0], w[1], w[2], w[3]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (rg.item == j) v[j] = t;
+    }
+    float x[4 * PER];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pack_widen(Ops{}, v[j], x + j * PER);
+    // amax as the unsigned maximum of the |x| bit patterns: that of the values when all are finite, and
+    // at or above the exponent mask exactly when one is a NaN or an inf (k_peer_finite's test)
+    uint32_t m = 0;
+#pragma unroll
+    for (int e = 0; e < 4 * PER; ++e) {
+        const uint32_t a = pk_bits(x[e]) & 0x7fffffffu;
+        m = m > a ? m : a;
+    }
+    m = quad_umax(m);
+    const bool nonfinite = m >= 0x7f800000u;
+    const float amax = pk_float(m);
+    const bool normal = !nonfinite && amax >= 0x1p-100f;
+    const float den = normal ? amax : 1.0f;
+    const float inv = 127.0f / den;                  // the two divisions, once per lane
+    const float scale = nonfinite ? pk_float(0x7fc00000u) : normal ? den / 127.0f : 0.0f;
+    uint32_t q[QB / 4];
+#pragma unroll
+    for (int d = 0; d < QB / 4; ++d) {
+        const uint32_t w = pack_q(x[4 * d], inv) | pack_q(x[4 * d + 1], inv) << 8 | pack_q(x[4 * d + 2], inv) << 16 |
+                           pack_q(x[4 * d + 3], inv) << 24;
+        q[d] = normal ? w : 0u;
+    }
+    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
+        q_plane + (int64_t)blockIdx.x * (kStreamBlock * QB), 0, kStreamBlock * QB, 0x00020000);
+#pragma unroll
+    for (int d = 0; d < QB / 16; ++d)
+        span_store(rq, lane * QB + d * 16, u32x4{q[4 * d], q[4 * d + 1], q[4 * d + 2], q[4 * d + 3]});
+    if ((lane & 3) == 0) {   // the quad's scale: 16 per wave, 64 contiguous bytes
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            scales + (int64_t)blockIdx.x * kPackScales, 0, kPackScales * 4, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b32(pk_bits(scale), rs, lane, 0, kAuxStore);
+    }
+}
+
+// The mirror image, shaped like k_pull: at most max_blocks one-wave workgroups stride over the blocks.
+// The q bytes and the scale are the only reads that cross the link (`nt`: each is read once); workgroup
+// 0 also copies the 256-byte header from the peer's slot, exactly.
+template <class Ops>
+DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pull_unpack(char *__restrict__ dst, int64_t nbytes,
+                                                              const char *__restrict__ q_plane,
+                                                              const float *__restrict__ scales, int64_t nblocks,
+                                                              u32x4 *__restrict__ hdr_dst,
+                                                              const u32x4 *__restrict__ hdr_src)
+{
+    constexpr int PER = Ops::PER;
+    constexpr int QB = 4 * PER;
+    const int lane = threadIdx.x;
+    if (hdr_src && blockIdx.x == 0 && lane < 16) hdr_dst[lane] = __builtin_nontemporal_load(hdr_src + lane);
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const int64_t off = b * kPackBlock;
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(q_plane + b * (kStreamBlock * QB)), 0, kStreamBlock * QB, 0x00020000);
+        u32x4 w[QB / 16];
+#pragma unroll
+        for (int d = 0; d < QB / 16; ++d) w[d] = span_load<u32x4>(rq, lane * QB + d * 16);
+        const float scale = __builtin_nontemporal_load(scales + b * kPackScales + (lane >> 2));
+        const __amdgpu_buffer_rsrc_t r = span_rsrc<kPackBlock>(dst, off, nbytes & ~(int64_t)15);
+        const Ragged rg = ragged_at(off, nbytes);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float x[PER];
+#pragma unroll
+            for (int e = 0; e < PER; ++e) {
+                const int byte = j * PER + e;                        // of the lane's q bytes
+                const uint32_t word = w[byte / 16][(byte / 4) % 4];
+                const int qv = (int)(word << (24 - 8 * (byte % 4))) >> 24;   // the signed byte
+                x[e] = (float)qv * scale;
+            }
+            const u32x4 out = pack_narrow(Ops{}, x);
+            span_store(r, lane * kPackLane + j * 16, out);
+            if (rg.lane == lane && rg.item == j) {
+                uint16_t *p = reinterpret_cast<uint16_t *>(dst + (nbytes & ~(int64_t)15));
+#pragma unroll
+                for (int i = 0; i < 7; ++i)
+                    if (2 * i < rg.bytes) p[i] = (uint16_t)(out[i / 2] >> (16 * (i & 1)));
+            }
+        }
+    }
+}
+
+int64_t pack_blocks(int32_t dtype, int64_t n)
+{
+    const int64_t bytes = n * (int64_t)dtype_size(dtype);
+    return bytes <= 0 ? 1 : (bytes + kPackBlock - 1) / kPackBlock;
+}
+
+int64_t pack_scale_offset(int32_t dtype, int64_t n)
+{
+    const int64_t q = pack_blocks(dtype, n) * (kPackBlock / (int64_t)dtype_size(dtype));
+    return (q + 4095) / 4096 * 4096;
+}
+
+int64_t pack_image_bytes(int32_t dtype, int64_t n)
+{
+    return pack_scale_offset(dtype, n) + (pack_blocks(dtype, n) * kPackScales * 4 + 4095) / 4096 * 4096;
+}
+
+hipError_t launch_pack(int32_t dtype, const void *payload, int64_t n, void *image, hipStream_t s,
+                       const LaunchTiming *timing)
+{
+    if (!is_float_dtype(dtype) || n < 0 || !payload || !image || !aligned16(payload, image)) return hipErrorInvalidValue;
+    const int64_t blocks = pack_blocks(dtype, n);
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    return with_ops(dtype, [&](auto ops) {
+        return launch(k_pack<decltype(ops)>, dim3((uint32_t)blocks), dim3(kStreamBlock), s, timing, payload,
+                      n * (int64_t)dtype_size(dtype), image, (char *)image + pack_scale_offset(dtype, n));
+    });
+}
+
+hipError_t launch_pull_unpack(int32_t dtype, void *payload_out, int64_t n, const void *image, void *header_out,
+                              const void *header, int max_blocks, bool remote, hipStream_t s,
+                              const LaunchTiming *timing)
+{
+    if (!is_float_dtype(dtype) || n < 0 || !payload_out || !image || !aligned16(payload_out, image, header_out, header) ||
+        max_blocks < 1 || (!header) != (!header_out))
+        return hipErrorInvalidValue;
+    if (remote) hipLaunchKernelGGL(k_acquire_system, dim3(256), dim3(64), 0, s);
+    const int64_t blocks = pack_blocks(dtype, n);
+    return with_ops(dtype, [&](auto ops) {
+        return launch(k_pull_unpack<decltype(ops)>, dim3((uint32_t)std::min<int64_t>(blocks, max_blocks)),
+                      dim3(kStreamBlock), s, timing, payload_out, n * (int64_t)dtype_size(dtype), image,
+                      (const char *)image + pack_scale_offset(dtype, n), blocks, header_out, header);
+    });
+}
+
 }  // namespace dpwa

@@ -257,6 +257,25 @@ hipError_t launch_window_roll(const char *old, const char *cur, int64_t nbytes, 
 // bytes were written by an earlier kernel, read by other devices).
 hipError_t launch_release_system(hipStream_t s);
 
+// Packed snapshots (include/dpwa_hip.h "packed snapshots"; kernels.hip "packed snapshots"): the int8
+// block-scaled image of a single-dtype payload of `n` elements -- a q plane of one byte per element,
+// padded to whole 4-KiB payload blocks, then from pack_scale_offset on (a 4096-byte boundary) one fp32
+// scale per 256-byte group; pack_image_bytes in all.
+//   pack          payload -> image on `s` (one launch, no release: the caller's publish has one)
+//   pull_unpack   image -> payload_out with at most `max_blocks` workgroups, and (both or neither) the
+//                 256 bytes at `header` -> header_out; `remote`: the image is another GPU's memory --
+//                 preceded by the system-scope acquire of launch_pull
+// Nothing is written behind the payload's last byte.  hipErrorInvalidValue, nothing queued: a dtype
+// that is no element type, n < 0, a null or not 16-B aligned pointer, max_blocks < 1.
+int64_t pack_blocks(int32_t dtype, int64_t n);
+int64_t pack_scale_offset(int32_t dtype, int64_t n);
+int64_t pack_image_bytes(int32_t dtype, int64_t n);
+hipError_t launch_pack(int32_t dtype, const void *payload, int64_t n, void *image, hipStream_t s,
+                       const LaunchTiming *timing = nullptr);
+hipError_t launch_pull_unpack(int32_t dtype, void *payload_out, int64_t n, const void *image, void *header_out,
+                              const void *header, int max_blocks, bool remote, hipStream_t s,
+                              const LaunchTiming *timing = nullptr);
+
 // What the stateless entry points (learner.cpp, distance.cpp) share; `fn` names the entry in messages.
 // The caller's begin/end events as a launch's timing argument: NULL when none were given.
 struct CallerTiming {

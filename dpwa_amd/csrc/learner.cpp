@@ -457,6 +457,14 @@ struct dpwa_learner {
     bool relay_deferred = false;
     RelayArgs relay_saved{};
     int relay_saved_pick = -1, relay_saved_blocks = 0;
+    // packed snapshots (dpwa_learner_pack_enable): image k mirrors slot k, packed by every publish and
+    // pulled in place of the payload under DPWA_PULL_PACKED, see kernels.hip
+    bool pack_on = false;
+    int64_t pack_stride = 0;                 // bytes from image 0 to image 1
+    DevMem pack_mem;                         // 2 images, IPC-exported
+    std::unordered_map<int, const char *> pack_images;   // per peer: image 0 (IPC-mapped)
+    std::vector<char *> pack_opened;         // IPC mappings to close (dpwa_learner_destroy)
+    std::vector<DevMem> pack_imported;       // fd-imported images
     // host readers of published slots (wire bridge) run on other threads; their stream is created
     // at the first read, under pub_mu
     std::mutex pub_mu;
@@ -697,6 +705,7 @@ int dpwa_learner_destroy(dpwa_learner *l)
     (void)hipDeviceSynchronize();
     for (auto &kv : l->peers) close_endpoint(kv.second);
     for (char *p : l->relay_opened) (void)hipIpcCloseMemHandle(p);
+    for (char *p : l->pack_opened) (void)hipIpcCloseMemHandle(p);
     delete l;   // every member frees what it owns, on l's device (dg)
     return DPWA_OK;
 }
@@ -822,6 +831,7 @@ static int publish_impl(dpwa_learner *l, const void *flat, double loss, const do
         reuse = true;
     }
     const bool header_only = reuse && l->written_through.noted() && l->wt_flat == flat;
+    const bool release = l->exported && !l->pack_on;   // (a pack-enabled learner releases behind its k_pack)
     if (header_only) {
         // the payload was written by the last average (readers of slot k were waited for then);
         // work on `s` after this publish (the next factor reads the clock the average wrote) is
@@ -833,17 +843,23 @@ static int publish_impl(dpwa_learner *l, const void *flat, double loss, const do
         if (l->wt_header) {
             // header and clock of this publish were written by the last average too: nothing
             // moves (IPC-exported slots still get their system-scope write-back)
-            if (l->exported) HIP_TRY(launch_release_system(s));
+            if (release) HIP_TRY(launch_release_system(s));
             l->cur = (l->cur + 1) & 3;
         } else {
             HIP_TRY(launch_publish_header(slot, l->n, l->dtype, &l->ctl->clock[l->cur], loss, loss_dev, l->loss_f32,
-                                          l->version + 1, l->exported, s));
+                                          l->version + 1, release, s));
         }
     } else {
         if (l->resident) return set_error(DPWA_ERR_STATE, "resident learner: parameters not in the next slot");
         if (int rc = wait_slot_readers(l, k, s)) return rc;
         HIP_TRY(launch_publish(slot, flat, (int64_t)l->payload_bytes, l->n, l->dtype, &l->ctl->clock[l->cur], loss,
-                               loss_dev, l->loss_f32, l->version + 1, l->exported, s));
+                               loss_dev, l->loss_f32, l->version + 1, release, s));
+    }
+    if (l->pack_on) {
+        // the packed image of this snapshot, whichever way its payload got into the slot: behind the copy,
+        // the write-through average and the reuse guard's fix-up on `s`, ahead of the one system release
+        HIP_TRY(launch_pack(l->dtype, slot + kPayloadOff, l->n, l->pack_mem.ptr + (size_t)k * (size_t)l->pack_stride, s));
+        if (l->exported) HIP_TRY(launch_release_system(s));
     }
     l->written_through.clear();
     l->wt_header = false;
@@ -970,10 +986,12 @@ int dpwa_learner_ipc_handle(dpwa_learner *l, void *handle_out, int64_t handle_le
 
 int dpwa_learner_export_fds(dpwa_learner *l, int which, int *fds, int max_fds, int *n_fds, int64_t *chunk_bytes)
 {
-    if (!l || (which != 0 && which != 1) || !n_fds || (max_fds > 0 && !fds) || (which == 1 && !l->relay_on))
+    if (!l || which < 0 || which > 2 || !n_fds || (max_fds > 0 && !fds) || (which == 1 && !l->relay_on) ||
+        (which == 2 && !l->pack_on))
         return set_error(DPWA_ERR_ARG, "dpwa_learner_export_fds: bad arguments");
     DeviceGuard dg(l->device);
-    const int rc = devmem_export(which == 0 ? l->slot_mem : l->relay_mem, fds, max_fds, n_fds, chunk_bytes);
+    const int rc = devmem_export(which == 0 ? l->slot_mem : which == 1 ? l->relay_mem : l->pack_mem, fds, max_fds, n_fds,
+                                 chunk_bytes);
     if (rc == DPWA_OK) l->exported = true;
     return rc;
 }
@@ -1067,8 +1085,18 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
         if (std::find(rv.begin(), rv.end(), l) == rv.end()) rv.push_back(l);
     }
     dpwa_learner *const owner = ep.kind == 1 ? ep.local : nullptr;
-    const Pull pull{peer_slot, kPayloadOff + round_up(l->payload_bytes, 16), l->pull_mode, l->pull_blocks,
-                    ep.kind == 2 || ep.device != l->device};
+    Pull pull{peer_slot, kPayloadOff + round_up(l->payload_bytes, 16), l->pull_mode, l->pull_blocks,
+              ep.kind == 2 || ep.device != l->device};
+    if (l->pull_mode == DPWA_PULL_PACKED && ep.kind == 2) {   // (a local peer keeps its path: no link to save)
+        auto im = l->pack_images.find(peer_id);
+        if (im == l->pack_images.end())
+            return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: peer %d's packed images are not attached "
+                                             "(dpwa_learner_pack_attach)", peer_id);
+        pull.image = im->second + (size_t)k * (size_t)l->pack_stride;
+        pull.dtype = l->dtype;
+        pull.n = l->n;
+        pull.unpack = launch_pull_unpack;
+    }
     if (flags & DPWA_FETCH_RESCUE) return l->fetch.pull_rescue(pull, s, !(flags & DPWA_FETCH_PUBLISHED), owner, k);
     if ((flags & DPWA_FETCH_ZERO_COPY) && ep.kind == 1 && ep.device == l->device) {
         l->fetch.read_in_place(peer_slot, owner, k);
@@ -1668,6 +1696,9 @@ int dpwa_learner_relay_enable(dpwa_learner *l, int world, int rank)
     if (!l || world < 2 || world > kMaxRelayRanks || rank < 0 || rank >= world)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_enable: bad world/rank");
     if (l->relay_on) return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_enable: already enabled");
+    if (l->pull_mode == DPWA_PULL_PACKED)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_enable: the learner pulls packed snapshots (DPWA_PULL_PACKED); "
+                                         "packed stripes for the relay are not built");
     DeviceGuard dg(l->device);
     const int64_t payload16 = (int64_t)round_up(l->payload_bytes, 16);
     l->relay_stripe = (int64_t)round_up((size_t)((payload16 + world - 1) / world), kPayloadOff);
@@ -1742,6 +1773,83 @@ int dpwa_learner_relay_attach_fds(dpwa_learner *l, int rank, int peer_id, const 
     l->relay_slots[rank] = ep->base;
     l->relay_bufs[rank] = m.ptr;
     l->relay_imported.push_back(std::move(m));
+    return DPWA_OK;
+}
+
+// ---------------------------------------------------------------- packed snapshots
+// The relay buffer's pattern: one exportable allocation, a handle or fds for it, and a mapping per peer.
+int dpwa_learner_pack_enable(dpwa_learner *l)
+{
+    if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_pack_enable: NULL learner");
+    if (l->dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_pack_enable: packed snapshots are not built for a DPWA_MIXED learner "
+                                       "(a segmented codec)");
+    if (l->pack_on) return set_error(DPWA_ERR_STATE, "dpwa_learner_pack_enable: already enabled");
+    DeviceGuard dg(l->device);
+    const int64_t stride = (int64_t)round_up((size_t)pack_image_bytes(l->dtype, l->n), kPayloadOff);
+    DevMem m;   // built aside: a failure leaves the learner without images
+    HIP_TRY(devmem_alloc(m, 2 * (size_t)stride, l->device));
+    HIP_TRY(hipMemset(m.ptr, 0, 2 * (size_t)stride));
+    HIP_TRY(hipDeviceSynchronize());
+    l->pack_mem = std::move(m);
+    l->pack_stride = stride;
+    l->pack_on = true;
+    return DPWA_OK;
+}
+
+int dpwa_learner_pack_handle(dpwa_learner *l, void *handle_out, int64_t handle_len)
+{
+    if (!l || !l->pack_on || !handle_out || handle_len < (int64_t)sizeof(IpcBlob))
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_pack_handle: packed snapshots not enabled or short buffer");
+    DeviceGuard dg(l->device);
+    IpcBlob b = make_blob(l, l->pack_mem, l->pack_stride);
+    if (!b.vmm) HIP_TRY(hipIpcGetMemHandle(&b.handle, l->pack_mem.ptr));
+    memset(handle_out, 0, (size_t)handle_len);
+    memcpy(handle_out, &b, sizeof(b));
+    l->exported = true;
+    return DPWA_OK;
+}
+
+static int pack_check(dpwa_learner *l, int peer_id, const void *pack_handle, int64_t handle_len, IpcBlob &b,
+                      const char *fn)
+{
+    if (!l || !l->pack_on || !pack_handle || handle_len < (int64_t)sizeof(IpcBlob))
+        return set_error(DPWA_ERR_ARG, "%s: bad arguments", fn);
+    auto it = l->peers.find(peer_id);
+    if (it == l->peers.end() || it->second.kind != 2)
+        return set_error(DPWA_ERR_STATE, "%s: peer %d's slots are not IPC-attached", fn, peer_id);
+    memcpy(&b, pack_handle, sizeof(b));
+    if (b.magic != kIpcMagic || b.slot_stride != l->pack_stride || b.n != l->n || b.dtype != l->dtype)
+        return set_error(DPWA_ERR_ARG, "%s: the packed images of peer %d do not match", fn, peer_id);
+    return DPWA_OK;
+}
+
+int dpwa_learner_pack_attach(dpwa_learner *l, int peer_id, const void *pack_handle, int64_t handle_len)
+{
+    IpcBlob b;
+    int rc = pack_check(l, peer_id, pack_handle, handle_len, b, "dpwa_learner_pack_attach");
+    if (rc) return rc;
+    if (b.vmm) return set_error(DPWA_ERR_ARG, "dpwa_learner_pack_attach: peer %d shares its packed images as fds", peer_id);
+    DeviceGuard dg(l->device);
+    void *ptr = nullptr;
+    HIP_TRY(hipIpcOpenMemHandle(&ptr, b.handle, hipIpcMemLazyEnablePeerAccess));
+    l->pack_opened.push_back((char *)ptr);
+    l->pack_images[peer_id] = (const char *)ptr;
+    return DPWA_OK;
+}
+
+int dpwa_learner_pack_attach_fds(dpwa_learner *l, int peer_id, const void *pack_handle, int64_t handle_len,
+                                 const int *fds, int n_fds, int64_t chunk_bytes)
+{
+    IpcBlob b;
+    int rc = pack_check(l, peer_id, pack_handle, handle_len, b, "dpwa_learner_pack_attach_fds");
+    if (rc) return rc;
+    if (!b.vmm || !fds) return set_error(DPWA_ERR_ARG, "dpwa_learner_pack_attach_fds: peer %d shares a hipIpc handle", peer_id);
+    DeviceGuard dg(l->device);
+    DevMem m;
+    if ((rc = devmem_import(m, fds, n_fds, chunk_bytes, 2 * (size_t)l->pack_stride, l->device))) return rc;
+    l->pack_images[peer_id] = m.ptr;
+    l->pack_imported.push_back(std::move(m));
     return DPWA_OK;
 }
 
@@ -1921,8 +2029,18 @@ int dpwa_learner_set_loss_dtype(dpwa_learner *l, int32_t dtype)
 
 int dpwa_learner_set_pull(dpwa_learner *l, int mode, int max_blocks)
 {
-    if (!l || (mode != DPWA_PULL_COPY_ENGINE && mode != DPWA_PULL_KERNEL) || max_blocks < 1)
+    if (!l || (mode != DPWA_PULL_COPY_ENGINE && mode != DPWA_PULL_KERNEL && mode != DPWA_PULL_PACKED) || max_blocks < 1)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_set_pull: bad arguments");
+    if (mode == DPWA_PULL_PACKED) {
+        if (l->dtype == DPWA_MIXED)
+            return set_error(DPWA_ERR_ARG, "dpwa_learner_set_pull: DPWA_PULL_PACKED is not built for a DPWA_MIXED learner "
+                                           "(a segmented codec)");
+        if (l->relay_on)
+            return set_error(DPWA_ERR_STATE, "dpwa_learner_set_pull: DPWA_PULL_PACKED while the relay is enabled (packed "
+                                             "stripes for the relay are not built)");
+        if (!l->pack_on)
+            return set_error(DPWA_ERR_STATE, "dpwa_learner_set_pull: DPWA_PULL_PACKED needs dpwa_learner_pack_enable first");
+    }
     l->pull_mode = mode;
     l->pull_blocks = max_blocks;
     return DPWA_OK;

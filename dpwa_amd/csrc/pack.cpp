@@ -1,0 +1,54 @@
+// pack.cpp -- packed snapshots without a learner: the stateless entry points of include/dpwa_hip.h
+// (dpwa_pack_bytes, dpwa_pack, dpwa_unpack).  A learner's images, packed at every publish and pulled in
+// place of the payload (DPWA_PULL_PACKED), are in learner.cpp, beside the slots they mirror.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+
+using namespace dpwa;
+
+extern "C" {
+
+// What all three check first: the rule broken, or null.  Host only.
+static const char *pack_problem(int32_t dtype, int64_t n)
+{
+    if (dtype == DPWA_MIXED) return "a DPWA_MIXED payload has no packed form (one element type per image)";
+    if (!is_float_dtype(dtype)) return "unknown dtype";
+    if (n < 0 || n > INT64_MAX / 4) return "n < 0 or too large";
+    return nullptr;
+}
+
+int dpwa_pack_bytes(int32_t dtype, int64_t n, int64_t *bytes)
+{
+    if (!bytes) return set_error(DPWA_ERR_ARG, "dpwa_pack_bytes: NULL argument");
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_pack_bytes: %s", why);
+    *bytes = pack_image_bytes(dtype, n);
+    return DPWA_OK;
+}
+
+int dpwa_pack(int32_t dtype, const void *payload, int64_t n, void *image, dpwa_stream_t stream, void *start_event,
+              void *stop_event)
+{
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_pack: %s", why);
+    if (!payload || !image || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_pack: a NULL pointer, or one event without the other");
+    if (!aligned16(payload, image))
+        return set_error(DPWA_ERR_ARG, "dpwa_pack: the payload or the image is not 16-byte aligned (there is no unaligned form)");
+    HIP_TRY(launch_pack(dtype, payload, n, image, (hipStream_t)stream, CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
+int dpwa_unpack(int32_t dtype, const void *image, int64_t n, void *payload_out, int max_blocks, dpwa_stream_t stream,
+                void *start_event, void *stop_event)
+{
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_unpack: %s", why);
+    if (!payload_out || !image || (!start_event) != (!stop_event) || max_blocks < 1)
+        return set_error(DPWA_ERR_ARG, "dpwa_unpack: a NULL pointer, one event without the other, or max_blocks < 1");
+    if (!aligned16(payload_out, image))
+        return set_error(DPWA_ERR_ARG, "dpwa_unpack: the image or the payload is not 16-byte aligned (there is no unaligned form)");
+    HIP_TRY(launch_pull_unpack(dtype, payload_out, n, image, nullptr, nullptr, max_blocks, false, (hipStream_t)stream,
+                               CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
+}  // extern "C"

@@ -29,6 +29,14 @@ from .sched import Scheduler, seed_key
 
 LOGGER = logging.getLogger(__name__)
 RELAY_PULLS = ("relay", "relay-avg")   # DistGroup's multi-link transports (dpwa_amd/group.py)
+MIXED_PACKED = ("pull='packed' is not available for a model that mixes dtypes: the packed image holds one element "
+                "type (a segmented codec is not built); use 'kernel' or 'copy'")
+RELAY_PACKED = ("pull='packed' and the relay pulls do not combine (packed stripes for the relay are not built): a "
+                "connection is created with one or the other and cannot switch to the other")
+GROUP_PACKED = ("pull='packed' needs lock-step rounds between processes (a DistGroup: gossip 'lockstep'): the image "
+                "of a snapshot is rewritten two publishes later, which only the round's barrier orders behind its "
+                "readers; free-running rounds (AsyncDistGroup) are refused, and peers in this process have no link "
+                "to save")
 MIXED_RELAY_AVG = ("pull='relay-avg' is not available for a model that mixes dtypes: the relay's fused second "
                    "phase is built for one element type; use 'relay' (the same relay, gathered first), 'kernel' "
                    "or 'copy'")
@@ -415,6 +423,8 @@ class DpwaConnection:
         self._skip_nonfinite = bool(skip_nonfinite_peer)
         if self._skip_nonfinite and pull is not None and pull.partition(":")[0] == "relay-avg":
             raise ValueError(FINITE_RELAY_AVG)
+        if self._layout is not None and pull is not None and pull.partition(":")[0] == "packed":
+            raise ValueError(MIXED_PACKED)
         self.config = DpwaConfiguration(config_file)
         self.nodes = self.config.get_nodes()
         self.fetch_probability = self.config.get_fetch_probability()
@@ -474,6 +484,8 @@ class DpwaConnection:
         # created with a relay pull: the relay buffers are made at the bind even if set_pull has chosen
         # another transport for the first rounds by then (set_pull's promise about such a connection)
         self._relay_created = self._pull.partition(":")[0] in RELAY_PULLS
+        # created with the packed pull: the images are made and exchanged at the bind, as the relay buffers are
+        self._pack_created = self._pull.partition(":")[0] == "packed"
         self._out = ctypes.c_int()
         self._out_ref = ctypes.byref(self._out)
         self._f_update_send = lib.dpwa_node_update_send
@@ -491,6 +503,8 @@ class DpwaConnection:
             group = DistGroup(self.nodes, name)
         self._group = group if group is not None else default_group(config_file, self.nodes, name,
                                                                     self.config.config.get("gossip"))
+        if self._pack_created and not getattr(self._group, "pack_capable", False):
+            raise ValueError(GROUP_PACKED)
         self._eager = bool(self._group.eager_fetch)
         self._flags = (_lib.FLAG_EAGER if self._group.eager_fetch else 0) | \
                       (_lib.FLAG_ZERO_COPY if self._group.zero_copy else 0)
@@ -880,6 +894,12 @@ class DpwaConnection:
             _lib.call("dpwa_learner_set_param_distance", self._learner.handle, arr, len(self._param_ranges),
                       self._distance_every)
             self._param_distance = ParameterDistances(self._learner, [r[0] for r in self._param_ranges], where)
+        if self._pull.partition(":")[0] == "packed" or self._pack_created:
+            if self._layout is not None:
+                raise ValueError(MIXED_PACKED)
+            if not getattr(self._group, "pack_capable", False):
+                raise ValueError(GROUP_PACKED)
+            self._group.pack_images = True    # allocate + exchange the packed images in on_bind
         if self._pull.partition(":")[0] in RELAY_PULLS or \
                 (self._relay_created and getattr(self._group, "relay_capable", False)):
             if not hasattr(self._group, "relay_blocks"):
@@ -894,13 +914,23 @@ class DpwaConnection:
         'kernel[:blocks]' (pull kernel), 'relay[:blocks]' (DistGroup only, multi-link
         two-phase relay; the connection must have been created with a relay pull so the
         relay buffers exist -- they do even if this was called with another transport before
-        the first update_send) or 'relay-avg[:blocks]' (the same relay with its second phase
+        the first update_send), 'relay-avg[:blocks]' (the same relay with its second phase
         fused into the average: the averaging kernel reads the peer's stripes where the first
-        phase left them).  Every rank must switch between the same two rounds."""
+        phase left them) or 'packed[:blocks]' (DistGroup only, and the connection must have been
+        created with it: every publish also packs an int8 block-scaled image of the snapshot, and a
+        fetch reads the peer's image -- 0.266x the bytes for fp32, 0.516x for bf16 / fp16 -- and
+        expands it on arrival; the parameters averaged with are the dequantised ones, headers and
+        clocks stay exact).  Every rank must switch between the same two rounds."""
         kind, _, blocks = mode.partition(":")
-        if kind not in ("copy", "kernel") + RELAY_PULLS:
-            raise ValueError("pull must be 'copy', 'kernel[:blocks]', 'relay[:blocks]' or 'relay-avg[:blocks]', "
-                             "got %r" % mode)
+        if kind not in ("copy", "kernel", "packed") + RELAY_PULLS:
+            raise ValueError("pull must be 'copy', 'kernel[:blocks]', 'relay[:blocks]', 'relay-avg[:blocks]' or "
+                             "'packed[:blocks]', got %r" % mode)
+        if (kind == "packed" and self._relay_created) or (kind in RELAY_PULLS and self._pack_created):
+            raise ValueError(RELAY_PACKED)
+        if kind == "packed" and self._layout is not None:
+            raise ValueError(MIXED_PACKED)
+        if kind == "packed" and not getattr(self._group, "pack_capable", False):
+            raise ValueError(GROUP_PACKED)
         if kind == "relay-avg" and self._layout is not None:
             raise ValueError(MIXED_RELAY_AVG)
         if kind == "relay-avg" and self._track_distance:
@@ -922,6 +952,11 @@ class DpwaConnection:
         if getattr(self._group, "relay_blocks", 0):
             self._group.relay_blocks = 0
         self._flags &= ~_lib.FLAG_PICK_ONLY
+        if kind == "packed":
+            if not getattr(self._group, "pack_ready", False):
+                raise ValueError("packed pull: create the connection with pull='packed' under a DistGroup")
+            _lib.call("dpwa_learner_set_pull", learner.handle, _lib.PULL_PACKED, int(blocks or 512))
+            return
         _lib.call("dpwa_learner_set_pull", learner.handle, _lib.PULL_KERNEL if kind == "kernel" else
                   _lib.PULL_COPY_ENGINE, int(blocks or 512))
 

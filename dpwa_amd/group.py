@@ -271,6 +271,7 @@ class DistGroup:
     eager_fetch = True
     zero_copy = False
     relay_capable = True         # lock-step rounds: the relay pulls are available
+    pack_capable = True          # ... and the packed pull: the round's barrier covers the images as it does the slots
     consensus_refusal = None
 
     def __init__(self, nodes, name, process_group=None):
@@ -293,6 +294,8 @@ class DistGroup:
         self.relay_blocks = 0        # > 0: relay transport (set by the connection's pull mode)
         self.relay_ready = False     # relay buffers allocated and exchanged
         self.relay_fused = False     # phase 2 read by the averaging kernel itself (pull "relay-avg")
+        self.pack_images = False     # packed images wanted (set by a connection created with pull "packed")
+        self.pack_ready = False      # packed images allocated and exchanged
         self._picks = None
         self._pick = None
 
@@ -313,11 +316,19 @@ class DistGroup:
             buf = ctypes.create_string_buffer(_lib.IPC_HANDLE_BYTES)
             _lib.call("dpwa_learner_relay_handle", learner._h, buf, _lib.IPC_HANDLE_BYTES)
             relay = buf.raw
+        pack = b""
+        if self.pack_images:
+            _lib.call("dpwa_learner_pack_enable", learner._h)
+            buf = ctypes.create_string_buffer(_lib.IPC_HANDLE_BYTES)
+            _lib.call("dpwa_learner_pack_handle", learner._h, buf, _lib.IPC_HANDLE_BYTES)
+            pack = buf.raw
         slot_fds, slot_chunk = learner.export_fds(0)
         relay_fds, relay_chunk = learner.export_fds(1) if self.relay_blocks else ([], 0)
-        server = _FdServer(slot_fds + relay_fds, self.world - 1) if (slot_fds or relay_fds) else None
+        pack_fds, pack_chunk = learner.export_fds(2) if self.pack_images else ([], 0)
+        all_fds = slot_fds + relay_fds + pack_fds
+        server = _FdServer(all_fds, self.world - 1) if all_fds else None
         mine = (handle, relay, server.address if server else None, len(slot_fds), slot_chunk, len(relay_fds),
-                relay_chunk, os.getpid())
+                relay_chunk, os.getpid(), pack, len(pack_fds), pack_chunk)
         infos = [None] * self.world
         try:
             self.dist.all_gather_object(infos, mine, group=self.pg)
@@ -325,8 +336,8 @@ class DistGroup:
                 server.allow(info[7] for r, info in enumerate(infos) if r != self.rank)
             for k in range(len(conn.peers)):
                 r = conn.peer_rank(k)
-                h, rh, address, ns, cs, nr, cr, _ = infos[r]
-                fds = _fetch_fds(address, ns + nr) if address else []
+                h, rh, address, ns, cs, nr, cr, _, ph, np_, cp = infos[r]
+                fds = _fetch_fds(address, ns + nr + np_) if address else []
                 try:
                     if ns:
                         learner.attach_fds(k, h, fds[:ns], cs)
@@ -340,6 +351,14 @@ class DistGroup:
                                       arr, nr, cr)
                         else:
                             _lib.call("dpwa_learner_relay_attach", learner._h, r, k, blob, _lib.IPC_HANDLE_BYTES)
+                    if self.pack_images:
+                        blob = ctypes.create_string_buffer(bytes(ph), _lib.IPC_HANDLE_BYTES)
+                        if np_:
+                            arr = (ctypes.c_int * np_)(*fds[ns + nr:])
+                            _lib.call("dpwa_learner_pack_attach_fds", learner._h, k, blob, _lib.IPC_HANDLE_BYTES,
+                                      arr, np_, cp)
+                        else:
+                            _lib.call("dpwa_learner_pack_attach", learner._h, k, blob, _lib.IPC_HANDLE_BYTES)
                 finally:
                     for fd in fds:
                         os.close(fd)
@@ -355,6 +374,7 @@ class DistGroup:
         else:
             if server is not None:
                 server.finish()
+        self.pack_ready = bool(self.pack_images)
         if self.relay_blocks:
             dev = learner.device
             self._pick = torch.full((1,), -1, dtype=torch.int32, device=dev)
@@ -459,6 +479,7 @@ class AsyncDistGroup(DistGroup):
     died answers as a refused connection (conn.py:253-256).  The copy and kernel pulls and
     write-through snapshots are supported; the relay needs lock-step rounds."""
     relay_capable = False
+    pack_capable = False         # (free-running groups: nothing orders a publish behind the readers of an image)
 
     def __init__(self, nodes, name, process_group=None, publish_timeout_ms=None):
         super().__init__(nodes, name, process_group)

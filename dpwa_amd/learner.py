@@ -179,8 +179,8 @@ class Learner:
         _lib.call("dpwa_learner_attach_ipc", self._h, peer_id, buf, _lib.IPC_HANDLE_BYTES)
 
     def export_fds(self, which=0):
-        """(fds, chunk bytes) sharing this learner's snapshot slots (which=0) or relay buffer
-        (which=1) when that allocation is VMM-backed (>= 1.5 GiB, or DPWA_VMM=1); ([], 0)
+        """(fds, chunk bytes) sharing this learner's snapshot slots (which=0), relay buffer
+        (which=1) or packed images (which=2) when that allocation is VMM-backed (>= 1.5 GiB, or DPWA_VMM=1); ([], 0)
         for an ordinary allocation, shared by ipc_handle's hipIpc handle.  The caller closes
         the fds once the peers hold theirs."""
         arr = (ctypes.c_int * MAX_FDS)()

@@ -43,7 +43,10 @@ extern "C" {
  * dpwa_check_finite_mixed, dpwa_learner_set_finite_check, dpwa_learner_finite_skips,
  * dpwa_node_set_finite_check.
  * Still 11, by additions only: the consensus of a group (dpwa_consensus_record) --
- * dpwa_consensus_workspace, dpwa_consensus, dpwa_consensus_mixed, dpwa_learner_consensus. */
+ * dpwa_consensus_workspace, dpwa_consensus, dpwa_consensus_mixed, dpwa_learner_consensus.
+ * Still 11, by additions only: packed snapshots (DPWA_PULL_PACKED, a new mode of dpwa_learner_set_pull;
+ * which = 2 of dpwa_learner_export_fds) -- dpwa_pack_bytes, dpwa_pack, dpwa_unpack, dpwa_learner_pack_enable,
+ * dpwa_learner_pack_handle, dpwa_learner_pack_attach, dpwa_learner_pack_attach_fds. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -309,6 +312,47 @@ int dpwa_consensus(int32_t dtype, const void *const *payloads, int count, int64_
 int dpwa_consensus_mixed(const dpwa_layout *layout, const void *const *payloads, int count, void *out, void *workspace,
                          dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
 
+/* Packed snapshots (extension, opt-in): an int8 block-scaled image of a single-dtype payload, which a
+ * publisher keeps beside each snapshot and a peer pulls in place of the payload (DPWA_PULL_PACKED), so
+ * that 68 B (fp32, 0.266x) or 132 B (bf16 / fp16, 0.516x) cross the link for every 256 B of payload.
+ * The header travels exactly; the parameters a peer receives are the dequantised ones, by this rule,
+ * fixed to the bit (tests/pack_ref.py restates it in numpy).  All arithmetic is fp32, every operation
+ * separately rounded (no contraction):
+ *   groups    the payload is cut into groups of 256 bytes: 64 fp32 elements, or 128 bf16 / fp16 elements,
+ *             which are first widened exactly to fp32.  The last group counts the bytes past the
+ *             payload's end as zeros, whatever the memory there holds.
+ *   amax      the maximum of |x| over the group.
+ *   a group with a NaN or a +-inf (exponent bits all ones): scale = the quiet NaN 0x7FC00000, every q = 0;
+ *             the whole group dequantises to NaN, so a non-finite peer stays visible to the non-finite
+ *             peer check and a NaN spreads as it does unpacked.
+ *   a group with amax < 0x1p-100f (zero included): scale = +0.0f, every q = 0; the group dequantises to
+ *             +0.0 -- values this tiny are flushed, signed zeros become +0.0.
+ *   otherwise scale = amax / 127.0f, inv = 127.0f / amax (two fp32 divisions), and for every element
+ *             q = clamp(rint(x * inv), -127, 127), rint rounding to nearest even, stored as int8.
+ *   back      x' = (float)q * scale; a bf16 / fp16 payload then rounds x' to nearest even.
+ *             |x' - x| <= amax / 127 (0.5 + 2^-15) before that last rounding: the half step, plus the
+ *             roundings of inv, x * inv, scale and the product (values with few mantissa bits do land on
+ *             exact ties of x * inv and reach past amax / 254).
+ *             (127 * scale may round above amax by one unit in the last place: an fp32 group whose amax
+ *             is FLT_MAX dequantises its +-127 to +-inf.)
+ * The image is a q plane and a scale plane.  With B = max(1, ceil(payload bytes / 4096)) payload blocks:
+ * the q plane holds one byte per element in payload order, padded with zeros to B whole blocks (1024 B
+ * per block of fp32, 2048 B of a 16-bit type); the scale plane starts at the next 4096-byte boundary and
+ * holds one fp32 per group, 16 per block (+0.0f for the groups past the end); the image ends at the next
+ * 4096-byte boundary.  dpwa_pack_bytes gives that size, a function of (dtype, n) alone.
+ *   dpwa_pack     payload (n elements) -> image, one launch on `stream`; writes both planes whole (B blocks
+ *                 each) and no other byte: the padding between and behind them is never written or read.
+ *   dpwa_unpack   image -> payload_out (n elements) with at most max_blocks one-wave workgroups; writes
+ *                 nothing behind the payload's last byte.
+ * Events as dpwa_average.  DPWA_ERR_ARG, nothing queued: DPWA_MIXED (a segmented codec is not built) or an
+ * unknown dtype, n < 0, a NULL pointer, a payload or image that is not 16-B aligned (there is no
+ * unaligned form), max_blocks < 1, one event without the other. */
+int dpwa_pack_bytes(int32_t dtype, int64_t n, int64_t *bytes);
+int dpwa_pack(int32_t dtype, const void *payload, int64_t n, void *image, dpwa_stream_t stream, void *start_event,
+              void *stop_event);
+int dpwa_unpack(int32_t dtype, const void *image, int64_t n, void *payload_out, int max_blocks, dpwa_stream_t stream,
+                void *start_event, void *stop_event);
+
 /* The per-parameter distance (extension, opt-in): the two sums above for every parameter tensor t of
  * the model, over that tensor's own elements only -- dist2_t = sum (double(q_i) - double(p_i))^2 and
  * norm2_t = sum double(p_i)^2 with dpwa_distance's arithmetic.  Where the tensors lie in the payload
@@ -457,7 +501,7 @@ int dpwa_learner_version(const dpwa_learner *l, uint64_t *version);
  * carries its hipIpcGetMemHandle.  Allocations of 1.5 GiB and more (or any size with
  * DPWA_VMM=1) are hipMemCreate chunks instead -- hipIpcOpenMemHandle does not return for
  * allocations above ~2 GiB on this ROCm stack -- and are shared as POSIX fds:
- * export_fds (which = 0: snapshot slots, 1: relay buffer) yields one fd per chunk, *n_fds = 0
+ * export_fds (which = 0: snapshot slots, 1: relay buffer, 2: packed images) yields one fd per chunk, *n_fds = 0
  * for an ordinary allocation; the caller passes them to the peer process (e.g. SCM_RIGHTS over
  * a Unix socket) and closes its copies; the peer maps them with attach_fds (the fds stay the
  * caller's). */
@@ -715,6 +759,20 @@ int dpwa_learner_relay_phase1(dpwa_learner *l, const int32_t *picks_dev, uint64_
                               dpwa_stream_t stream);
 int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_pick, uint64_t version,
                               int blocks, int fuse);
+/* Packed snapshots of a learner (the codec: "packed snapshots" above).  pack_enable allocates two
+ * images, image k beside slot k, zeroed once; from then on every publish -- the full one, the
+ * header-only one behind a write-through average, a resident learner's -- packs slot (version - 1) % 2
+ * into image (version - 1) % 2 on the publish's stream, ahead of its system-scope release.  The image
+ * of publish v is next rewritten by publish v + 2, exactly as the slot is, so whatever keeps a peer's
+ * read of the slot ahead of that publish (the lock-step round's barrier) covers the image.
+ * pack_handle / pack_attach / pack_attach_fds export the images and map peer `peer_id`'s (whose slots are
+ * IPC-attached already), as the relay buffer's calls do; fds come from export_fds with which = 2.
+ * DPWA_ERR_ARG: a DPWA_MIXED learner, images of another n or dtype.  DPWA_ERR_STATE: enabled twice. */
+int dpwa_learner_pack_enable(dpwa_learner *l);
+int dpwa_learner_pack_handle(dpwa_learner *l, void *handle_out, int64_t handle_len);
+int dpwa_learner_pack_attach(dpwa_learner *l, int peer_id, const void *pack_handle, int64_t handle_len);
+int dpwa_learner_pack_attach_fds(dpwa_learner *l, int peer_id, const void *pack_handle, int64_t handle_len,
+                                 const int *fds, int n_fds, int64_t chunk_bytes);
 /* Kernel timing for measurement.  time_averages allocates `capacity` begin/end event pairs
  * (0 frees them; synchronises the device).  After arm_timing, the next averaging launch
  * (average / average_through, 16-B aligned parameters) goes through hipExtLaunchKernelGGL
@@ -740,7 +798,13 @@ int dpwa_learner_wait_fetch(dpwa_learner *l, dpwa_stream_t stream);
 
 /* How a copying fetch (any non-zero-copy fetch) moves its bytes: DPWA_PULL_COPY_ENGINE
  * (hipMemcpyAsync on the side stream, the default) or DPWA_PULL_KERNEL (a copy kernel of at
- * most max_blocks workgroups reading the IPC-mapped peer slot over xGMI). */
+ * most max_blocks workgroups reading the IPC-mapped peer slot over xGMI), or DPWA_PULL_PACKED (lock-step
+ * rounds between processes: a kernel of at most max_blocks one-wave workgroups reads the peer's packed
+ * image of that slot and its header and writes the header and the dequantised payload where the other
+ * modes write the copy -- same buffers, streams, timing and timeouts; everything after the fetch sees an
+ * ordinary snapshot, the lossy one.  A peer in this process keeps its own path.  It needs pack_enable
+ * (DPWA_ERR_STATE without, and while the relay is enabled; DPWA_ERR_ARG for a DPWA_MIXED learner); a fetch
+ * from a peer whose images are not attached is DPWA_ERR_STATE). */
 /* What a device loss pointer (`loss_dev` of publish / factor / average) points at: a float64
  * (DPWA_F64, the default) or a float32 (DPWA_F32: e.g. a training loss tensor passed as is,
  * widened exactly on the device as Python's float() widens it). */
@@ -748,6 +812,7 @@ int dpwa_learner_set_loss_dtype(dpwa_learner *l, int32_t dtype);
 
 #define DPWA_PULL_COPY_ENGINE 0
 #define DPWA_PULL_KERNEL 1
+#define DPWA_PULL_PACKED 2
 int dpwa_learner_set_pull(dpwa_learner *l, int mode, int max_blocks);
 
 /* Reference-style seam (dpwa.py:156 returns (payload, factor) and pytorch.py:68 does the
