@@ -32,7 +32,7 @@ CONNECT_OK, CONNECT_REFUSED, CONNECT_ERROR = 0, 1, 2
 REPLY_PAYLOAD, REPLY_EMPTY, REPLY_TIMEOUT, REPLY_ERROR = 3, 4, 5, 6
 PEER_READY, PEER_NO_STATE, PEER_DOWN, PEER_SLOW, PEER_DEAD = 0, 1, 2, 3, 4
 NODE_PEER_UNSET, NODE_PEER_LOCAL, NODE_PEER_REMOTE = 0, 1, 2
-PULL_COPY_ENGINE, PULL_KERNEL, PULL_PACKED = 0, 1, 2
+PULL_COPY_ENGINE, PULL_KERNEL, PULL_PACKED, PULL_PACKED_AVG = 0, 1, 2, 3
 FETCH_ZERO_COPY, FETCH_PUBLISHED, FETCH_RESCUE = 1, 2, 4
 FETCH_LANDED, FETCH_IN_FLIGHT, FETCH_TIMED_OUT = 0, 1, 2
 FLAG_EAGER, FLAG_ZERO_COPY, FLAG_REUSE_SNAPSHOT, FLAG_WRITE_THROUGH, FLAG_PICK_ONLY = 1, 2, 4, 8, 16
@@ -166,6 +166,7 @@ SIGNATURES = {
     "dpwa_pack_bytes": [_i32, _i64, ctypes.POINTER(_i64)],
     "dpwa_pack": [_i32, _vp, _i64, _vp, _vp, _vp, _vp],
     "dpwa_unpack": [_i32, _vp, _i64, _vp, _int, _vp, _vp, _vp],
+    "dpwa_average_packed": [_i32, _vp, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp],
     "dpwa_learner_consensus": [_vp, ctypes.POINTER(_i32), _int, _u64, _vp, _vp, _vp],
     "dpwa_learner_set_finite_check": [_vp, _int],
     "dpwa_learner_finite_skips": [_vp, ctypes.POINTER(_u64)],

@@ -139,7 +139,7 @@ class DpwaPyTorchAdapter:
         gpu = DpwaConfiguration(config_file).get_gpu(name)      # optional per-node placement
         self._flat = FlatParameters(net.named_parameters(), device=None if gpu is None else torch.device("cuda", gpu))
         if transport == "wire":
-            if str(connection_kwargs.get("pull") or "").partition(":")[0] == "packed":
+            if str(connection_kwargs.get("pull") or "").partition(":")[0] in ("packed", "packed-avg"):
                 raise ValueError("pull='packed' needs the device transport: the wire transport speaks the reference's "
                                  "protocol, which carries float32 snapshots whole")
             from ..bridge import SnapshotCodec, WireConnection

@@ -129,11 +129,23 @@ struct Pull {
     hipError_t (*unpack)(int32_t dtype, void *payload_out, int64_t n, const void *image, void *header_out,
                          const void *header, int max_blocks, bool remote, hipStream_t s,
                          const LaunchTiming *timing) = nullptr;
+    // DPWA_PULL_PACKED_AVG (`image_bytes` set, `unpack` not): the image crosses the link as bytes -- the copy
+    // engine, or the pull kernel when `mode` is DPWA_PULL_KERNEL -- into the landing image that accompanies the
+    // staging buffer, and only the header goes into the buffer itself; nothing is expanded here.
+    size_t image_bytes = 0;
+    bool lands_packed() const { return image_bytes && !unpack; }
     // on `stream`, between the events of the fetch-timing pair `ft` when there is one
-    int into(char *dst, hipStream_t stream, const LaunchTiming *ft = nullptr) const
+    int into(char *dst, hipStream_t stream, const LaunchTiming *ft = nullptr, char *landing = nullptr) const
     {
+        if (lands_packed() && !landing) return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: no landing image");
         if (ft) HIP_TRY(hipEventRecord(ft->start, stream));
-        if (unpack)
+        if (lands_packed() && mode == DPWA_PULL_KERNEL) {
+            HIP_TRY(launch_pull(dst, from, (int64_t)sizeof(dpwa_header), 1, cross_device, stream));
+            HIP_TRY(launch_pull(landing, image, (int64_t)image_bytes, blocks, cross_device, stream));
+        } else if (lands_packed()) {
+            HIP_TRY(hipMemcpyAsync(dst, from, sizeof(dpwa_header), hipMemcpyDefault, stream));
+            HIP_TRY(hipMemcpyAsync(landing, image, image_bytes, hipMemcpyDefault, stream));
+        } else if (unpack)
             HIP_TRY(unpack(dtype, dst + DPWA_SLOT_PAYLOAD_OFFSET, n, image, dst, from, blocks, cross_device, stream, nullptr));
         else if (mode == DPWA_PULL_KERNEL)
             HIP_TRY(launch_pull(dst, from, (int64_t)bytes, blocks, cross_device, stream));
@@ -153,6 +165,9 @@ struct Source {
     bool copied = false;                    // a copy, which `landed` covers
     const void *owner = nullptr;            // local peer whose slot is being read (reader tracking); null: none
     int slot = -1;
+    // DPWA_PULL_PACKED_AVG: the payload behind this header is still packed, in this landing image (which `landed`
+    // and the staging buffer's done event cover with the buffer); null: it lies behind the header
+    const char *packed = nullptr;
     int lane() const { return kind == Lane ? index : -1; }
 };
 
@@ -186,6 +201,7 @@ public:
     {
         phase_ = Phase::None;
         src_.ptr = nullptr;
+        src_.packed = nullptr;
     }
 
     const Source &source() const { return src_; }
@@ -194,6 +210,17 @@ public:
     // Is there a copy to wait for?  (An in-place source has none: stream order covers it.)
     bool awaits_copy() const { return fetched() && src_.copied; }
     char *staging() const { return staging_[0].ptr(); }
+    // The landing images of DPWA_PULL_PACKED_AVG, one beside each staging buffer a lock-step pull can land in
+    // (pull_ordered: 0; pull_published: 0 and 1), `bytes` each; made once (dpwa_learner_set_pull), never in a round.
+    hipError_t alloc_landing(size_t bytes)
+    {
+        hipError_t e = hipSuccess;
+        for (int b = 0; b < 2 && e == hipSuccess; ++b)
+            if (!landing_[b].ptr()) e = landing_[b].alloc(bytes);
+        return e;
+    }
+    // The landing image was expanded into the staging payload (by the consumer, on its stream behind wait_landed).
+    void unpacked() { src_.packed = nullptr; }
     RescueLanes &lanes() { return lanes_; }
     hipStream_t stream() const { return stream_ ? stream_ : side_; }   // the fetch in flight moves its bytes on it
     // Where this learner finished reading its last source: whoever rewrites that orders after it.
@@ -249,9 +276,9 @@ public:
         stage_next_ ^= 1;
         // WAR: the average that last read this buffer; nothing else on the caller's stream
         HIP_TRY(stage_done_[b].wait(side_));
-        if (int rc = p.into(staging_[b].ptr(), side_, ft)) return rc;
+        if (int rc = p.into(staging_[b].ptr(), side_, ft, landing_[b].ptr())) return rc;
         HIP_TRY(landed_.record(side_));
-        pulled(Source{staging_[b].ptr(), Source::Staging, b, true, owner, slot});
+        pulled(Source{staging_[b].ptr(), Source::Staging, b, true, owner, slot, p.lands_packed() ? landing_[b].ptr() : nullptr});
         return DPWA_OK;
     }
 
@@ -265,9 +292,9 @@ public:
         // WAR on our own staging buffer: the previous average must have consumed it (the side
         // stream waits, and now follows `s`, which covers a consumption on itself)
         HIP_TRY(consumed_.order(side_, s));
-        if (int rc = p.into(staging_[0].ptr(), side_, ft)) return rc;
+        if (int rc = p.into(staging_[0].ptr(), side_, ft, landing_[0].ptr())) return rc;
         HIP_TRY(landed_.record(side_));
-        pulled(Source{staging_[0].ptr(), Source::Staging, 0, true, owner, slot});
+        pulled(Source{staging_[0].ptr(), Source::Staging, 0, true, owner, slot, p.lands_packed() ? landing_[0].ptr() : nullptr});
         return DPWA_OK;
     }
 
@@ -406,6 +433,7 @@ private:
     size_t slot_stride_ = 0;
     hipStream_t side_ = nullptr;        // the learner's (not owned)
     DevBuf staging_[2];                 // 1 slot each; the second for published pulls
+    DevBuf landing_[2];                 // the packed image that lands beside staging b (DPWA_PULL_PACKED_AVG)
     DoneEvent stage_done_[2];           // the last reader of staging b is done
     int stage_next_ = 0;
     RescueLanes lanes_;

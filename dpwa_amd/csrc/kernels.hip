@@ -2789,4 +2789,152 @@ hipError_t launch_pull_unpack(int32_t dtype, void *payload_out, int64_t n, const
     });
 }
 
+// ---------------------------------------------------------------- the average straight from a packed image
+// k_lerp's fused factor + lerp (lerp_span: one-wave workgroups over an exact grid of 1-KiB payload spans,
+// a 16-byte item per lane, the parameter load and the two stores through descriptors ranged to the
+// payload's whole items, the cache policy by size) with the peer operand dequantised in registers from the
+// packed image instead of loaded from a contiguous payload: k_pull_unpack's store and k_lerp's load of the
+// same bytes, 2 n s of HBM traffic, drop out of a DPWA_PULL_PACKED_AVG round.
+//
+// Lane l of span s owns the item at payload byte 1024 s + 16 l.  The q plane holds one byte per element
+// in payload order, so its q bytes are the PER bytes at q-plane offset 64 PER s + PER l: one dword (fp32)
+// or two (16-bit) per lane, one coalesced 256- or 512-byte `nt` read per wave.  A 256-byte group is 16
+// lanes, so the wave needs scales[4 s .. 4 s + 3]: either every lane loads its own (four distinct
+// addresses, one 16-byte request per wave), or -- USCALE, the default by measurement -- the four come
+// through the wave's one uniform 16-byte load and three selects pick the lane's (DESIGN §3 has the timing
+// of both).  No LDS memory.
+// The image is padded to whole 4-KiB blocks, so neither plane is range-checked; the grid covers the
+// payload's bytes and so never leaves the image.
+//
+// x' = (float)q * scale is one separately rounded fp32 multiply per element and a 16-bit type rounds it
+// with pack_narrow, so the item is, to the bit, what k_pull_unpack would have stored; Ops::lerp is
+// unchanged.  The ragged item of a payload that is no multiple of 16 bytes belongs to one lane, which has
+// its q bytes and scale in registers anyway: it reads and writes the parameters' elements one by one
+// (Ops::lerp_s) and nothing behind the payload's last byte.
+template <class V> __device__ __forceinline__ float item_elem(OpsF32, V v, int i) { return v[i]; }
+template <class Ops, class V> __device__ __forceinline__ uint16_t item_elem(Ops, V v, int i)
+{
+    return (uint16_t)(v[i / 2] >> (16 * (i & 1)));
+}
+
+template <class Ops, bool DUAL, bool OOP, int POLICY, bool USCALE>
+__global__ __launch_bounds__(kStreamBlock) void k_lerp_packed(typename Ops::V *__restrict__ param,
+                                                              const char *__restrict__ q_plane,
+                                                              const float *__restrict__ scales, int64_t n,
+                                                              LerpArgs args)
+{
+    using V = typename Ops::V;
+    using S = typename Ops::S;
+    using P = LerpPolicy<POLICY>;
+    constexpr int PER = Ops::PER;
+    constexpr int SPAN = kStreamBlock * 16;
+    const int lane = threadIdx.x;
+    const int lane_off = lane * 16;
+    const int64_t nbytes = n * (int64_t)sizeof(S);
+    const int64_t vbytes = nbytes & ~(int64_t)15;
+    const int64_t span_off = (int64_t)blockIdx.x * SPAN;
+    const __amdgpu_buffer_rsrc_t rp = span_rsrc<SPAN>(param, span_off, vbytes);
+    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)(q_plane + (int64_t)blockIdx.x * (kStreamBlock * PER)), 0, kStreamBlock * PER, 0x00020000);
+    // issue this lane's loads before anything else
+    const V p = span_load<V, P::param_load>(rp, lane_off);
+    uint32_t w[PER / 4];
+    if constexpr (PER == 4) {
+        w[0] = __builtin_amdgcn_raw_buffer_load_b32(rq, lane * 4, 0, kAuxStream);
+    } else {
+        const auto w2 = __builtin_amdgcn_raw_buffer_load_b64(rq, lane * 8, 0, kAuxStream);
+        w[0] = w2[0], w[1] = w2[1];
+    }
+    float scale;
+    const float *const sc = scales + (int64_t)blockIdx.x * 4;
+    if constexpr (USCALE) {
+        const f32x4 s4 = *reinterpret_cast<const f32x4 *>(sc);   // uniform: the wave's one load
+        const int g = lane >> 4;
+        scale = g == 0 ? s4.x : g == 1 ? s4.y : g == 2 ? s4.z : s4.w;
+    } else {
+        scale = __builtin_nontemporal_load(sc + (lane >> 4));
+    }
+    const bool ragged = (nbytes & 15) && span_off + lane_off == vbytes;   // this lane owns the partial item
+    [[maybe_unused]] S *const ps = reinterpret_cast<S *>(reinterpret_cast<char *>(param) + vbytes);
+    [[maybe_unused]] S *const ss = reinterpret_cast<S *>(reinterpret_cast<char *>(args.snap) + vbytes);
+    const int rag = (int)(nbytes & 15) / (int)sizeof(S);
+    float a, b;
+    if (!lerp_coef<COEF_FUSED>(args, blockIdx.x == 0, a, b)) {
+        if (DUAL) {   // no-op round; a write-through snapshot still gets the parameters
+            span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, p);
+            if (ragged) {
+#pragma unroll
+                for (int i = 0; i < PER - 1; ++i)
+                    if (i < rag) ss[i] = ps[i];
+            }
+        }
+        return;
+    }
+    float x[PER];
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+        const int qv = (int)(w[e / 4] << (24 - 8 * (e % 4))) >> 24;   // the signed byte
+        x[e] = (float)qv * scale;
+    }
+    const V q = __builtin_bit_cast(V, pack_narrow(Ops{}, x));
+    const V r = Ops::lerp(a, b, q, p);
+    if (!OOP) span_store<V, P::store>(rp, lane_off, r);
+    if (DUAL) span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, r);
+    if (ragged) {
+#pragma unroll
+        for (int i = 0; i < PER - 1; ++i)
+            if (i < rag) {
+                const S t = Ops::lerp_s(a, b, item_elem(Ops{}, q, i), ps[i]);
+                if (!OOP) ps[i] = t;
+                if (DUAL) ss[i] = t;
+            }
+    }
+}
+
+// How the wave gets its four scales (k_lerp_packed): the wave's one uniform load, or with
+// DPWA_PACKED_SCALES=lane every lane's own (A/B runs).  Measured write-through, interleaved on the same
+// buffers (profiles/pack_avg_cost.json, pack_avg_cost_lane.json): 11.17M fp32 24.6 us against 32.5,
+// 2^26 bf16 64.8 against 69.7.
+constexpr int kPackedScalesUniform = 1;
+static bool packed_scales_uniform()
+{
+    static const bool on = env_knob("DPWA_PACKED_SCALES", kPackedScalesUniform, [](const char *e) {
+        return strcmp(e, "uniform") == 0 ? 1 : strcmp(e, "lane") == 0 ? 0 : kNoValue;
+    }) != 0;
+    return on;
+}
+
+hipError_t launch_average_packed(int32_t dtype, void *param, int64_t n, const void *image, const FusedArgs &fa,
+                                 void *snap, hipStream_t s, const LaunchTiming *timing, bool oop)
+{
+    if (!is_float_dtype(dtype) || n < 0 || !image || (!param && n > 0) || (oop && !snap && n > 0) ||
+        !aligned16(param, image, snap))
+        return hipErrorInvalidValue;
+    const int64_t nbytes = n * (int64_t)dtype_size(dtype);
+    const int64_t grid = nbytes <= 0 ? 1 : (nbytes + kStreamBlock * 16 - 1) / (kStreamBlock * 16);
+    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+    LerpArgs args{};
+    args.fused = fa;
+    args.snap = snap;
+    const char *const q_plane = (const char *)image;
+    const float *const scales = (const float *)(q_plane + pack_scale_offset(dtype, n));
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        using V = typename Ops::V;
+        const auto run = [&](void (*kernel)(V *, const char *, const float *, int64_t, LerpArgs)) {
+            return launch(kernel, dim3((uint32_t)grid), dim3(kStreamBlock), s, timing, param, q_plane, scales, n, args);
+        };
+        const auto forms = [&](auto uscale) {
+            constexpr bool U = decltype(uscale)::value;
+            // (resident: the product policy unless DPWA_LERP_POLICY forces the other, as k_lerp's resident form)
+            return BySizePolicies::with(oop ? lerp_policy() : lerp_policy(nbytes), [&](auto policy) {
+                constexpr int P = decltype(policy)::value;
+                if (oop) return run(k_lerp_packed<Ops, true, true, P, U>);
+                return snap ? run(k_lerp_packed<Ops, true, false, P, U>) : run(k_lerp_packed<Ops, false, false, P, U>);
+            });
+        };
+        return packed_scales_uniform() ? forms(std::true_type{}) : forms(std::false_type{});
+    });
+}
+
 }  // namespace dpwa

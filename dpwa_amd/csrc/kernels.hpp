@@ -276,6 +276,15 @@ hipError_t launch_pull_unpack(int32_t dtype, void *payload_out, int64_t n, const
                               const void *header, int max_blocks, bool remote, hipStream_t s,
                               const LaunchTiming *timing = nullptr);
 
+// The fused average of launch_average with the peer operand read from a packed image (k_lerp_packed):
+// `image` is what launch_pack wrote for a payload of `n` elements of `dtype`, fa.hdr the peer's header,
+// which lies wherever the caller has it.  The bits are those of launch_pull_unpack into a buffer followed
+// by launch_average from it.  hipErrorInvalidValue, nothing queued: a dtype that is no element type
+// (DPWA_MIXED among them), n < 0, a null image, `param` / `snap` / `image` not 16-B aligned (there is no
+// unaligned form), `oop` without `snap`, more than 2^31 - 1 spans.
+hipError_t launch_average_packed(int32_t dtype, void *param, int64_t n, const void *image, const FusedArgs &fa,
+                                 void *snap, hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
+
 // What the stateless entry points (learner.cpp, distance.cpp) share; `fn` names the entry in messages.
 // The caller's begin/end events as a launch's timing argument: NULL when none were given.
 struct CallerTiming {

@@ -460,6 +460,7 @@ struct dpwa_learner {
     // packed snapshots (dpwa_learner_pack_enable): image k mirrors slot k, packed by every publish and
     // pulled in place of the payload under DPWA_PULL_PACKED, see kernels.hip
     bool pack_on = false;
+    bool pull_by_kernel = false;             // DPWA_PULL_PACKED_AVG with a block cap: the image moves by launch_pull
     int64_t pack_stride = 0;                 // bytes from image 0 to image 1
     DevMem pack_mem;                         // 2 images, IPC-exported
     std::unordered_map<int, const char *> pack_images;   // per peer: image 0 (IPC-mapped)
@@ -1087,7 +1088,8 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
     dpwa_learner *const owner = ep.kind == 1 ? ep.local : nullptr;
     Pull pull{peer_slot, kPayloadOff + round_up(l->payload_bytes, 16), l->pull_mode, l->pull_blocks,
               ep.kind == 2 || ep.device != l->device};
-    if (l->pull_mode == DPWA_PULL_PACKED && ep.kind == 2) {   // (a local peer keeps its path: no link to save)
+    const bool packed_pull = l->pull_mode == DPWA_PULL_PACKED || l->pull_mode == DPWA_PULL_PACKED_AVG;
+    if (packed_pull && ep.kind == 2) {   // (a local peer keeps its path: no link to save)
         auto im = l->pack_images.find(peer_id);
         if (im == l->pack_images.end())
             return set_error(DPWA_ERR_STATE, "dpwa_learner_fetch: peer %d's packed images are not attached "
@@ -1095,7 +1097,14 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
         pull.image = im->second + (size_t)k * (size_t)l->pack_stride;
         pull.dtype = l->dtype;
         pull.n = l->n;
-        pull.unpack = launch_pull_unpack;
+        if (l->pull_mode == DPWA_PULL_PACKED_AVG && !(flags & DPWA_FETCH_RESCUE)) {
+            // the image lands as it is, beside the staging buffer; the average reads it there (a rescue pull
+            // keeps DPWA_PULL_PACKED's path: a lane has no landing image)
+            pull.image_bytes = (size_t)pack_image_bytes(l->dtype, l->n);
+            pull.mode = l->pull_by_kernel ? DPWA_PULL_KERNEL : DPWA_PULL_COPY_ENGINE;
+        } else {
+            pull.unpack = launch_pull_unpack;
+        }
     }
     if (flags & DPWA_FETCH_RESCUE) return l->fetch.pull_rescue(pull, s, !(flags & DPWA_FETCH_PUBLISHED), owner, k);
     if ((flags & DPWA_FETCH_ZERO_COPY) && ep.kind == 1 && ep.device == l->device) {
@@ -1108,6 +1117,22 @@ int dpwa_learner_fetch(dpwa_learner *l, int peer_id, uint64_t peer_version, int 
 }
 
 static int relay_materialize(dpwa_learner *l);
+
+// A fetch source whose payload is still packed (DPWA_PULL_PACKED_AVG) and whose consumer is not the fused
+// average: the landing image is expanded into the staging payload behind the header, on the consumer's
+// stream behind the landing, and everything goes on as under DPWA_PULL_PACKED.  Noted as a read of the
+// source: the staging buffer's next refill then waits for this launch whatever follows it on `s`.
+static int pack_materialize(dpwa_learner *l, hipStream_t s)
+{
+    const Source &src = l->fetch.source();
+    if (!l->fetch.fetched() || !src.packed) return DPWA_OK;
+    HIP_TRY(l->fetch.wait_landed(s));
+    HIP_TRY(launch_pull_unpack(l->dtype, const_cast<char *>(src.ptr) + kPayloadOff, l->n, src.packed, nullptr, nullptr,
+                               INT_MAX, false, s));
+    HIP_TRY(l->fetch.note_consumed(s));
+    l->fetch.unpacked();
+    return DPWA_OK;
+}
 
 static FusedArgs fused_args(dpwa_learner *l, double loss, const double *loss_dev)
 {
@@ -1148,6 +1173,7 @@ int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dp
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = relay_materialize(l)) return rc;
+    if (int rc = pack_materialize(l, s)) return rc;
     HIP_TRY(l->fetch.wait_landed(s));
     const FusedArgs fa = fused_args(l, loss, loss_dev);
     if (int rc = finite_pass(l, fa, l->fetch.source().ptr + kPayloadOff, s)) return rc;
@@ -1172,6 +1198,7 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     if (l->dtype == DPWA_MIXED && !aligned16(flat))   // (its layout is known: the factor was computed)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
     if (int rc = l->measure.operands_problem("dpwa_learner_lerp", flat)) return rc;
+    if (int rc = pack_materialize(l, s)) return rc;   // (a second pull since the factor)
     const Measured m{&l->measure, payload(l), flat, l->fetch.source().ptr + kPayloadOff, nullptr};
     int rc = measured_average(&m, 1, s, [&]() -> int {
         HIP_TRY(launch_lerp(m.p, flat, m.peer, m.p.coef, 0.f, 0.f, s));
@@ -1190,6 +1217,7 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
 struct AvgPlan {
     void *flat = nullptr;
     const char *peer = nullptr;   // payload averaged with (contiguous source)
+    const char *image = nullptr;  // ... or the packed image it is still in (k_lerp_packed); then `peer` is null
     char *snap = nullptr;         // write-through destination
     FusedArgs fa{};
     bool relay = false;           // the relay's phase 2 fused into this average (k_lerp_relay)
@@ -1198,8 +1226,9 @@ struct AvgPlan {
     int snap_slot = -1;
 };
 
+// `alone`: the plan is launched by average_launch, never as a member of a batched, pair or group dispatch.
 static int average_prepare(dpwa_learner *l, void *flat, double loss, const double *loss_dev, hipStream_t s,
-                           bool write_through, AvgPlan &p)
+                           bool write_through, AvgPlan &p, bool alone)
 {
     if (!l->fetch.fetched() || l->fetch.factored()) return set_error(DPWA_ERR_STATE, "dpwa_learner_average: no fetch in flight");
     if (int rc = need_layout(l, "dpwa_learner_average")) return rc;
@@ -1238,7 +1267,16 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
         p.relay = true;
     } else {
         if (int rc = relay_materialize(l)) return rc;
-        p.peer = l->fetch.source().ptr + kPayloadOff;
+        // a payload that is still packed: k_lerp_packed reads the landing image itself, unless something of this
+        // round needs the contiguous payload (a measurement, the non-finite check, a batched dispatch, the
+        // unaligned form), which expands it first
+        if (l->fetch.source().packed && alone && !l->measure.whole() && !l->measure.param() && !l->finite_check &&
+            aligned16(flat, p.snap)) {
+            p.image = l->fetch.source().packed;
+        } else {
+            if (int rc = pack_materialize(l, s)) return rc;
+            p.peer = l->fetch.source().ptr + kPayloadOff;
+        }
     }
     HIP_TRY(l->fetch.wait_landed(s));
     return DPWA_OK;
@@ -1281,6 +1319,8 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
         if (p.relay) {   // (never a segmented payload: relay_phase2 refuses)
             HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
                                          timing, p.oop));
+        } else if (p.image) {   // (never a segmented payload or a measuring learner: average_prepare)
+            HIP_TRY(launch_average_packed(l->dtype, p.flat, l->n, p.image, p.fa, p.snap, s, timing, p.oop));
         } else {
             HIP_TRY(launch_average(e, p.flat, p.peer, p.fa, p.snap, s, timing, p.oop));
         }
@@ -1293,7 +1333,7 @@ static int average_impl(dpwa_learner *l, void *flat, double loss, const double *
 {
     TraceRange tr("dpwa.average");
     AvgPlan p;
-    if (int rc = average_prepare(l, flat, loss, loss_dev, s, write_through, p)) return rc;
+    if (int rc = average_prepare(l, flat, loss, loss_dev, s, write_through, p, true)) return rc;
     if (int rc = average_launch(l, p, s)) return rc;
     return average_commit(l, p, s);
 }
@@ -1394,7 +1434,7 @@ int dpwa_learner_average_many(dpwa_learner *const *ls, void *const *flats, const
     idx.reserve((size_t)count);
     for (int i = 0; i < count; ++i) {
         int rc = average_prepare(ls[i], flats[i], loss[i], loss_dev ? loss_dev[i] : nullptr, s, write_through[i] != 0,
-                                 plans[i]);
+                                 plans[i], false);
         if (rc) return rc;   // nothing launched yet for this learner; earlier ones are prepared only
         idx.push_back(i);
     }
@@ -1696,7 +1736,7 @@ int dpwa_learner_relay_enable(dpwa_learner *l, int world, int rank)
     if (!l || world < 2 || world > kMaxRelayRanks || rank < 0 || rank >= world)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_relay_enable: bad world/rank");
     if (l->relay_on) return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_enable: already enabled");
-    if (l->pull_mode == DPWA_PULL_PACKED)
+    if (l->pull_mode == DPWA_PULL_PACKED || l->pull_mode == DPWA_PULL_PACKED_AVG)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_enable: the learner pulls packed snapshots (DPWA_PULL_PACKED); "
                                          "packed stripes for the relay are not built");
     DeviceGuard dg(l->device);
@@ -2015,6 +2055,7 @@ int dpwa_learner_wait_fetch(dpwa_learner *l, dpwa_stream_t stream)
     if (l->fetch.awaits_copy()) {
         DeviceGuard dg(l->device);
         if (int rc = relay_materialize(l)) return rc;
+        if (int rc = pack_materialize(l, (hipStream_t)stream)) return rc;
         HIP_TRY(l->fetch.wait_landed((hipStream_t)stream));
     }
     return DPWA_OK;
@@ -2029,9 +2070,10 @@ int dpwa_learner_set_loss_dtype(dpwa_learner *l, int32_t dtype)
 
 int dpwa_learner_set_pull(dpwa_learner *l, int mode, int max_blocks)
 {
-    if (!l || (mode != DPWA_PULL_COPY_ENGINE && mode != DPWA_PULL_KERNEL && mode != DPWA_PULL_PACKED) || max_blocks < 1)
+    if (!l || mode < DPWA_PULL_COPY_ENGINE || mode > DPWA_PULL_PACKED_AVG || max_blocks < 0 ||
+        (max_blocks == 0 && mode != DPWA_PULL_PACKED_AVG))
         return set_error(DPWA_ERR_ARG, "dpwa_learner_set_pull: bad arguments");
-    if (mode == DPWA_PULL_PACKED) {
+    if (mode == DPWA_PULL_PACKED || mode == DPWA_PULL_PACKED_AVG) {
         if (l->dtype == DPWA_MIXED)
             return set_error(DPWA_ERR_ARG, "dpwa_learner_set_pull: DPWA_PULL_PACKED is not built for a DPWA_MIXED learner "
                                            "(a segmented codec)");
@@ -2041,8 +2083,13 @@ int dpwa_learner_set_pull(dpwa_learner *l, int mode, int max_blocks)
         if (!l->pack_on)
             return set_error(DPWA_ERR_STATE, "dpwa_learner_set_pull: DPWA_PULL_PACKED needs dpwa_learner_pack_enable first");
     }
+    if (mode == DPWA_PULL_PACKED_AVG) {   // the landing images, here and never inside a round
+        DeviceGuard dg(l->device);
+        HIP_TRY(l->fetch.alloc_landing((size_t)pack_image_bytes(l->dtype, l->n)));
+    }
     l->pull_mode = mode;
-    l->pull_blocks = max_blocks;
+    l->pull_by_kernel = mode == DPWA_PULL_PACKED_AVG && max_blocks > 0;
+    l->pull_blocks = max_blocks > 0 ? max_blocks : 512;   // (a rescue pull of DPWA_PULL_PACKED_AVG unpacks with the default)
     return DPWA_OK;
 }
 
@@ -2062,6 +2109,7 @@ int dpwa_learner_copy_fetched(dpwa_learner *l, void *dst_dev, dpwa_stream_t stre
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = relay_materialize(l)) return rc;
+    if (int rc = pack_materialize(l, s)) return rc;
     HIP_TRY(l->fetch.wait_landed(s));
     if (l->payload_bytes)
         HIP_TRY(hipMemcpyAsync(dst_dev, l->fetch.source().ptr + kPayloadOff, l->payload_bytes, hipMemcpyDeviceToDevice, s));

@@ -51,4 +51,23 @@ int dpwa_unpack(int32_t dtype, const void *image, int64_t n, void *payload_out, 
     return DPWA_OK;
 }
 
+// dpwa_average with the peer's payload still packed: dpwa_unpack into a buffer and dpwa_average from it, in one
+// launch and without the buffer (k_lerp_packed).
+int dpwa_average_packed(int32_t dtype, void *param, const void *header, const void *image, int64_t n,
+                        const dpwa_interp *cfg, double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload,
+                        dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_average_packed: %s", why);
+    if (!cfg || !clock_dev || !coef_dev || !header || !image || (n > 0 && !param) || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_packed: a NULL pointer, or one event without the other");
+    if (int rc = check_method(cfg, "dpwa_average_packed")) return rc;
+    if (!aligned16(param, image, snap_payload))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_packed: the parameters, the image or the snapshot payload is not "
+                                       "16-byte aligned (there is no unaligned form)");
+    const FusedArgs fa = stateless_args(cfg, clock_dev, header, loss, coef_dev);
+    HIP_TRY(launch_average_packed(dtype, param, n, image, fa, snap_payload, (hipStream_t)stream,
+                                  CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
 }  // extern "C"

@@ -29,6 +29,9 @@ from .sched import Scheduler, seed_key
 
 LOGGER = logging.getLogger(__name__)
 RELAY_PULLS = ("relay", "relay-avg")   # DistGroup's multi-link transports (dpwa_amd/group.py)
+# the packed pulls: 'packed' expands the image on arrival, 'packed-avg' leaves that to the averaging kernel; one
+# set of preconditions and refusals (the messages name 'packed' for both)
+PACKED_PULLS = ("packed", "packed-avg")
 MIXED_PACKED = ("pull='packed' is not available for a model that mixes dtypes: the packed image holds one element "
                 "type (a segmented codec is not built); use 'kernel' or 'copy'")
 RELAY_PACKED = ("pull='packed' and the relay pulls do not combine (packed stripes for the relay are not built): a "
@@ -423,7 +426,7 @@ class DpwaConnection:
         self._skip_nonfinite = bool(skip_nonfinite_peer)
         if self._skip_nonfinite and pull is not None and pull.partition(":")[0] == "relay-avg":
             raise ValueError(FINITE_RELAY_AVG)
-        if self._layout is not None and pull is not None and pull.partition(":")[0] == "packed":
+        if self._layout is not None and pull is not None and pull.partition(":")[0] in PACKED_PULLS:
             raise ValueError(MIXED_PACKED)
         self.config = DpwaConfiguration(config_file)
         self.nodes = self.config.get_nodes()
@@ -485,7 +488,7 @@ class DpwaConnection:
         # another transport for the first rounds by then (set_pull's promise about such a connection)
         self._relay_created = self._pull.partition(":")[0] in RELAY_PULLS
         # created with the packed pull: the images are made and exchanged at the bind, as the relay buffers are
-        self._pack_created = self._pull.partition(":")[0] == "packed"
+        self._pack_created = self._pull.partition(":")[0] in PACKED_PULLS
         self._out = ctypes.c_int()
         self._out_ref = ctypes.byref(self._out)
         self._f_update_send = lib.dpwa_node_update_send
@@ -894,7 +897,7 @@ class DpwaConnection:
             _lib.call("dpwa_learner_set_param_distance", self._learner.handle, arr, len(self._param_ranges),
                       self._distance_every)
             self._param_distance = ParameterDistances(self._learner, [r[0] for r in self._param_ranges], where)
-        if self._pull.partition(":")[0] == "packed" or self._pack_created:
+        if self._pull.partition(":")[0] in PACKED_PULLS or self._pack_created:
             if self._layout is not None:
                 raise ValueError(MIXED_PACKED)
             if not getattr(self._group, "pack_capable", False):
@@ -920,16 +923,21 @@ class DpwaConnection:
         created with it: every publish also packs an int8 block-scaled image of the snapshot, and a
         fetch reads the peer's image -- 0.266x the bytes for fp32, 0.516x for bf16 / fp16 -- and
         expands it on arrival; the parameters averaged with are the dequantised ones, headers and
-        clocks stay exact).  Every rank must switch between the same two rounds."""
+        clocks stay exact) or 'packed-avg[:blocks]' (the same connections, bytes on the link and bits
+        as 'packed', without the expansion: the image lands as it is -- by the copy engine, or with
+        ':blocks' by the pull kernel -- and the averaging kernel dequantises it in registers; a
+        round that needs the contiguous payload -- the split update_wait, a tracked distance, the
+        non-finite check, a batched average, unaligned parameters -- expands it first, as 'packed'
+        does).  Every rank must switch between the same two rounds."""
         kind, _, blocks = mode.partition(":")
-        if kind not in ("copy", "kernel", "packed") + RELAY_PULLS:
-            raise ValueError("pull must be 'copy', 'kernel[:blocks]', 'relay[:blocks]', 'relay-avg[:blocks]' or "
-                             "'packed[:blocks]', got %r" % mode)
-        if (kind == "packed" and self._relay_created) or (kind in RELAY_PULLS and self._pack_created):
+        if kind not in ("copy", "kernel") + PACKED_PULLS + RELAY_PULLS:
+            raise ValueError("pull must be 'copy', 'kernel[:blocks]', 'relay[:blocks]', 'relay-avg[:blocks]', "
+                             "'packed[:blocks]' or 'packed-avg[:blocks]', got %r" % mode)
+        if (kind in PACKED_PULLS and self._relay_created) or (kind in RELAY_PULLS and self._pack_created):
             raise ValueError(RELAY_PACKED)
-        if kind == "packed" and self._layout is not None:
+        if kind in PACKED_PULLS and self._layout is not None:
             raise ValueError(MIXED_PACKED)
-        if kind == "packed" and not getattr(self._group, "pack_capable", False):
+        if kind in PACKED_PULLS and not getattr(self._group, "pack_capable", False):
             raise ValueError(GROUP_PACKED)
         if kind == "relay-avg" and self._layout is not None:
             raise ValueError(MIXED_RELAY_AVG)
@@ -952,10 +960,13 @@ class DpwaConnection:
         if getattr(self._group, "relay_blocks", 0):
             self._group.relay_blocks = 0
         self._flags &= ~_lib.FLAG_PICK_ONLY
-        if kind == "packed":
+        if kind in PACKED_PULLS:
             if not getattr(self._group, "pack_ready", False):
                 raise ValueError("packed pull: create the connection with pull='packed' under a DistGroup")
-            _lib.call("dpwa_learner_set_pull", learner.handle, _lib.PULL_PACKED, int(blocks or 512))
+            if kind == "packed":
+                _lib.call("dpwa_learner_set_pull", learner.handle, _lib.PULL_PACKED, int(blocks or 512))
+            else:   # no block cap: the copy engine moves the image (max_blocks 0)
+                _lib.call("dpwa_learner_set_pull", learner.handle, _lib.PULL_PACKED_AVG, int(blocks or 0))
             return
         _lib.call("dpwa_learner_set_pull", learner.handle, _lib.PULL_KERNEL if kind == "kernel" else
                   _lib.PULL_COPY_ENGINE, int(blocks or 512))

@@ -294,7 +294,7 @@ class DistGroup:
         self.relay_blocks = 0        # > 0: relay transport (set by the connection's pull mode)
         self.relay_ready = False     # relay buffers allocated and exchanged
         self.relay_fused = False     # phase 2 read by the averaging kernel itself (pull "relay-avg")
-        self.pack_images = False     # packed images wanted (set by a connection created with pull "packed")
+        self.pack_images = False     # packed images wanted (set by a connection created with a packed pull)
         self.pack_ready = False      # packed images allocated and exchanged
         self._picks = None
         self._pick = None

@@ -46,7 +46,9 @@ extern "C" {
  * dpwa_consensus_workspace, dpwa_consensus, dpwa_consensus_mixed, dpwa_learner_consensus.
  * Still 11, by additions only: packed snapshots (DPWA_PULL_PACKED, a new mode of dpwa_learner_set_pull;
  * which = 2 of dpwa_learner_export_fds) -- dpwa_pack_bytes, dpwa_pack, dpwa_unpack, dpwa_learner_pack_enable,
- * dpwa_learner_pack_handle, dpwa_learner_pack_attach, dpwa_learner_pack_attach_fds. */
+ * dpwa_learner_pack_handle, dpwa_learner_pack_attach, dpwa_learner_pack_attach_fds.
+ * Still 11, by additions only: the average straight from a packed image -- dpwa_average_packed, and
+ * DPWA_PULL_PACKED_AVG, a new mode of dpwa_learner_set_pull (which alone accepts max_blocks = 0). */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -352,6 +354,20 @@ int dpwa_pack(int32_t dtype, const void *payload, int64_t n, void *image, dpwa_s
               void *stop_event);
 int dpwa_unpack(int32_t dtype, const void *image, int64_t n, void *payload_out, int max_blocks, dpwa_stream_t stream,
                 void *start_event, void *stop_event);
+/* dpwa_average with the peer's payload still packed: the stateless twin of dpwa_average whose peer operand is
+ * the image dpwa_pack wrote (`image`) and whose factor reads the peer's 256-byte dpwa_header at `header`,
+ * wherever that lies.  One launch (k_lerp_packed): every element is dequantised in registers by the rule
+ * above ("back") and goes through dpwa_average's arithmetic, so param, snap_payload, the clock and *coef_dev
+ * end up, to the bit, as dpwa_unpack into a buffer followed by dpwa_average from it leave them -- the no-op
+ * (ZeroDivision) round included, in which a write-through snapshot still receives the unchanged parameters.
+ * Nothing behind the payload's last byte is written, in param or in snap_payload.  The image is read whole
+ * blocks at a time, as dpwa_pack wrote it.  DPWA_ERR_ARG, nothing queued: what dpwa_average and dpwa_unpack
+ * refuse -- DPWA_MIXED or an unknown dtype, n < 0, a NULL pointer (snap_payload may be NULL: no write-through),
+ * an unknown method, param / image / snap_payload not 16-B aligned (there is no unaligned form), one event
+ * without the other. */
+int dpwa_average_packed(int32_t dtype, void *param, const void *header, const void *image, int64_t n,
+                        const dpwa_interp *cfg, double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload,
+                        dpwa_stream_t stream, void *start_event, void *stop_event);
 
 /* The per-parameter distance (extension, opt-in): the two sums above for every parameter tensor t of
  * the model, over that tensor's own elements only -- dist2_t = sum (double(q_i) - double(p_i))^2 and
@@ -804,7 +820,17 @@ int dpwa_learner_wait_fetch(dpwa_learner *l, dpwa_stream_t stream);
  * modes write the copy -- same buffers, streams, timing and timeouts; everything after the fetch sees an
  * ordinary snapshot, the lossy one.  A peer in this process keeps its own path.  It needs pack_enable
  * (DPWA_ERR_STATE without, and while the relay is enabled; DPWA_ERR_ARG for a DPWA_MIXED learner); a fetch
- * from a peer whose images are not attached is DPWA_ERR_STATE). */
+ * from a peer whose images are not attached is DPWA_ERR_STATE), or DPWA_PULL_PACKED_AVG (DPWA_PULL_PACKED's
+ * preconditions, refusals and bits in every round, without its unpack: the fetch copies the peer's header into
+ * staging and the peer's image, as bytes, into a landing image of this learner's -- the copy engine when
+ * max_blocks is 0, which only this mode accepts, else the pull kernel of at most max_blocks workgroups -- and
+ * dpwa_learner_average / average_through dequantise it in registers (k_lerp_packed, dpwa_average_packed's
+ * kernel), so the expanded payload is never stored and read back.  set_pull allocates the landing images, one
+ * beside each staging buffer; no round allocates.  Whatever else consumes the fetch first expands the landing
+ * image into the staging payload with one launch on the consumer's stream and goes on as under
+ * DPWA_PULL_PACKED: dpwa_learner_factor / lerp, wait_fetch, copy_fetched, dpwa_learner_average_many, a learner
+ * that measures a distance or skips non-finite peers, parameters that are not 16-B aligned.  A rescue pull
+ * (DPWA_FETCH_RESCUE) and a peer in this process keep DPWA_PULL_PACKED's paths). */
 /* What a device loss pointer (`loss_dev` of publish / factor / average) points at: a float64
  * (DPWA_F64, the default) or a float32 (DPWA_F32: e.g. a training loss tensor passed as is,
  * widened exactly on the device as Python's float() widens it). */
@@ -813,6 +839,7 @@ int dpwa_learner_set_loss_dtype(dpwa_learner *l, int32_t dtype);
 #define DPWA_PULL_COPY_ENGINE 0
 #define DPWA_PULL_KERNEL 1
 #define DPWA_PULL_PACKED 2
+#define DPWA_PULL_PACKED_AVG 3
 int dpwa_learner_set_pull(dpwa_learner *l, int mode, int max_blocks);
 
 /* Reference-style seam (dpwa.py:156 returns (payload, factor) and pytorch.py:68 does the

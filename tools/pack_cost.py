@@ -6,6 +6,13 @@ should not exceed the mix's p90 of the same repeat ("within_mix_p90").  No link 
 the payload are both in this GPU's memory.
 
     python tools/pack_cost.py [--launches K] [--warmup W] [--repeats R] [--out FILE]
+
+--avg measures the average straight from the image instead (profiles/pack_avg_cost.json), the same way, all
+write-through: "pair" dpwa_unpack + dpwa_average back to back, from the first dispatch's begin to the second's end
+(the two launches dpwa_average_packed replaces); "fused" dpwa_average_packed; "mix" dpwa_stream_mix(nr=2, nw=2), the
+nearest mix its arguments express -- it reads 2 n s where the fused kernel reads (1 + 1/s + 1/64) n s, so it
+over-counts reads; "avg" the plain dpwa_average, whose peer is contiguous.  Every buffer is local and, at these
+sizes, Infinity-Cache warm from the launch before.
 """
 import argparse
 import ctypes
@@ -57,6 +64,78 @@ def compare(lib, code, tdtype, n, launches, warmup, max_blocks, dev):
     return {f: [1e3 * a.elapsed_time(b) for a, b in pairs[warmup:]] for f, pairs in ev.items()}, size.value
 
 
+AVG_FORMS = ("pair", "fused", "mix", "avg")
+
+
+def compare_avg(lib, code, tdtype, n, launches, warmup, max_blocks, dev):
+    """One repeat of the --avg forms, interleaved; constant factor 0.5 on the same parameters throughout."""
+    esize = torch.empty((), dtype=tdtype).element_size()
+    off = _lib.SLOT_PAYLOAD_OFFSET // esize
+    param, snap = torch.empty(n, device=dev, dtype=tdtype).normal_(), torch.empty(n, device=dev, dtype=tdtype)
+    slot = torch.zeros(off + n, device=dev, dtype=tdtype)          # a zero header (clock 0), then the peer's payload
+    slot[off:].normal_()
+    size = ctypes.c_int64()
+    _lib.call("dpwa_pack_bytes", code, n, ctypes.byref(size))
+    image = torch.zeros(size.value, dtype=torch.uint8, device=dev)
+    s = _lib.stream_handle(None)
+    _lib.call("dpwa_pack", code, slot[off:].data_ptr(), n, image.data_ptr(), s, None, None)
+    clock = torch.zeros(2, dtype=torch.float64, device=dev)
+    coef = torch.zeros(32, dtype=torch.uint8, device=dev)
+    cfg = _lib.Interp(_lib.INTERP_CONSTANT, 0, 0.5, 0.0)
+    tail = (ctypes.byref(cfg), clock.data_ptr(), 1.0, coef.data_ptr(), snap.data_ptr(), s)
+    src = (ctypes.c_void_p * 2)(param.data_ptr(), slot[off:].data_ptr())
+    dst = (ctypes.c_void_p * 2)(param.data_ptr(), snap.data_ptr())
+    nbytes = n * esize // 16 * 16
+    total = warmup + launches
+    ev = {f: events(total) for f in AVG_FORMS}
+    mid = events(total)
+    torch.cuda.synchronize()
+    for i in range(total):
+        k = i % len(AVG_FORMS)
+        for form in AVG_FORMS[k:] + AVG_FORMS[:k]:
+            a0, a1 = (e.cuda_event for e in ev[form][i])
+            if form == "pair":
+                m0, m1 = (e.cuda_event for e in mid[i])
+                rc = lib.dpwa_unpack(code, image.data_ptr(), n, slot[off:].data_ptr(), max_blocks, s, a0, m0) or \
+                    lib.dpwa_average(code, param.data_ptr(), slot.data_ptr(), n, *tail, m1, a1)
+            elif form == "fused":
+                rc = lib.dpwa_average_packed(code, param.data_ptr(), slot.data_ptr(), image.data_ptr(), n, *tail, a0, a1)
+            elif form == "mix":
+                rc = lib.dpwa_stream_mix(dst, 2, src, 2, nbytes, s, a0, a1)
+            else:
+                rc = lib.dpwa_average(code, param.data_ptr(), slot.data_ptr(), n, *tail, a0, a1)
+            if rc:
+                raise _lib.DpwaError(form, rc, lib.dpwa_last_error().decode())
+    torch.cuda.synchronize()
+    return {f: [1e3 * a.elapsed_time(b) for a, b in pairs[warmup:]] for f, pairs in ev.items()}, size.value
+
+
+def main_avg(args, lib, dev):
+    out = {"what": "the average straight from a packed image, write-through: pair = dpwa_unpack + dpwa_average from the "
+                   "first begin to the second end, fused = dpwa_average_packed, mix = dpwa_stream_mix(nr=2, nw=2) "
+                   "(over-counts the fused kernel's reads), avg = dpwa_average from a contiguous peer; interleaved "
+                   "launch by launch on the same buffers, all local and Infinity-Cache warm; no link is measured",
+           "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "launches": args.launches,
+           "repeats": args.repeats, "unpack_max_blocks": args.max_blocks,
+           "DPWA_PACKED_SCALES": os.environ.get("DPWA_PACKED_SCALES", ""), "sizes": {}}
+    for name, code, tdtype, n in SIZES:
+        reps = []
+        for _ in range(args.repeats):
+            us, image_bytes = compare_avg(lib, code, tdtype, n, args.launches, args.warmup, args.max_blocks, dev)
+            r = {k: stats(v) for k, v in us.items()}
+            for f in AVG_FORMS[:1] + AVG_FORMS[2:]:
+                r["fused_over_" + f] = round(r["fused"]["median_us"] / r[f]["median_us"], 3)
+            reps.append(r)
+            torch.cuda.empty_cache()
+        out["sizes"][name] = {"numel": n, "image_bytes": image_bytes, "repeats": reps}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({nm: [{f: r[f]["median_us"] for f in AVG_FORMS} for r in e["repeats"]]
+                      for nm, e in out["sizes"].items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=300)
@@ -64,11 +143,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--max-blocks", type=int, default=1 << 20, help="of dpwa_unpack (uncapped: the kernel alone)")
     ap.add_argument("--out", default="pack_cost.json")
+    ap.add_argument("--avg", action="store_true", help="measure dpwa_average_packed against what it replaces")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pack_cost.py needs a GPU")
     dev = torch.device("cuda", 0)
     lib = _lib.load()
+    if args.avg:
+        return main_avg(args, lib, dev)
     out = {"what": "dpwa_pack and a local dpwa_unpack against dpwa_stream_mix(nr=1, nw=1) over the payload's bytes on "
                    "the same buffers, interleaved launch by launch; dispatch begin/end events; no link is measured",
            "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "launches": args.launches,
