@@ -167,6 +167,9 @@ SIGNATURES = {
     "dpwa_pack": [_i32, _vp, _i64, _vp, _vp, _vp, _vp],
     "dpwa_unpack": [_i32, _vp, _i64, _vp, _int, _vp, _vp, _vp],
     "dpwa_average_packed": [_i32, _vp, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_average_pack": [_i32, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp,
+                          _vp],
+    "dpwa_pack_if": [_i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
     "dpwa_learner_consensus": [_vp, ctypes.POINTER(_i32), _int, _u64, _vp, _vp, _vp],
     "dpwa_learner_set_finite_check": [_vp, _int],
     "dpwa_learner_finite_skips": [_vp, ctypes.POINTER(_u64)],
@@ -220,6 +223,8 @@ SIGNATURES = {
     "dpwa_learner_relay_attach": [_vp, _int, _int, _vp, _i64],
     "dpwa_learner_relay_attach_fds": [_vp, _int, _int, _vp, _i64, _pint, _int, _i64],
     "dpwa_learner_pack_enable": [_vp],
+    "dpwa_learner_pack_counts": [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+    "dpwa_learner_pack_image": [_vp, _int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)],
     "dpwa_learner_pack_handle": [_vp, _vp, _i64],
     "dpwa_learner_pack_attach": [_vp, _int, _vp, _i64],
     "dpwa_learner_pack_attach_fds": [_vp, _int, _vp, _i64, _pint, _int, _i64],

@@ -62,6 +62,7 @@ constexpr int kBlock = 256;   // 4 waves of 64
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
@@ -2569,6 +2570,7 @@ hipError_t launch_consensus_finish(double *acc, dpwa_consensus_record *out, int6
 constexpr int kPackBlock = 4096;        // payload bytes per wave
 constexpr int kPackLane = 64;           // payload bytes per lane
 constexpr int kPackScales = kPackBlock / 256;   // groups, and scales, per block
+constexpr int kPackIfBlocks = 2048;     // k_pack_if's grid at most: 8 waves a CU
 static_assert(kPackBlock == kStreamBlock * kPackLane && kPackLane == 4 * 16, "a lane owns four 16-byte items");
 
 // Bit casts as builtins: the two kernels carry a target attribute, and a helper of another feature set (the
@@ -2636,14 +2638,15 @@ __device__ __forceinline__ uint32_t pack_q(float x, float inv)
     return (uint32_t)(int)r & 0xffu;
 }
 
+// One wave packs payload block `blk`.
 template <class Ops>
-DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pack(const char *__restrict__ payload, int64_t nbytes,
-                                                       char *__restrict__ q_plane, float *__restrict__ scales)
+DPWA_NO_PK_F32 __device__ __forceinline__ void pack_block(int64_t blk, const char *__restrict__ payload, int64_t nbytes,
+                                                          char *__restrict__ q_plane, float *__restrict__ scales)
 {
     constexpr int PER = Ops::PER;          // elements of a 16-byte item
     constexpr int QB = 4 * PER;            // q bytes of a lane
     const int lane = threadIdx.x;
-    const int64_t off = (int64_t)blockIdx.x * kPackBlock;
+    const int64_t off = blk * kPackBlock;
     const __amdgpu_buffer_rsrc_t r = span_rsrc<kPackBlock>(payload, off, nbytes & ~(int64_t)15);
     // the payload was just written by the publish or the average: the default cache policy
     u32x4 v[4];
@@ -2687,15 +2690,36 @@ DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pack(const char
         q[d] = normal ? w : 0u;
     }
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        q_plane + (int64_t)blockIdx.x * (kStreamBlock * QB), 0, kStreamBlock * QB, 0x00020000);
+        q_plane + blk * (kStreamBlock * QB), 0, kStreamBlock * QB, 0x00020000);
 #pragma unroll
     for (int d = 0; d < QB / 16; ++d)
         span_store(rq, lane * QB + d * 16, u32x4{q[4 * d], q[4 * d + 1], q[4 * d + 2], q[4 * d + 3]});
     if ((lane & 3) == 0) {   // the quad's scale: 16 per wave, 64 contiguous bytes
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            scales + (int64_t)blockIdx.x * kPackScales, 0, kPackScales * 4, 0x00020000);
+            scales + blk * kPackScales, 0, kPackScales * 4, 0x00020000);
         __builtin_amdgcn_raw_buffer_store_b32(pk_bits(scale), rs, lane, 0, kAuxStore);
     }
+}
+
+template <class Ops>
+DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pack(const char *__restrict__ payload, int64_t nbytes,
+                                                       char *__restrict__ q_plane, float *__restrict__ scales)
+{
+    pack_block<Ops>((int64_t)blockIdx.x, payload, nbytes, q_plane, scales);
+}
+
+// k_pack behind the reuse guard of a publish whose image the average wrote: the guard's fix-up, if there was
+// one, left that image stale, and its verdict stays on the device.  Every wave returns at once unless the
+// verdict word carries this publish's generation; a hit repacks the whole payload, a capped grid striding over
+// the blocks as k_pull_unpack's, and a miss moves no payload byte.
+template <class Ops>
+DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pack_if(const char *__restrict__ payload, int64_t nbytes,
+                                                          char *__restrict__ q_plane, float *__restrict__ scales,
+                                                          int64_t nblocks, const int32_t *__restrict__ dirty,
+                                                          int32_t gen)
+{
+    if (*dirty != gen) return;   // uniform
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) pack_block<Ops>(b, payload, nbytes, q_plane, scales);
 }
 
 // The mirror image, shaped like k_pull: at most max_blocks one-wave workgroups stride over the blocks.
@@ -2773,6 +2797,19 @@ hipError_t launch_pack(int32_t dtype, const void *payload, int64_t n, void *imag
     });
 }
 
+hipError_t launch_pack_if(int32_t dtype, const void *payload, int64_t n, void *image, const int32_t *dirty, int32_t gen,
+                          hipStream_t s, const LaunchTiming *timing)
+{
+    if (!is_float_dtype(dtype) || n < 0 || !payload || !image || !dirty || !aligned16(payload, image))
+        return hipErrorInvalidValue;
+    const int64_t blocks = pack_blocks(dtype, n);
+    return with_ops(dtype, [&](auto ops) {
+        return launch(k_pack_if<decltype(ops)>, dim3((uint32_t)std::min<int64_t>(blocks, kPackIfBlocks)),
+                      dim3(kStreamBlock), s, timing, payload, n * (int64_t)dtype_size(dtype), image,
+                      (char *)image + pack_scale_offset(dtype, n), blocks, dirty, gen);
+    });
+}
+
 hipError_t launch_pull_unpack(int32_t dtype, void *payload_out, int64_t n, const void *image, void *header_out,
                               const void *header, int max_blocks, bool remote, hipStream_t s,
                               const LaunchTiming *timing)
@@ -2817,12 +2854,148 @@ template <class Ops, class V> __device__ __forceinline__ uint16_t item_elem(Ops,
     return (uint16_t)(v[i / 2] >> (16 * (i & 1)));
 }
 
-template <class Ops, bool DUAL, bool OOP, int POLICY, bool USCALE>
-__global__ __launch_bounds__(kStreamBlock) void k_lerp_packed(typename Ops::V *__restrict__ param,
-                                                              const char *__restrict__ q_plane,
-                                                              const float *__restrict__ scales, int64_t n,
-                                                              LerpArgs args)
+// Where the peer's item of a span comes from (packed_span): a contiguous payload, loaded as k_lerp loads it, or
+// a packed image, dequantised as above.  load() issues the lane's loads, item() is the lane's 16-byte item and
+// ragged() element i of the payload's ragged item, for the lane that owns it.
+struct PayloadPeer {
+    const char *payload;
+    template <class Ops> struct Raw {
+        typename Ops::V q;
+    };
+    template <class Ops> __device__ __forceinline__ Raw<Ops> load(uint32_t span, int lane, int64_t vbytes) const
+    {
+        constexpr int SPAN = kStreamBlock * 16;
+        return Raw<Ops>{span_load<typename Ops::V>(span_rsrc<SPAN>(payload, (int64_t)span * SPAN, vbytes), lane * 16)};
+    }
+    template <class Ops> __device__ __forceinline__ typename Ops::V item(const Raw<Ops> &raw, int) const { return raw.q; }
+    template <class Ops>
+    __device__ __forceinline__ typename Ops::S ragged(typename Ops::V, int64_t vbytes, int i) const
+    {
+        return reinterpret_cast<const typename Ops::S *>(payload + vbytes)[i];
+    }
+};
+
+template <bool USCALE> struct ImagePeer {
+    const char *q_plane;
+    const float *scales;
+    template <class Ops> struct Raw {
+        uint32_t w[Ops::PER / 4];
+        f32x4 s4;      // USCALE: the wave's four scales
+        float scale;   // otherwise: the lane's own
+    };
+    template <class Ops> __device__ __forceinline__ Raw<Ops> load(uint32_t span, int lane, int64_t) const
+    {
+        constexpr int PER = Ops::PER;
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(q_plane + (int64_t)span * (kStreamBlock * PER)), 0, kStreamBlock * PER, 0x00020000);
+        Raw<Ops> raw{};
+        if constexpr (PER == 4) {
+            raw.w[0] = __builtin_amdgcn_raw_buffer_load_b32(rq, lane * 4, 0, kAuxStream);
+        } else {
+            const auto w2 = __builtin_amdgcn_raw_buffer_load_b64(rq, lane * 8, 0, kAuxStream);
+            raw.w[0] = w2[0], raw.w[1] = w2[1];
+        }
+        const float *const sc = scales + (int64_t)span * 4;
+        if constexpr (USCALE)
+            raw.s4 = *reinterpret_cast<const f32x4 *>(sc);   // uniform: the wave's one load
+        else
+            raw.scale = __builtin_nontemporal_load(sc + (lane >> 4));
+        return raw;
+    }
+    template <class Ops> __device__ __forceinline__ typename Ops::V item(const Raw<Ops> &raw, int lane) const
+    {
+        float scale = raw.scale;
+        if constexpr (USCALE) {
+            const int g = lane >> 4;
+            scale = g == 0 ? raw.s4.x : g == 1 ? raw.s4.y : g == 2 ? raw.s4.z : raw.s4.w;
+        }
+        float x[Ops::PER];
+#pragma unroll
+        for (int e = 0; e < Ops::PER; ++e) {
+            const int qv = (int)(raw.w[e / 4] << (24 - 8 * (e % 4))) >> 24;   // the signed byte
+            x[e] = (float)qv * scale;
+        }
+        return __builtin_bit_cast(typename Ops::V, pack_narrow(Ops{}, x));
+    }
+    template <class Ops> __device__ __forceinline__ typename Ops::S ragged(typename Ops::V q, int64_t, int i) const
+    {
+        return item_elem(Ops{}, q, i);
+    }
+};
+
+// Element i of an item that is being put together (the ragged item of an emitting span), from zeros.
+__device__ __forceinline__ void item_put(f32x4 &v, int i, float t) { v[i] = t; }
+__device__ __forceinline__ void item_put(u32x4 &v, int i, uint16_t t) { v[i / 2] |= (uint32_t)t << (16 * (i & 1)); }
+
+// The unsigned maximum over the 16 lanes of a DPP row, the same in all 16: lane ^ 1, lane ^ 2 (quad_perm), then
+// row_half_mirror (lane -> 7 - lane within each 8) and row_mirror (lane -> 15 - lane), which pair every quad
+// with the one it has not met.  Every lane of the wave is active where this is called.
+__device__ __forceinline__ uint32_t row_umax(uint32_t v)
 {
+    v = quad_umax(v);
+    uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);
+    v = v > o ? v : o;
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);
+    return v > o ? v : o;
+}
+
+// What an emitting span adds: the image bytes of the item this lane stored into the snapshot, by k_pack's
+// arithmetic to the bit (the codec of include/dpwa_hip.h).  A 256-byte group is the 16 lanes of a row, so amax
+// crosses lanes by row_umax alone: no LDS memory, no ds_bpermute, no barrier.  The lane's q bytes go to q-plane
+// offset 64 PER span + PER lane (one coalesced 256- or 512-byte store per wave, where ImagePeer reads) and lane 0
+// of each row stores the group's scale (scales[4 span ..], 16 bytes per wave); both `sc1`, as the snapshot's
+// stores: a peer reads them next.  `item` is zeros in the lanes past the payload's end.
+template <class Ops>
+__device__ __forceinline__ void emit_item(u32x4 item, uint32_t span, int lane, char *__restrict__ q_out,
+                                          float *__restrict__ scales_out)
+{
+    constexpr int PER = Ops::PER;
+    float x[PER];
+    pack_widen(Ops{}, item, x);
+    uint32_t m = 0;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+        const uint32_t a = pk_bits(x[e]) & 0x7fffffffu;
+        m = m > a ? m : a;
+    }
+    m = row_umax(m);
+    const bool nonfinite = m >= 0x7f800000u;
+    const float amax = pk_float(m);
+    const bool normal = !nonfinite && amax >= 0x1p-100f;
+    const float den = normal ? amax : 1.0f;
+    const float inv = 127.0f / den;                  // the two divisions, once per lane
+    const float scale = nonfinite ? pk_float(0x7fc00000u) : normal ? den / 127.0f : 0.0f;
+    uint32_t q[PER / 4];
+#pragma unroll
+    for (int d = 0; d < PER / 4; ++d) {
+        const uint32_t w = pack_q(x[4 * d], inv) | pack_q(x[4 * d + 1], inv) << 8 | pack_q(x[4 * d + 2], inv) << 16 |
+                           pack_q(x[4 * d + 3], inv) << 24;
+        q[d] = normal ? w : 0u;
+    }
+    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
+        q_out + (int64_t)span * (kStreamBlock * PER), 0, kStreamBlock * PER, 0x00020000);
+    if constexpr (PER == 4)
+        __builtin_amdgcn_raw_buffer_store_b32(q[0], rq, lane * 4, 0, kAuxStore);
+    else
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{q[0], q[1]}, rq, lane * 8, 0, kAuxStore);
+    if ((lane & 15) == 0) {
+        const __amdgpu_buffer_rsrc_t rs =
+            __builtin_amdgcn_make_buffer_rsrc(scales_out + (int64_t)span * 4, 0, 16, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b32(pk_bits(scale), rs, (lane >> 4) * 4, 0, kAuxStore);
+    }
+}
+
+// One 1-KiB span of the fused average whose ragged item stays with its lane: k_lerp_packed's body, with the
+// peer's item from `peer` (PayloadPeer / ImagePeer).  EMIT (with DUAL): the span also writes the image bytes of
+// what it stored into args.snap -- the averaged item, or in a no-op round the unchanged parameters -- so the
+// grid may reach past the payload (whole 4-KiB blocks): such spans have zero-range descriptors, touch neither
+// operand and emit q = 0 and scale = +0.0f.
+template <class Ops, bool DUAL, bool OOP, int POLICY, class Peer, bool EMIT>
+__device__ __forceinline__ void packed_span(typename Ops::V *__restrict__ param, const Peer &peer, int64_t n,
+                                            const LerpArgs &args, char *__restrict__ q_out,
+                                            float *__restrict__ scales_out)
+{
+    static_assert(!EMIT || DUAL, "the emitting forms are those that write a snapshot");
     using V = typename Ops::V;
     using S = typename Ops::S;
     using P = LerpPolicy<POLICY>;
@@ -2834,61 +3007,74 @@ __global__ __launch_bounds__(kStreamBlock) void k_lerp_packed(typename Ops::V *_
     const int64_t vbytes = nbytes & ~(int64_t)15;
     const int64_t span_off = (int64_t)blockIdx.x * SPAN;
     const __amdgpu_buffer_rsrc_t rp = span_rsrc<SPAN>(param, span_off, vbytes);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(q_plane + (int64_t)blockIdx.x * (kStreamBlock * PER)), 0, kStreamBlock * PER, 0x00020000);
     // issue this lane's loads before anything else
     const V p = span_load<V, P::param_load>(rp, lane_off);
-    uint32_t w[PER / 4];
-    if constexpr (PER == 4) {
-        w[0] = __builtin_amdgcn_raw_buffer_load_b32(rq, lane * 4, 0, kAuxStream);
-    } else {
-        const auto w2 = __builtin_amdgcn_raw_buffer_load_b64(rq, lane * 8, 0, kAuxStream);
-        w[0] = w2[0], w[1] = w2[1];
-    }
-    float scale;
-    const float *const sc = scales + (int64_t)blockIdx.x * 4;
-    if constexpr (USCALE) {
-        const f32x4 s4 = *reinterpret_cast<const f32x4 *>(sc);   // uniform: the wave's one load
-        const int g = lane >> 4;
-        scale = g == 0 ? s4.x : g == 1 ? s4.y : g == 2 ? s4.z : s4.w;
-    } else {
-        scale = __builtin_nontemporal_load(sc + (lane >> 4));
-    }
+    const auto raw = peer.template load<Ops>(blockIdx.x, lane, vbytes);
     const bool ragged = (nbytes & 15) && span_off + lane_off == vbytes;   // this lane owns the partial item
     [[maybe_unused]] S *const ps = reinterpret_cast<S *>(reinterpret_cast<char *>(param) + vbytes);
     [[maybe_unused]] S *const ss = reinterpret_cast<S *>(reinterpret_cast<char *>(args.snap) + vbytes);
     const int rag = (int)(nbytes & 15) / (int)sizeof(S);
+    [[maybe_unused]] V item{};   // EMIT: what this lane stored into the snapshot; zeros past the payload's end
+    [[maybe_unused]] const bool whole = span_off + lane_off < vbytes;
     float a, b;
     if (!lerp_coef<COEF_FUSED>(args, blockIdx.x == 0, a, b)) {
         if (DUAL) {   // no-op round; a write-through snapshot still gets the parameters
             span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, p);
+            if constexpr (EMIT) item = p;   // (zeros out of range)
             if (ragged) {
 #pragma unroll
                 for (int i = 0; i < PER - 1; ++i)
-                    if (i < rag) ss[i] = ps[i];
+                    if (i < rag) {
+                        const S t = ps[i];
+                        ss[i] = t;
+                        if constexpr (EMIT) item_put(item, i, t);
+                    }
             }
         }
-        return;
-    }
-    float x[PER];
+        if constexpr (!EMIT) return;
+    } else {
+        const V q = peer.template item<Ops>(raw, lane);
+        const V r = Ops::lerp(a, b, q, p);
+        if (!OOP) span_store<V, P::store>(rp, lane_off, r);
+        if (DUAL) span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, r);
+        if constexpr (EMIT)
+            if (whole) item = r;
+        if (ragged) {
 #pragma unroll
-    for (int e = 0; e < PER; ++e) {
-        const int qv = (int)(w[e / 4] << (24 - 8 * (e % 4))) >> 24;   // the signed byte
-        x[e] = (float)qv * scale;
+            for (int i = 0; i < PER - 1; ++i)
+                if (i < rag) {
+                    const S t = Ops::lerp_s(a, b, peer.template ragged<Ops>(q, vbytes, i), ps[i]);
+                    if (!OOP) ps[i] = t;
+                    if (DUAL) ss[i] = t;
+                    if constexpr (EMIT) item_put(item, i, t);
+                }
+        }
     }
-    const V q = __builtin_bit_cast(V, pack_narrow(Ops{}, x));
-    const V r = Ops::lerp(a, b, q, p);
-    if (!OOP) span_store<V, P::store>(rp, lane_off, r);
-    if (DUAL) span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, r);
-    if (ragged) {
-#pragma unroll
-        for (int i = 0; i < PER - 1; ++i)
-            if (i < rag) {
-                const S t = Ops::lerp_s(a, b, item_elem(Ops{}, q, i), ps[i]);
-                if (!OOP) ps[i] = t;
-                if (DUAL) ss[i] = t;
-            }
-    }
+    if constexpr (EMIT) emit_item<Ops>(__builtin_bit_cast(u32x4, item), blockIdx.x, lane, q_out, scales_out);
+}
+
+template <class Ops, bool DUAL, bool OOP, int POLICY, bool USCALE>
+__global__ __launch_bounds__(kStreamBlock) void k_lerp_packed(typename Ops::V *__restrict__ param,
+                                                              const char *__restrict__ q_plane,
+                                                              const float *__restrict__ scales, int64_t n,
+                                                              LerpArgs args)
+{
+    packed_span<Ops, DUAL, OOP, POLICY, ImagePeer<USCALE>, false>(param, ImagePeer<USCALE>{q_plane, scales}, n, args,
+                                                                  nullptr, nullptr);
+}
+
+// The emitting form of the fused write-through average (include/dpwa_hip.h dpwa_average_pack): one-wave
+// workgroups over 4 pack_blocks spans, so that both planes of the image are written whole.  The next
+// snapshot's image leaves from the registers that hold the snapshot: a round moves (3 + 0.27) n s bytes (fp32;
+// 3 + 0.52 for a 16-bit type) plus the peer operand, in one launch, where the average followed by k_pack moved
+// (3 + 1.27) n s in two.  There is no resident (OOP) form: resident parameters live in the slot and the step
+// that follows the average writes them there, so their image can only be taken at the publish.
+template <class Ops, int POLICY, class Peer>
+__global__ __launch_bounds__(kStreamBlock) void k_lerp_emit(typename Ops::V *__restrict__ param, Peer peer, int64_t n,
+                                                            LerpArgs args, char *__restrict__ q_out,
+                                                            float *__restrict__ scales_out)
+{
+    packed_span<Ops, true, false, POLICY, Peer, true>(param, peer, n, args, q_out, scales_out);
 }
 
 // How the wave gets its four scales (k_lerp_packed): the wave's one uniform load, or with
@@ -2934,6 +3120,52 @@ hipError_t launch_average_packed(int32_t dtype, void *param, int64_t n, const vo
             });
         };
         return packed_scales_uniform() ? forms(std::true_type{}) : forms(std::false_type{});
+    });
+}
+
+// A write-through round of a pack-enabled learner emits the next snapshot's image from its average; DPWA_PACK_FUSED=0 keeps the average and the publish's k_pack as two launches (A/B runs).
+// profiles/pack_emit_cost.json has both, interleaved on the same buffers.
+bool pack_fused()
+{
+    static const bool on = env_knob("DPWA_PACK_FUSED", 1, [](const char *e) {
+        return strcmp(e, "1") == 0 ? 1 : strcmp(e, "0") == 0 ? 0 : kNoValue;
+    }) != 0;
+    return on;
+}
+
+hipError_t launch_average_emit(int32_t dtype, void *param, int64_t n, const void *peer, const void *peer_image,
+                               const FusedArgs &fa, void *snap, void *image_out, hipStream_t s,
+                               const LaunchTiming *timing)
+{
+    if (!is_float_dtype(dtype) || n < 0 || (!peer) == (!peer_image) || !param || !snap || !image_out ||
+        snap == param || !aligned16(param, peer, peer_image) || !aligned16(snap, image_out))
+        return hipErrorInvalidValue;
+    const int64_t nbytes = n * (int64_t)dtype_size(dtype);
+    const int64_t grid = 4 * pack_blocks(dtype, n);   // both planes whole
+    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+    LerpArgs args{};
+    args.fused = fa;
+    args.snap = snap;
+    const int64_t scale_off = pack_scale_offset(dtype, n);
+    char *const q_out = (char *)image_out;
+    float *const scales_out = (float *)(q_out + scale_off);
+    return with_ops(dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        using V = typename Ops::V;
+        const auto from = [&](auto src) {
+            using Peer = decltype(src);
+            const auto run = [&](void (*kernel)(V *, Peer, int64_t, LerpArgs, char *, float *)) {
+                return launch(kernel, dim3((uint32_t)grid), dim3(kStreamBlock), s, timing, param, src, n, args, q_out,
+                              scales_out);
+            };
+            // (the policies of launch_average_packed)
+            return BySizePolicies::with(lerp_policy(nbytes), [&](auto policy) {
+                return run(k_lerp_emit<Ops, decltype(policy)::value, Peer>);
+            });
+        };
+        if (peer) return from(PayloadPeer{(const char *)peer});
+        const char *const q_plane = (const char *)peer_image;
+        return from(ImagePeer<true>{q_plane, (const float *)(q_plane + scale_off)});
     });
 }
 

@@ -285,6 +285,23 @@ hipError_t launch_pull_unpack(int32_t dtype, void *payload_out, int64_t n, const
 hipError_t launch_average_packed(int32_t dtype, void *param, int64_t n, const void *image, const FusedArgs &fa,
                                  void *snap, hipStream_t s, const LaunchTiming *timing = nullptr, bool oop = false);
 
+// The fused average that also emits the image of the snapshot it writes (k_lerp_emit): launch_average (`peer`,
+// a contiguous payload) or launch_average_packed (`peer_image`) -- exactly one of the two -- writing through to
+// `snap`, and launch_pack(dtype, snap, n, image_out) in the same launch: both planes of image_out whole and no
+// other byte, the no-op round included (the image of the unchanged parameters).  No resident form: a resident
+// learner's step writes the slot after the average, so its image is taken at the publish.  The bits of all outputs are those of the two launches.  hipErrorInvalidValue, nothing queued:
+// what those refuse, a null `param`, `snap` or `image_out`, `snap` == `param`, both or neither peer operand,
+// any pointer not 16-B aligned, more than 2^31 - 1 spans.
+hipError_t launch_average_emit(int32_t dtype, void *param, int64_t n, const void *peer, const void *peer_image,
+                               const FusedArgs &fa, void *snap, void *image_out, hipStream_t s,
+                               const LaunchTiming *timing = nullptr);
+// launch_pack by a grid whose every wave returns at once unless *dirty == gen (device memory: the reuse
+// guard's verdict word and its generation of this publish).
+hipError_t launch_pack_if(int32_t dtype, const void *payload, int64_t n, void *image, const int32_t *dirty, int32_t gen,
+                          hipStream_t s, const LaunchTiming *timing = nullptr);
+// DPWA_PACK_FUSED: does a pack-enabled learner's write-through average emit the image (default)?
+bool pack_fused();
+
 // What the stateless entry points (learner.cpp, distance.cpp) share; `fn` names the entry in messages.
 // The caller's begin/end events as a launch's timing argument: NULL when none were given.
 struct CallerTiming {

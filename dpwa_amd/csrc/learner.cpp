@@ -429,6 +429,7 @@ struct dpwa_learner {
     StreamMark written_through;
     const void *wt_flat = nullptr;
     bool wt_header = false;             // the write-through average also wrote the next header
+    bool wt_image = false;              // ... and the slot's packed image (k_lerp_emit; pack_on)
     bool header_on_publish = false;     // never write the next header ahead (served to wire peers)
     bool reuse_guard = false;           // check a header-only publish's parameters on the device
     // resident parameters (dpwa_learner_set_resident): they live in slot res_slot's payload and
@@ -457,9 +458,10 @@ struct dpwa_learner {
     bool relay_deferred = false;
     RelayArgs relay_saved{};
     int relay_saved_pick = -1, relay_saved_blocks = 0;
-    // packed snapshots (dpwa_learner_pack_enable): image k mirrors slot k, packed by every publish and
-    // pulled in place of the payload under DPWA_PULL_PACKED, see kernels.hip
+    // packed snapshots (dpwa_learner_pack_enable): image k mirrors slot k, packed by every publish or by the
+    // average that wrote the slot, and pulled in place of the payload under DPWA_PULL_PACKED, see kernels.hip
     bool pack_on = false;
+    uint64_t packs_by_publish = 0, packs_by_average = 0;   // images written by k_pack / by k_lerp_emit
     bool pull_by_kernel = false;             // DPWA_PULL_PACKED_AVG with a block cap: the image moves by launch_pull
     int64_t pack_stride = 0;                 // bytes from image 0 to image 1
     DevMem pack_mem;                         // 2 images, IPC-exported
@@ -736,12 +738,20 @@ static int wait_slot_readers(dpwa_learner *l, int k, hipStream_t s)
 
 static int relocate_impl(dpwa_learner *l, hipStream_t s);
 
-// `flat` is in the next publish's slot, written there on `s` (`header`: with its header and clock)
-static void set_written_through(dpwa_learner *l, const void *flat, bool header, hipStream_t s)
+// `flat` is in the next publish's slot, written there on `s` (`header`: with its header and clock; `image`: with
+// the slot's packed image, by the same launch)
+static void set_written_through(dpwa_learner *l, const void *flat, bool header, hipStream_t s, bool image = false)
 {
     l->written_through.note(s);
     l->wt_flat = flat;
     l->wt_header = header;
+    l->wt_image = image;
+}
+
+static void clear_written_through(dpwa_learner *l)
+{
+    l->written_through.clear();
+    l->wt_image = false;
 }
 
 // ---------------------------------------------------------------- window guard (resident)
@@ -858,11 +868,20 @@ static int publish_impl(dpwa_learner *l, const void *flat, double loss, const do
     }
     if (l->pack_on) {
         // the packed image of this snapshot, whichever way its payload got into the slot: behind the copy,
-        // the write-through average and the reuse guard's fix-up on `s`, ahead of the one system release
-        HIP_TRY(launch_pack(l->dtype, slot + kPayloadOff, l->n, l->pack_mem.ptr + (size_t)k * (size_t)l->pack_stride, s));
+        // the write-through average and the reuse guard's fix-up on `s`, ahead of the one system release.
+        // The average that wrote the slot may have written the image with it (k_lerp_emit); then only the
+        // guard's fix-up can have left it stale, and its verdict is on the device: k_pack_if reads it there.
+        char *const image = l->pack_mem.ptr + (size_t)k * (size_t)l->pack_stride;
+        if (!(header_only && l->wt_image)) {
+            HIP_TRY(launch_pack(l->dtype, slot + kPayloadOff, l->n, image, s));
+            l->packs_by_publish++;
+        } else if (l->reuse_guard) {   // (never resident: average_prepare)
+            HIP_TRY(launch_pack_if(l->dtype, slot + kPayloadOff, l->n, image, &l->ctl->guard_dirty,
+                                   (int32_t)(l->version + 1), s));
+        }
         if (l->exported) HIP_TRY(launch_release_system(s));
     }
-    l->written_through.clear();
+    clear_written_through(l);
     l->wt_header = false;
     if (l->resident && l->reuse_guard) {   // the last window's check; this window's samples
         if (int rc = window_roll(l, (const char *)flat, s)) return rc;
@@ -1206,7 +1225,7 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     });
     if (rc) return rc;
     HIP_TRY(l->fetch.note_consumed(s));
-    l->written_through.clear();
+    clear_written_through(l);
     l->fetch.finish();
     return DPWA_OK;
 }
@@ -1223,6 +1242,7 @@ struct AvgPlan {
     bool relay = false;           // the relay's phase 2 fused into this average (k_lerp_relay)
     bool write_through = false;
     bool oop = false;             // resident: the result goes to `snap` only
+    char *emit = nullptr;         // the snapshot's packed image, written by this launch too (k_lerp_emit)
     int snap_slot = -1;
 };
 
@@ -1270,13 +1290,18 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
         // a payload that is still packed: k_lerp_packed reads the landing image itself, unless something of this
         // round needs the contiguous payload (a measurement, the non-finite check, a batched dispatch, the
         // unaligned form), which expands it first
-        if (l->fetch.source().packed && alone && !l->measure.whole() && !l->measure.param() && !l->finite_check &&
-            aligned16(flat, p.snap)) {
+        const bool plain = alone && !l->measure.whole() && !l->measure.param() && !l->finite_check && aligned16(flat, p.snap);
+        if (l->fetch.source().packed && plain) {
             p.image = l->fetch.source().packed;
         } else {
             if (int rc = pack_materialize(l, s)) return rc;
             p.peer = l->fetch.source().ptr + kPayloadOff;
         }
+        // a round that writes slot k of a pack-enabled learner writes image k in the same launch, under the
+        // conditions that leave the launch to k_lerp / k_lerp_packed (never a segmented payload: pack_enable)
+        // and never a resident learner: its step writes the slot after the average, behind the image's back
+        if (l->pack_on && write_through && !l->resident && plain && aligned16(p.peer) && pack_fused())
+            p.emit = l->pack_mem.ptr + (size_t)p.snap_slot * (size_t)l->pack_stride;
     }
     HIP_TRY(l->fetch.wait_landed(s));
     return DPWA_OK;
@@ -1299,8 +1324,9 @@ static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
     l->timing_armed = false;
     l->cur = (l->cur + 1) & 3;
     if (p.oop) l->res_slot = p.snap_slot;   // the parameters moved into the next publish's slot
-    set_written_through(l, p.oop ? p.snap : p.flat, p.fa.next_header != nullptr, s);
-    if (!p.write_through) l->written_through.clear();
+    set_written_through(l, p.oop ? p.snap : p.flat, p.fa.next_header != nullptr, s, p.emit != nullptr);
+    if (!p.write_through) clear_written_through(l);
+    if (p.emit) l->packs_by_average++;
     l->fetch.finish();
     return DPWA_OK;
 }
@@ -1319,6 +1345,8 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
         if (p.relay) {   // (never a segmented payload: relay_phase2 refuses)
             HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
                                          timing, p.oop));
+        } else if (p.emit) {   // (as p.image; p.peer or p.image, whichever average_prepare chose)
+            HIP_TRY(launch_average_emit(l->dtype, p.flat, l->n, p.peer, p.image, p.fa, p.snap, p.emit, s, timing));
         } else if (p.image) {   // (never a segmented payload or a measuring learner: average_prepare)
             HIP_TRY(launch_average_packed(l->dtype, p.flat, l->n, p.image, p.fa, p.snap, s, timing, p.oop));
         } else {
@@ -1834,6 +1862,24 @@ int dpwa_learner_pack_enable(dpwa_learner *l)
     l->pack_mem = std::move(m);
     l->pack_stride = stride;
     l->pack_on = true;
+    return DPWA_OK;
+}
+
+int dpwa_learner_pack_counts(dpwa_learner *l, uint64_t *by_publish, uint64_t *by_average)
+{
+    if (!l || !by_publish || !by_average) return set_error(DPWA_ERR_ARG, "dpwa_learner_pack_counts: NULL argument");
+    *by_publish = l->packs_by_publish;
+    *by_average = l->packs_by_average;
+    return DPWA_OK;
+}
+
+int dpwa_learner_pack_image(dpwa_learner *l, int k, const void **image, int64_t *bytes)
+{
+    if (!l || !image || !bytes || k < 0 || k > 1)
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_pack_image: NULL argument or an image other than 0 and 1");
+    if (!l->pack_on) return set_error(DPWA_ERR_STATE, "dpwa_learner_pack_image: packed snapshots not enabled");
+    *image = l->pack_mem.ptr + (size_t)k * (size_t)l->pack_stride;
+    *bytes = pack_image_bytes(l->dtype, l->n);
     return DPWA_OK;
 }
 

@@ -1,6 +1,7 @@
 // pack.cpp -- packed snapshots without a learner: the stateless entry points of include/dpwa_hip.h
-// (dpwa_pack_bytes, dpwa_pack, dpwa_unpack).  A learner's images, packed at every publish and pulled in
-// place of the payload (DPWA_PULL_PACKED), are in learner.cpp, beside the slots they mirror.
+// (dpwa_pack_bytes, dpwa_pack, dpwa_pack_if, dpwa_unpack, dpwa_average_packed, dpwa_average_pack).  A learner's
+// images, packed at a publish or by the average ahead of it and pulled in place of the payload
+// (DPWA_PULL_PACKED), are in learner.cpp, beside the slots they mirror.
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -67,6 +68,44 @@ int dpwa_average_packed(int32_t dtype, void *param, const void *header, const vo
     const FusedArgs fa = stateless_args(cfg, clock_dev, header, loss, coef_dev);
     HIP_TRY(launch_average_packed(dtype, param, n, image, fa, snap_payload, (hipStream_t)stream,
                                   CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
+// dpwa_average (peer_payload) or dpwa_average_packed (peer_image) writing through to snap_payload, and dpwa_pack of
+// that snapshot into image_out, in one launch (k_lerp_emit).
+int dpwa_average_pack(int32_t dtype, void *param, const void *header, const void *peer_payload, const void *peer_image,
+                      int64_t n, const dpwa_interp *cfg, double *clock_dev, double loss, dpwa_coef *coef_dev,
+                      void *snap_payload, void *image_out, dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_average_pack: %s", why);
+    if (!cfg || !clock_dev || !coef_dev || !header || !param || !snap_payload || !image_out ||
+        (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: a NULL pointer, or one event without the other");
+    if ((!peer_payload) == (!peer_image))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: exactly one of peer_payload and peer_image");
+    if (snap_payload == param)
+        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: snap_payload is the parameters");
+    if (int rc = check_method(cfg, "dpwa_average_pack")) return rc;
+    if (!aligned16(param, peer_payload, peer_image) || !aligned16(snap_payload, image_out))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: the parameters, the peer's payload or image, the snapshot payload "
+                                       "or the image is not 16-byte aligned (there is no unaligned form)");
+    const FusedArgs fa = stateless_args(cfg, clock_dev, header, loss, coef_dev);
+    HIP_TRY(launch_average_emit(dtype, param, n, peer_payload, peer_image, fa, snap_payload, image_out,
+                                (hipStream_t)stream, CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
+// dpwa_pack behind a device-side condition (k_pack_if): the form a learner's reuse guard runs.
+int dpwa_pack_if(int32_t dtype, const void *payload, int64_t n, void *image, const int32_t *dirty_dev, int32_t gen,
+                 dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_pack_if: %s", why);
+    if (!payload || !image || !dirty_dev || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_pack_if: a NULL pointer, or one event without the other");
+    if (!aligned16(payload, image))
+        return set_error(DPWA_ERR_ARG, "dpwa_pack_if: the payload or the image is not 16-byte aligned (there is no unaligned form)");
+    HIP_TRY(launch_pack_if(dtype, payload, n, image, dirty_dev, gen, (hipStream_t)stream,
+                           CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 

@@ -48,7 +48,9 @@ extern "C" {
  * which = 2 of dpwa_learner_export_fds) -- dpwa_pack_bytes, dpwa_pack, dpwa_unpack, dpwa_learner_pack_enable,
  * dpwa_learner_pack_handle, dpwa_learner_pack_attach, dpwa_learner_pack_attach_fds.
  * Still 11, by additions only: the average straight from a packed image -- dpwa_average_packed, and
- * DPWA_PULL_PACKED_AVG, a new mode of dpwa_learner_set_pull (which alone accepts max_blocks = 0). */
+ * DPWA_PULL_PACKED_AVG, a new mode of dpwa_learner_set_pull (which alone accepts max_blocks = 0).
+ * Still 11, by additions only: the average that packs the snapshot it writes -- dpwa_average_pack, dpwa_pack_if,
+ * dpwa_learner_pack_counts, dpwa_learner_pack_image. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -368,6 +370,28 @@ int dpwa_unpack(int32_t dtype, const void *image, int64_t n, void *payload_out, 
 int dpwa_average_packed(int32_t dtype, void *param, const void *header, const void *image, int64_t n,
                         const dpwa_interp *cfg, double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload,
                         dpwa_stream_t stream, void *start_event, void *stop_event);
+/* The write-through average that also packs the snapshot it writes: dpwa_average (peer_payload: the payload of
+ * the peer's snapshot) or dpwa_average_packed (peer_image: its packed image) -- exactly one of the two is
+ * non-NULL -- with snap_payload required, and dpwa_pack of that snapshot into image_out, in one launch
+ * (k_lerp_emit).  Every lane holds the item it stores into the snapshot and the wave derives that item's
+ * image bytes from it by the rule above, so the snapshot is not read back:
+ *   - param, snap_payload, *coef_dev and the clock end up, to the bit, as dpwa_average (peer_payload) or
+ *     dpwa_average_packed (peer_image) leaves them;
+ *   - image_out ends up, byte for byte, as dpwa_pack(dtype, snap_payload, n, image_out) run afterwards would
+ *     leave it: both planes whole (B blocks each) and no other byte.  The no-op (ZeroDivision) round included:
+ *     the snapshot receives the unchanged parameters and the image is theirs.
+ * Nothing behind the payload's last byte is written, in param or in snap_payload.  DPWA_ERR_ARG, nothing queued:
+ * what dpwa_average_packed and dpwa_pack refuse -- DPWA_MIXED or an unknown dtype, n < 0, a NULL pointer, an
+ * unknown method, a pointer that is not 16-B aligned (there is no unaligned form), one event without the other
+ * -- and both or neither of peer_payload and peer_image, and snap_payload == param.
+ * dpwa_pack_if is dpwa_pack behind a condition on the device: every wave returns at once unless
+ * *dirty_dev == gen when it runs (a miss moves no payload byte; a hit packs the whole payload).  A learner
+ * runs it behind its reuse guard, whose verdict never reaches the host (dpwa_learner_pack_enable). */
+int dpwa_average_pack(int32_t dtype, void *param, const void *header, const void *peer_payload, const void *peer_image,
+                      int64_t n, const dpwa_interp *cfg, double *clock_dev, double loss, dpwa_coef *coef_dev,
+                      void *snap_payload, void *image_out, dpwa_stream_t stream, void *start_event, void *stop_event);
+int dpwa_pack_if(int32_t dtype, const void *payload, int64_t n, void *image, const int32_t *dirty_dev, int32_t gen,
+                 dpwa_stream_t stream, void *start_event, void *stop_event);
 
 /* The per-parameter distance (extension, opt-in): the two sums above for every parameter tensor t of
  * the model, over that tensor's own elements only -- dist2_t = sum (double(q_i) - double(p_i))^2 and
@@ -778,13 +802,28 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
 /* Packed snapshots of a learner (the codec: "packed snapshots" above).  pack_enable allocates two
  * images, image k beside slot k, zeroed once; from then on every publish -- the full one, the
  * header-only one behind a write-through average, a resident learner's -- packs slot (version - 1) % 2
- * into image (version - 1) % 2 on the publish's stream, ahead of its system-scope release.  The image
- * of publish v is next rewritten by publish v + 2, exactly as the slot is, so whatever keeps a peer's
- * read of the slot ahead of that publish (the lock-step round's barrier) covers the image.
+ * into image (version - 1) % 2 on the publish's stream, ahead of its system-scope release, or the average
+ * that wrote the slot did: a write-through average that runs alone (not batched, not measuring a distance,
+ * not skipping non-finite peers, not the relay's, parameters 16-B aligned) writes image k in the launch that
+ * writes slot k (dpwa_average_pack's kernel), and the header-only publish behind it launches no k_pack.
+ * Every other publish packs as before: a full copy, a round that did not average, a measured or batched
+ * round, a relocation, and every publish of a resident learner -- its parameters are the slot, the step that
+ * follows the average writes them there, and only the publish sees what peers will read.  Where the reuse
+ * guard runs (dpwa_learner_set_reuse_guard) its
+ * fix-up may change the slot on the device with no verdict on the host, so that publish runs dpwa_pack_if on
+ * the guard's verdict word: a repack of the whole payload on a hit, an early exit otherwise.
+ * DPWA_PACK_FUSED=0 (read once) keeps the pack at every publish.  The image of publish v is next rewritten by
+ * publish v + 2 or by the average ahead of it that rewrites the slot, exactly when the slot is, so whatever
+ * keeps a peer's read of the slot ahead of that write (the lock-step round's barrier) covers the image.
+ * pack_counts: how many images the publishes packed (k_pack) and how many the averages did (host counters;
+ * dpwa_pack_if is counted by neither).  pack_image: image k (0 or 1) as device memory of this learner and
+ * its size, dpwa_pack_bytes(dtype, n); read-only, for tests and A/B runs.
  * pack_handle / pack_attach / pack_attach_fds export the images and map peer `peer_id`'s (whose slots are
  * IPC-attached already), as the relay buffer's calls do; fds come from export_fds with which = 2.
  * DPWA_ERR_ARG: a DPWA_MIXED learner, images of another n or dtype.  DPWA_ERR_STATE: enabled twice. */
 int dpwa_learner_pack_enable(dpwa_learner *l);
+int dpwa_learner_pack_counts(dpwa_learner *l, uint64_t *by_publish, uint64_t *by_average);
+int dpwa_learner_pack_image(dpwa_learner *l, int k, const void **image, int64_t *bytes);
 int dpwa_learner_pack_handle(dpwa_learner *l, void *handle_out, int64_t handle_len);
 int dpwa_learner_pack_attach(dpwa_learner *l, int peer_id, const void *pack_handle, int64_t handle_len);
 int dpwa_learner_pack_attach_fds(dpwa_learner *l, int peer_id, const void *pack_handle, int64_t handle_len,

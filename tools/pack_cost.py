@@ -13,6 +13,12 @@ write-through: "pair" dpwa_unpack + dpwa_average back to back, from the first di
 nearest mix its arguments express -- it reads 2 n s where the fused kernel reads (1 + 1/s + 1/64) n s, so it
 over-counts reads; "avg" the plain dpwa_average, whose peer is contiguous.  Every buffer is local and, at these
 sizes, Infinity-Cache warm from the launch before.
+
+--emit measures the write-through average that packs its snapshot (profiles/pack_emit_cost.json), for both peer
+sources ("payload": a contiguous peer, "image": a packed one) and both cold (a 1-GiB fill between the timed forms)
+and cache-warm: "pair" dpwa_average / dpwa_average_packed + dpwa_pack of the snapshot, from the first dispatch's
+begin to the second's end (the two launches dpwa_average_pack replaces); "fused" dpwa_average_pack; "avg" the plain
+write-through average alone; "pack_if" dpwa_pack_if on a miss (what a guarded publish still launches).
 """
 import argparse
 import ctypes
@@ -136,6 +142,89 @@ def main_avg(args, lib, dev):
                       for nm, e in out["sizes"].items()}))
 
 
+EMIT_FORMS = ("pair", "fused", "avg", "pack_if")
+
+
+def compare_emit(lib, code, tdtype, n, launches, warmup, dev, source, cold):
+    """One repeat of the --emit forms, interleaved; constant factor 0.5 on the same parameters throughout."""
+    esize = torch.empty((), dtype=tdtype).element_size()
+    off = _lib.SLOT_PAYLOAD_OFFSET // esize
+    param, snap = torch.empty(n, device=dev, dtype=tdtype).normal_(), torch.empty(n, device=dev, dtype=tdtype)
+    slot = torch.zeros(off + n, device=dev, dtype=tdtype)          # a zero header (clock 0), then the peer's payload
+    slot[off:].normal_()
+    size = ctypes.c_int64()
+    _lib.call("dpwa_pack_bytes", code, n, ctypes.byref(size))
+    peer_image, out_image = (torch.zeros(size.value, dtype=torch.uint8, device=dev) for _ in range(2))
+    s = _lib.stream_handle(None)
+    _lib.call("dpwa_pack", code, slot[off:].data_ptr(), n, peer_image.data_ptr(), s, None, None)
+    clock = torch.zeros(2, dtype=torch.float64, device=dev)
+    coef = torch.zeros(32, dtype=torch.uint8, device=dev)
+    dirty = torch.zeros(1, dtype=torch.int32, device=dev)          # never this publish's generation: a miss
+    cfg = _lib.Interp(_lib.INTERP_CONSTANT, 0, 0.5, 0.0)
+    tail = (ctypes.byref(cfg), clock.data_ptr(), 1.0, coef.data_ptr(), snap.data_ptr())
+    scrub = torch.empty(1 << 28, dtype=torch.float32, device=dev) if cold else None
+    payload, image = slot[off:].data_ptr(), peer_image.data_ptr()
+
+    def average(a0, a1):
+        if source == "payload":
+            return lib.dpwa_average(code, param.data_ptr(), slot.data_ptr(), n, *tail, s, a0, a1)
+        return lib.dpwa_average_packed(code, param.data_ptr(), slot.data_ptr(), image, n, *tail, s, a0, a1)
+
+    total = warmup + launches
+    ev = {f: events(total) for f in EMIT_FORMS}
+    mid = events(total)
+    torch.cuda.synchronize()
+    for i in range(total):
+        k = i % len(EMIT_FORMS)
+        for form in EMIT_FORMS[k:] + EMIT_FORMS[:k]:
+            if cold:
+                scrub.fill_(float(i))
+            a0, a1 = (e.cuda_event for e in ev[form][i])
+            if form == "pair":
+                m0, m1 = (e.cuda_event for e in mid[i])
+                rc = average(a0, m0) or lib.dpwa_pack(code, snap.data_ptr(), n, out_image.data_ptr(), s, m1, a1)
+            elif form == "fused":
+                rc = lib.dpwa_average_pack(code, param.data_ptr(), slot.data_ptr(), payload if source == "payload" else None,
+                                           None if source == "payload" else image, n, *tail, out_image.data_ptr(), s, a0, a1)
+            elif form == "avg":
+                rc = average(a0, a1)
+            else:
+                rc = lib.dpwa_pack_if(code, snap.data_ptr(), n, out_image.data_ptr(), dirty.data_ptr(), 1, s, a0, a1)
+            if rc:
+                raise _lib.DpwaError(form, rc, lib.dpwa_last_error().decode())
+    torch.cuda.synchronize()
+    return {f: [1e3 * a.elapsed_time(b) for a, b in pairs[warmup:]] for f, pairs in ev.items()}
+
+
+def main_emit(args, lib, dev):
+    out = {"what": "the write-through average that packs its snapshot: pair = dpwa_average (source payload) or "
+                   "dpwa_average_packed (source image) + dpwa_pack of the snapshot, from the first begin to the second "
+                   "end; fused = dpwa_average_pack; avg = that average alone; pack_if = dpwa_pack_if on a miss; "
+                   "interleaved launch by launch on the same local buffers, warm (Infinity-Cache warm from the launch "
+                   "before) and cold (a 1-GiB fill before every timed form); no link is measured",
+           "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "launches": args.launches,
+           "repeats": args.repeats, "sizes": {}}
+    for name, code, tdtype, n in SIZES:
+        entry = {"numel": n}
+        for source in ("payload", "image"):
+            for cold in (False, True):
+                reps = []
+                for _ in range(args.repeats):
+                    us = compare_emit(lib, code, tdtype, n, args.launches, args.warmup, dev, source, cold)
+                    reps.append({k: stats(v) for k, v in us.items()})
+                    torch.cuda.empty_cache()
+                pair = [r["pair"]["median_us"] for r in reps]
+                entry["%s_%s" % (source, "cold" if cold else "warm")] = {
+                    "repeats": reps, "pair_median_spread_us": round(max(pair) - min(pair), 3)}
+        out["sizes"][name] = entry
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({nm: {k: [{f: r[f]["median_us"] for f in EMIT_FORMS} for r in v["repeats"]]
+                           for k, v in e.items() if k != "numel"} for nm, e in out["sizes"].items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=300)
@@ -144,6 +233,7 @@ def main():
     ap.add_argument("--max-blocks", type=int, default=1 << 20, help="of dpwa_unpack (uncapped: the kernel alone)")
     ap.add_argument("--out", default="pack_cost.json")
     ap.add_argument("--avg", action="store_true", help="measure dpwa_average_packed against what it replaces")
+    ap.add_argument("--emit", action="store_true", help="measure dpwa_average_pack against what it replaces")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pack_cost.py needs a GPU")
@@ -151,6 +241,8 @@ def main():
     lib = _lib.load()
     if args.avg:
         return main_avg(args, lib, dev)
+    if args.emit:
+        return main_emit(args, lib, dev)
     out = {"what": "dpwa_pack and a local dpwa_unpack against dpwa_stream_mix(nr=1, nw=1) over the payload's bytes on "
                    "the same buffers, interleaved launch by launch; dispatch begin/end events; no link is measured",
            "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "launches": args.launches,
