@@ -83,6 +83,12 @@ class Distance(ctypes.Structure):
                 ("n", ctypes.c_int64)]
 
 
+class HealRecord(ctypes.Structure):
+    """dpwa_heal_record: what the guarded averaging kernels have healed and refused so far."""
+    _fields_ = [("healed", ctypes.c_uint64), ("refused", ctypes.c_uint64), ("rounds", ctypes.c_uint64),
+                ("clock", ctypes.c_double)]
+
+
 class ParamRange(ctypes.Structure):
     """dpwa_param_range: where one parameter tensor lies in the payload."""
     _fields_ = [("byte_offset", ctypes.c_int64), ("byte_length", ctypes.c_int64), ("dtype", ctypes.c_int32),
@@ -174,6 +180,12 @@ SIGNATURES = {
     "dpwa_learner_set_finite_check": [_vp, _int],
     "dpwa_learner_finite_skips": [_vp, ctypes.POINTER(_u64)],
     "dpwa_node_set_finite_check": [_vp, _int],
+    "dpwa_average_guarded": [_i32, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_average_guarded_mixed": [ctypes.POINTER(Layout), _vp, _vp, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp,
+                                   _vp, _vp],
+    "dpwa_learner_set_heal": [_vp, _int],
+    "dpwa_learner_heal_record": [_vp, ctypes.POINTER(HealRecord)],
+    "dpwa_node_set_heal": [_vp, _int],
     "dpwa_learner_set_distance": [_vp, _int],
     "dpwa_learner_distance": [_vp, ctypes.POINTER(_vp)],
     "dpwa_layout_digest": [ctypes.POINTER(Layout), _i64, ctypes.POINTER(ctypes.c_uint32)],

@@ -112,7 +112,7 @@ class DpwaPyTorchAdapter:
 
     def __init__(self, net, name, config_file, write_through=True, transport="device", reuse_guard=True,
                  resident=False, track_distance=False, distance_every=1, skip_nonfinite_peer=False,
-                 **connection_kwargs):
+                 heal_nonfinite=False, **connection_kwargs):
         """transport: "device" (peers are learners of this process or of the torch.distributed
         job, pulled from HBM/over xGMI) or "wire" (peers are reached over TCP at the YAML's
         host/port with the reference's protocol -- e.g. reference CPU nodes; dpwa_amd/bridge.py).
@@ -129,10 +129,17 @@ class DpwaPyTorchAdapter:
 
         skip_nonfinite_peer (extension, off by default): a round whose fetched peer snapshot holds a NaN
         or an inf averages nothing and is counted (``nonfinite_skips``) instead of spreading it into
-        this model; see ``DpwaConnection``.  One more read of the peer's snapshot per round."""
+        this model; see ``DpwaConnection``.  One more read of the peer's snapshot per round.
+
+        heal_nonfinite (extension, off by default, device transport): the averaging kernel never takes a NaN
+        or an inf from the peer and replaces a NaN or an inf of this model with the peer's finite element,
+        counting both (``nonfinite_elements``); see ``DpwaConnection``.  No extra read, no extra launch.
+        Optimizer state is not touched: ``if adapter.nonfinite_elements.healed > seen: optimizer.state.clear()``."""
         connection_kwargs = dict(connection_kwargs, track_distance=track_distance)
         if skip_nonfinite_peer:      # (off: the connection is built exactly as before)
             connection_kwargs["skip_nonfinite_peer"] = True
+        if heal_nonfinite:
+            connection_kwargs["heal_nonfinite"] = True
         if resident and transport != "device":
             raise ValueError("resident parameters need the device transport")
         self._net = net
@@ -360,6 +367,13 @@ class DpwaPyTorchAdapter:
         """Rounds skipped because the peer's snapshot held a NaN or an inf (``skip_nonfinite_peer=True``;
         an int, 0 with the switch off).  Reading it waits for the device."""
         return self._conn.nonfinite_skips
+
+    @property
+    def nonfinite_elements(self):
+        """``(healed, refused, rounds, clock)``: what ``heal_nonfinite=True`` has replaced in this model, not taken
+        from peers, the guarded rounds that averaged and the last one's clock (a named tuple; zeros with the
+        switch off).  Reading it waits for the device."""
+        return self._conn.nonfinite_elements
 
     @property
     def last_distance(self):

@@ -249,6 +249,10 @@ class _WireGroup:
         pass
 
 
+HEAL_WIRE = ("heal_nonfinite=True needs the device transport: the wire transport has no guarded round (its peers' "
+             "snapshots arrive as float32 blobs decoded on the host)")
+
+
 class WireConnection(DpwaConnection):
     """DpwaConnection whose peers are reached over TCP at the (host, port) of the YAML.
 
@@ -257,7 +261,9 @@ class WireConnection(DpwaConnection):
     (deterministic lock-step when every node's update_send precedes every update_wait)."""
 
     def __init__(self, name, config_file, codec=None, seed=None, eager=True, serve=True, track_distance=False,
-                 skip_nonfinite_peer=False):
+                 skip_nonfinite_peer=False, heal_nonfinite=False):
+        if heal_nonfinite:
+            raise ValueError(HEAL_WIRE)
         super().__init__(name, config_file, seed=seed, group=_WireGroup(), track_distance=track_distance,
                          skip_nonfinite_peer=skip_nonfinite_peer)
         self.codec = codec

@@ -31,6 +31,9 @@
 //             (k_peer_finite*), a test on the exponent bits; a lane that finds a NaN or an inf
 //             stores the round's stamp into the learner's veto word, and the factor of a round
 //             whose stamp it finds there is the no-op's, with a status of its own.
+//  * healing: opt-in -- guarded forms of the single-learner average (k_lerp_guarded*) that select every
+//             result element by the exponent bits of q and p: never a NaN or an inf from the peer, a NaN
+//             or an inf of our own replaced by the peer's finite element, both counted.
 //  * factor:  the same fp64 math as a one-thread kernel for the split API.
 //  * publish: update_send's snapshot (dpwa.py:111-116, pytorch.py:49-53) -- clock += 1 on
 //             the device and one copy of the flat buffer into a snapshot slot behind its
@@ -366,9 +369,11 @@ struct LerpArgs {
 // every lane, which keeps the uniform (a, b) in registers (no LDS hand-off, no barrier), or with
 // LDS (workgroups of more than one wave) by wave 0, which shares them through LDS; callers
 // issue their loads first, so that they are in flight meanwhile.  Lane 0 of the workgroup for
-// which `first_wg` holds commits the factor.
+// which `first_wg` holds commits the factor.  `new_clock` (the guarded kernels, one-wave workgroups, device or
+// fused coefficients): where to leave the round's new clock.
 template <int MODE, bool LDS = false>
-__device__ __forceinline__ bool lerp_coef(const LerpArgs &args, bool first_wg, float &a, float &b)
+__device__ __forceinline__ bool lerp_coef(const LerpArgs &args, bool first_wg, float &a, float &b,
+                                          double *new_clock = nullptr)
 {
     if (MODE == COEF_HOST) {
         a = args.a;
@@ -378,11 +383,13 @@ __device__ __forceinline__ bool lerp_coef(const LerpArgs &args, bool first_wg, f
         if (args.coef->status != DPWA_STATUS_OK) return false;
         a = args.coef->a;
         b = args.coef->b;
+        if (new_clock) *new_clock = args.coef->new_clock;
         return true;
     } else if (!LDS) {
         const dpwa_coef c = fused_factor(args.fused, first_wg && threadIdx.x == 0);
         a = c.a;
         b = c.b;
+        if (new_clock) *new_clock = c.new_clock;
         return c.status == DPWA_STATUS_OK;
     } else {
         __shared__ float s_a, s_b;
@@ -599,6 +606,109 @@ struct DistTrack {
     double *acc;
 };
 
+// ---------------------------------------------------------------- healing non-finite elements
+// Opt-in (dpwa_learner_set_heal; the rule is stated in include/dpwa_hip.h "healing"): the guarded averaging
+// kernels select every result element from what the lane holds anyway -- the peer's q, our p and the lerp r of
+// the whole item -- by the exponent bits of q and p (all ones: bad; the test of the non-finite peer check):
+//     q good, p good: r        q bad: p (refused)        q good, p bad: q (healed)
+// No factor can do this (1*q + 0*p is NaN for a NaN p), so it is a select on the operands: per element two
+// masks of whole elements, mq and mp, and two bit-field inserts (v_bfi_b32) into r.  A dword of a 16-bit type
+// holds two elements that may fall in different rows, so each half's mask comes from its own half's exponent.
+// No branch per element, no LDS.  The bad operands have been through the lerp; what it made of them is masked.
+//
+// Counting: a lane counts its healed and refused elements (at most 9 of each: the 8 of a 16-bit item and one
+// tail element) in the halves of one register.  The wave's totals come from ballots: one ballot says whether
+// any lane counted anything -- a clean span, which is what every round pays, ends there with no atomic -- and
+// in a span that did, four ballots and population counts per counter (one per bit of the lane counts) add them
+// up on the scalar unit; a DPP or shuffle reduction would move data across lanes six steps deep for the same
+// two numbers and would have no cheaper answer to "anything at all?".  Lane 0 then adds the non-zero totals to
+// the cumulative record with 64-bit vector global atomics; integer adds commute, so the record is bit-exact
+// from run to run.  `rounds` and `clock` are written by the lane that commits the factor (COEF_DEV: lane 0 of
+// global workgroup 0), for a round that averaged.
+struct NoGuard {
+    static constexpr bool ON = false;
+};
+struct HealGuard {
+    static constexpr bool ON = true;
+    dpwa_heal_record *rec;
+};
+
+__device__ __forceinline__ uint32_t bad_mask_f32(uint32_t w) { return (w & 0x7f800000u) == 0x7f800000u ? 0xffffffffu : 0u; }
+// the two 16-bit elements of a dword, exponent mask M (bf16 0x7f80, fp16 0x7c00): 0xffff over each bad half
+template <uint32_t M> __device__ __forceinline__ uint32_t bad_mask_16x2(uint32_t w)
+{
+    return ((w & M) == M ? 0x0000ffffu : 0u) | ((w & (M << 16)) == (M << 16) ? 0xffff0000u : 0u);
+}
+
+// One dword: mq / mp cover the bad elements of q / p, E has the lowest bit of every element of the dword set.
+template <uint32_t E>
+__device__ __forceinline__ uint32_t heal_word(uint32_t q, uint32_t p, uint32_t r, uint32_t mq, uint32_t mp, uint32_t &counts)
+{
+    const uint32_t take_q = mp & ~mq;
+    counts += (uint32_t)__builtin_popcount(take_q & E) + ((uint32_t)__builtin_popcount(mq & E) << 16);
+    r = (q & take_q) | (r & ~take_q);
+    return (p & mq) | (r & ~mq);
+}
+
+__device__ __forceinline__ f32x4 heal_item(OpsF32, f32x4 q, f32x4 p, f32x4 r, uint32_t &counts)
+{
+    const u32x4 qb = __builtin_bit_cast(u32x4, q), pb = __builtin_bit_cast(u32x4, p), rb = __builtin_bit_cast(u32x4, r);
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = heal_word<1u>(qb[e], pb[e], rb[e], bad_mask_f32(qb[e]), bad_mask_f32(pb[e]), counts);
+    return __builtin_bit_cast(f32x4, o);
+}
+
+template <uint32_t M> __device__ __forceinline__ u32x4 heal_item16(u32x4 q, u32x4 p, u32x4 r, uint32_t &counts)
+{
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        o[e] = heal_word<0x00010001u>(q[e], p[e], r[e], bad_mask_16x2<M>(q[e]), bad_mask_16x2<M>(p[e]), counts);
+    return o;
+}
+__device__ __forceinline__ u32x4 heal_item(OpsBF16, u32x4 q, u32x4 p, u32x4 r, uint32_t &counts)
+{
+    return heal_item16<0x7f80u>(q, p, r, counts);
+}
+__device__ __forceinline__ u32x4 heal_item(OpsF16, u32x4 q, u32x4 p, u32x4 r, uint32_t &counts)
+{
+    return heal_item16<0x7c00u>(q, p, r, counts);
+}
+
+// One element (the ragged tail); a 16-bit element is the low half of a dword whose high half is zero (good).
+__device__ __forceinline__ float heal_s(OpsF32, float q, float p, float r, uint32_t &counts)
+{
+    const uint32_t qb = __float_as_uint(q), pb = __float_as_uint(p);
+    return __uint_as_float(heal_word<1u>(qb, pb, __float_as_uint(r), bad_mask_f32(qb), bad_mask_f32(pb), counts));
+}
+__device__ __forceinline__ uint16_t heal_s(OpsBF16, uint16_t q, uint16_t p, uint16_t r, uint32_t &counts)
+{
+    return (uint16_t)heal_word<1u>(q, p, r, bad_mask_16x2<0x7f80u>(q), bad_mask_16x2<0x7f80u>(p), counts);
+}
+__device__ __forceinline__ uint16_t heal_s(OpsF16, uint16_t q, uint16_t p, uint16_t r, uint32_t &counts)
+{
+    return (uint16_t)heal_word<1u>(q, p, r, bad_mask_16x2<0x7c00u>(q), bad_mask_16x2<0x7c00u>(p), counts);
+}
+
+__device__ __forceinline__ void heal_commit(dpwa_heal_record *rec, bool first_wg, uint32_t counts, double new_clock)
+{
+    if (first_wg && threadIdx.x == 0) {   // (this lane alone writes them)
+        rec->rounds = rec->rounds + 1;
+        rec->clock = new_clock;
+    }
+    if (__builtin_amdgcn_ballot_w64(counts != 0) == 0) return;   // uniform: a clean span
+    uint32_t healed = 0, refused = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // lane counts are <= 9: four bit planes
+        healed += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64((counts >> k) & 1u)) << k;
+        refused += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64((counts >> (16 + k)) & 1u)) << k;
+    }
+    if (threadIdx.x != 0) return;
+    if (healed) __hip_atomic_fetch_add(&rec->healed, (uint64_t)healed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (refused) __hip_atomic_fetch_add(&rec->refused, (uint64_t)refused, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // One 16-byte item per lane; items beyond n/PER (the ragged tail) go to block 0.
 // DUAL also stores the result into args.snap (write-through snapshot: the next publish of
 // these parameters then needs no copy).  OOP (with DUAL): the result is stored into args.snap
@@ -607,12 +717,17 @@ struct DistTrack {
 // averaging's own bytes; learner.cpp "resident").  BLOCK lanes per workgroup (kStreamBlock).
 // Track (DistTrack, one-wave workgroups only): a round that averages also adds its distance sums,
 // formed from the q and p this lane loaded anyway; a no-op round adds nothing.
-template <class Ops, int MODE, bool DUAL, int BLOCK, int POLICY, class Src, bool OOP = false, class Track = NoTrack>
+// Guard (HealGuard, one-wave workgroups, device or fused coefficients; "healing non-finite elements" above): a
+// round that averages selects every result element by the rule of include/dpwa_hip.h and counts what it healed
+// and refused; a no-op round selects and counts nothing.
+template <class Ops, int MODE, bool DUAL, int BLOCK, int POLICY, class Src, bool OOP = false, class Track = NoTrack,
+          class Guard = NoGuard>
 __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restrict__ param, const Src &src,
                                           int64_t n, const LerpArgs &args, const Ops &ops = Ops{},
-                                          const Track &track = Track{})
+                                          const Track &track = Track{}, const Guard &guard = Guard{})
 {
     static_assert(!Track::ON || BLOCK == 64, "the tracked form runs one-wave workgroups");
+    static_assert(!Guard::ON || (BLOCK == 64 && MODE != COEF_HOST), "the guarded form: one wave, a dpwa_coef");
     using V = typename Ops::V;
     using P = LerpPolicy<POLICY>;
     constexpr int SPAN = BLOCK * 16;
@@ -625,7 +740,8 @@ __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restr
     const V q = span_load<V>(rq, lane_off);
     const V p = span_load<V, P::param_load>(rp, lane_off);
     float a, b;
-    if (!lerp_coef<MODE, BLOCK != 64>(args, blk == 0, a, b)) {
+    [[maybe_unused]] double new_clock = 0.0;
+    if (!lerp_coef<MODE, BLOCK != 64>(args, blk == 0, a, b, Guard::ON ? &new_clock : nullptr)) {
         if (MODE == COEF_FUSED && DUAL) {   // no-op round; a write-through snapshot still gets the parameters
             span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, p);
             if constexpr (Ops::TAIL) {
@@ -638,7 +754,9 @@ __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restr
         }
         return;
     }
-    const V r = ops.lerp(a, b, q, p);
+    V r = ops.lerp(a, b, q, p);
+    [[maybe_unused]] uint32_t counts = 0;   // HealGuard: this lane's healed | refused << 16
+    if constexpr (Guard::ON) r = heal_item(ops, q, p, r, counts);
     if (!OOP) span_store<V, P::store>(rp, lane_off, r);
     if (DUAL) span_store<V, P::snap_store>(span_rsrc<SPAN>(args.snap, span_off, vbytes), lane_off, r);
     [[maybe_unused]] double d2 = 0.0, n2 = 0.0;
@@ -650,13 +768,15 @@ __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restr
         if (blk == 0 && threadIdx.x < n - tail) {
             const int64_t j = tail + threadIdx.x;
             const S qs = *reinterpret_cast<const S *>(src.at(j * (int64_t)sizeof(S))), pj = ps[j];
-            const S t = Ops::lerp_s(a, b, qs, pj);
+            S t = Ops::lerp_s(a, b, qs, pj);
+            if constexpr (Guard::ON) t = heal_s(ops, qs, pj, t, counts);
             if (!OOP) ps[j] = t;
             if (DUAL) reinterpret_cast<S *>(args.snap)[j] = t;
             if constexpr (Track::ON) dist_add_s(ops, qs, pj, d2, n2);
         }
     }
     if constexpr (Track::ON) dist_commit(track.acc, blk, d2, n2);
+    if constexpr (Guard::ON) heal_commit(guard.rec, blk == 0, counts, new_clock);
 }
 
 template <class Ops, int MODE, bool DUAL, int BLOCK = kBlock, int POLICY = 0, bool OOP = false>
@@ -721,6 +841,43 @@ __global__ __launch_bounds__(kStreamBlock) void k_lerp_mixed(u32x4 *__restrict__
     const ContigSrc src{(const char *)peer};
     const OpsMixed ops{segs, src.span_of<kStreamBlock * 16>(blockIdx.x)};
     lerp_span<OpsMixed, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP>(blockIdx.x, param, src, total, args, ops);
+}
+
+// The guarded forms of the single-learner average ("healing non-finite elements"): k_lerp's span code with
+// HealGuard, so a good/good element has k_lerp's bits.  Fused (MODE COEF_FUSED: plain, write-through DUAL,
+// resident OOP) and device coefficients (COEF_DEV, the lerp of a split round); one-wave workgroups; the cache
+// policy k_lerp would take (by size; resident: kProductPolicy).  16-B aligned operands only.
+template <class Ops, int MODE, bool DUAL, bool OOP, int POLICY>
+__global__ __launch_bounds__(kStreamBlock) void k_lerp_guarded(typename Ops::V *__restrict__ param,
+                                                               const typename Ops::V *__restrict__ peer, int64_t n,
+                                                               LerpArgs args, dpwa_heal_record *__restrict__ rec)
+{
+    lerp_span<Ops, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP, NoTrack, HealGuard>(
+        blockIdx.x, param, ContigSrc{(const char *)peer}, n, args, Ops{}, NoTrack{}, HealGuard{rec});
+}
+
+// The same over a segmented payload: the span's test, like its lerp, is its segment's (seg_dtype from the
+// span's byte offset, as k_lerp_mixed; padding bytes are zeros on both sides: good, and they stay zeros).
+__device__ __forceinline__ u32x4 heal_item(const OpsMixed &ops, u32x4 q, u32x4 p, u32x4 r, uint32_t &counts)
+{
+    const int32_t dtype = seg_dtype(ops.segs, ops.span_off);
+    if (dtype == DPWA_F32)
+        return __builtin_bit_cast(u32x4, heal_item(OpsF32{}, __builtin_bit_cast(f32x4, q), __builtin_bit_cast(f32x4, p),
+                                                   __builtin_bit_cast(f32x4, r), counts));
+    if (dtype == DPWA_BF16) return heal_item(OpsBF16{}, q, p, r, counts);
+    return heal_item(OpsF16{}, q, p, r, counts);
+}
+
+template <int MODE, bool DUAL, int POLICY, bool OOP>
+__global__ __launch_bounds__(kStreamBlock) void k_lerp_guarded_mixed(u32x4 *__restrict__ param,
+                                                                     const u32x4 *__restrict__ peer, int64_t total,
+                                                                     LerpArgs args, SegTable segs,
+                                                                     dpwa_heal_record *__restrict__ rec)
+{
+    const ContigSrc src{(const char *)peer};
+    const OpsMixed ops{segs, src.span_of<kStreamBlock * 16>(blockIdx.x)};
+    lerp_span<OpsMixed, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP, NoTrack, HealGuard>(
+        blockIdx.x, param, src, total, args, ops, NoTrack{}, HealGuard{rec});
 }
 
 // The tracked form of the single-learner fused average (k_lerp's span code with DistTrack, so the
@@ -1546,6 +1703,73 @@ hipError_t launch_average_tracked(int32_t dtype, void *param, const void *peer, 
             return snap ? run(k_lerp_tracked<Ops, true, false, P>) : run(k_lerp_tracked<Ops, false, false, P>);
         });
     });
+}
+
+// ---------------------------------------------------------------- guarded (healing) launches
+// One guarded launch, fused (MODE COEF_FUSED; `oop`: resident) or with device coefficients (COEF_DEV).  Refused
+// before anything is queued: no record or a misaligned one, n < 0, an operand that is not 16-B aligned (there
+// is no unaligned form), a resident launch without its destination, more than 2^31 - 1 spans, and what
+// with_ops / with_segments refuse.
+template <int MODE>
+static hipError_t launch_guarded(const Elems &e, void *param, const void *peer, const LerpArgs &args, bool oop,
+                                 dpwa_heal_record *rec, hipStream_t s, const LaunchTiming *timing)
+{
+    void *const snap = args.snap;
+    if (!rec || ((uintptr_t)rec & 7) || !aligned16(param) || !aligned16(peer) || !aligned16(snap)) return hipErrorInvalidValue;
+    if (e.segmented()) {
+        const bool bad = !param || !peer || (oop && !snap);
+        return with_segments(e, bad, [&](int64_t total, dim3 grid, const SegTable &t) {
+            const auto run = [&](void (*kernel)(u32x4 *, const u32x4 *, int64_t, LerpArgs, SegTable, dpwa_heal_record *)) {
+                return launch(kernel, grid, dim3(kStreamBlock), s, timing, param, peer, total, args, t, rec);
+            };
+            if constexpr (MODE == COEF_FUSED)
+                if (oop) return run(k_lerp_guarded_mixed<MODE, true, kProductPolicy, true>);
+            return BySizePolicies::with(lerp_policy(total), [&](auto policy) {
+                constexpr int P = decltype(policy)::value;
+                if constexpr (MODE == COEF_FUSED)   // (a lerp with device coefficients writes the parameters only)
+                    if (snap) return run(k_lerp_guarded_mixed<MODE, true, P, false>);
+                return run(k_lerp_guarded_mixed<MODE, false, P, false>);
+            });
+        });
+    }
+    const int64_t n = e.n;
+    if (n < 0 || (oop && !snap && n > 0) || (n > 0 && (!param || !peer))) return hipErrorInvalidValue;
+    if (n == 0 && MODE != COEF_FUSED) return hipSuccess;
+    return with_ops(e.dtype, [&](auto ops) {
+        using Ops = decltype(ops);
+        using V = typename Ops::V;
+        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+        const auto run = [&](void (*kernel)(V *, const V *, int64_t, LerpArgs, dpwa_heal_record *)) {
+            return launch(kernel, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, timing, param,
+                          peer, n, args, rec);
+        };
+        if constexpr (MODE == COEF_FUSED)
+            if (oop) return run(k_lerp_guarded<Ops, MODE, true, true, kProductPolicy>);   // resident: no choice by size
+        return BySizePolicies::with(lerp_policy(n * (int64_t)sizeof(typename Ops::S)), [&](auto policy) {
+            constexpr int P = decltype(policy)::value;
+            if constexpr (MODE == COEF_FUSED)
+                if (snap) return run(k_lerp_guarded<Ops, MODE, true, false, P>);
+            return run(k_lerp_guarded<Ops, MODE, false, false, P>);
+        });
+    });
+}
+
+hipError_t launch_average_guarded(const Elems &e, void *param, const void *peer, const FusedArgs &fa, void *snap,
+                                  dpwa_heal_record *rec, hipStream_t s, const LaunchTiming *timing, bool oop)
+{
+    LerpArgs args{};
+    args.fused = fa;
+    args.snap = snap;
+    return launch_guarded<COEF_FUSED>(e, param, peer, args, oop, rec, s, timing);
+}
+
+hipError_t launch_lerp_guarded(const Elems &e, void *param, const void *peer, const dpwa_coef *coef,
+                               dpwa_heal_record *rec, hipStream_t s)
+{
+    if (!coef) return hipErrorInvalidValue;
+    LerpArgs args{};
+    args.coef = coef;
+    return launch_guarded<COEF_DEV>(e, param, peer, args, false, rec, s, nullptr);
 }
 
 hipError_t launch_distance(const Elems &e, const void *param, const void *peer, double *acc, hipStream_t s)

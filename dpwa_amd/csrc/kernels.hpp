@@ -113,6 +113,18 @@ hipError_t launch_distance(const Elems &e, const void *param, const void *peer, 
 hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_coef *coef, int64_t n, hipStream_t s,
                                   const LaunchTiming *timing = nullptr);
 
+// The guarded averages (include/dpwa_hip.h "healing"; kernels.hip "healing non-finite elements"): launch_average
+// (k_lerp_guarded / k_lerp_guarded_mixed) and launch_lerp with device coefficients, every result element selected
+// by the healing rule and the healed / refused elements added to *rec (device memory, 8-B aligned; rounds and
+// clock written when the round averaged).  hipErrorInvalidValue, nothing queued: no record, no `coef`, n < 0, a
+// `param`, `peer` or `snap` that is not 16-B aligned (there is no unaligned form), `oop` without `snap`, more
+// than 2^31 - 1 spans, and what Elems refuses.
+hipError_t launch_average_guarded(const Elems &e, void *param, const void *peer, const FusedArgs &fa, void *snap,
+                                  dpwa_heal_record *rec, hipStream_t s, const LaunchTiming *timing = nullptr,
+                                  bool oop = false);
+hipError_t launch_lerp_guarded(const Elems &e, void *param, const void *peer, const dpwa_coef *coef,
+                               dpwa_heal_record *rec, hipStream_t s);
+
 // The consensus of a group (dpwa_consensus, include/dpwa_hip.h; kernels.hip "consensus of a group"):
 // the element-wise mean of `count` (1..kMaxConsensus) payloads src[0..count), summed in that order
 // in fp64 and scaled by `r` (the host's 1.0 / count), stored into `out` (null: measure only), and

@@ -290,6 +290,8 @@ struct Ctl {            // device control block
     uint32_t finite_veto;
     uint32_t reserved;
     uint64_t finite_skips;
+    // healing (dpwa_learner_set_heal): the cumulative record the guarded kernels add to (kernels.hip)
+    dpwa_heal_record heal;
 };
 
 
@@ -483,6 +485,7 @@ struct dpwa_learner {
     // skip a round whose peer snapshot is not finite (dpwa_learner_set_finite_check); the stamp of the last
     // checked round: never 0, so the zeroed veto word matches no round
     bool finite_check = false;
+    bool heal = false;   // the guarded kernels average (dpwa_learner_set_heal)
     uint32_t finite_stamp = 0;
     HostWord<int32_t> status;           // pinned mirror of coef.status for non-blocking polls
     // the consensus of a group (dpwa_learner_consensus): its accumulator rows, made and zeroed at the
@@ -591,6 +594,27 @@ int dpwa_average(int32_t dtype, void *param, const void *peer_slot, int64_t n, c
     return DPWA_OK;
 }
 
+int dpwa_average_guarded(int32_t dtype, void *param, const void *peer_slot, int64_t n, const dpwa_interp *cfg,
+                         double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload,
+                         dpwa_heal_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (!cfg || !clock_dev || !coef_dev || !peer_slot || n < 0 || (n > 0 && !param) || dtype_size(dtype) == 0 ||
+        (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_guarded: bad arguments");
+    if (dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "dpwa_average_guarded: a DPWA_MIXED payload needs its layout (dpwa_average_guarded_mixed)");
+    if (!record_dev || ((uintptr_t)record_dev & 7))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_guarded: the record is NULL or not 8-byte aligned");
+    if (!aligned16(param, peer_slot, snap_payload))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_guarded: the guarded average has no form for operands that are not "
+                                       "16-byte aligned");
+    if (int rc = check_method(cfg, "dpwa_average_guarded")) return rc;
+    const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
+    HIP_TRY(launch_average_guarded(Elems{dtype, n, nullptr}, param, (const char *)peer_slot + kPayloadOff, fa, snap_payload,
+                                   record_dev, (hipStream_t)stream, CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
 static uint32_t layout_fnv(const dpwa_layout &layout)
 {
     uint32_t h = 2166136261u;
@@ -629,6 +653,25 @@ int dpwa_average_mixed(const dpwa_layout *layout, void *param, const void *peer_
     const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
     HIP_TRY(launch_average(Elems{DPWA_MIXED, layout_bytes(*layout), layout}, param, (const char *)peer_slot + kPayloadOff,
                            fa, snap_payload, (hipStream_t)stream, CallerTiming(start_event, stop_event)));
+    return DPWA_OK;
+}
+
+int dpwa_average_guarded_mixed(const dpwa_layout *layout, void *param, const void *peer_slot, const dpwa_interp *cfg,
+                               double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload,
+                               dpwa_heal_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (!layout || !cfg || !clock_dev || !coef_dev || !peer_slot || !param || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_guarded_mixed: bad arguments");
+    if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_average_guarded_mixed: %s", why);
+    if (!record_dev || ((uintptr_t)record_dev & 7))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_guarded_mixed: the record is NULL or not 8-byte aligned");
+    if (!aligned16(param, peer_slot, snap_payload))
+        return set_error(DPWA_ERR_ARG, "dpwa_average_guarded_mixed: a segmented payload is 16-byte aligned");
+    if (int rc = check_method(cfg, "dpwa_average_guarded_mixed")) return rc;
+    const FusedArgs fa = stateless_args(cfg, clock_dev, peer_slot, loss, coef_dev);
+    HIP_TRY(launch_average_guarded(Elems{DPWA_MIXED, layout_bytes(*layout), layout}, param,
+                                   (const char *)peer_slot + kPayloadOff, fa, snap_payload, record_dev, (hipStream_t)stream,
+                                   CallerTiming(start_event, stop_event)));
     return DPWA_OK;
 }
 
@@ -1206,6 +1249,15 @@ int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dp
     return DPWA_OK;
 }
 
+// The guarded kernels have no form for parameters that are not 16-byte aligned (the peer payload and the
+// snapshot slots always are): refused before anything is queued.
+static int heal_operands_problem(const dpwa_learner *l, const char *fn, const void *flat)
+{
+    if (!l->heal || aligned16(flat)) return DPWA_OK;
+    return set_error(DPWA_ERR_ARG, "%s: healing (dpwa_learner_set_heal) has no form for parameters that are not "
+                                   "16-byte aligned", fn);
+}
+
 int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
 {
     if (!l || (!flat && l->n > 0)) return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: NULL argument");
@@ -1217,10 +1269,12 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     if (l->dtype == DPWA_MIXED && !aligned16(flat))   // (its layout is known: the factor was computed)
         return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
     if (int rc = l->measure.operands_problem("dpwa_learner_lerp", flat)) return rc;
+    if (int rc = heal_operands_problem(l, "dpwa_learner_lerp", flat)) return rc;
     if (int rc = pack_materialize(l, s)) return rc;   // (a second pull since the factor)
     const Measured m{&l->measure, payload(l), flat, l->fetch.source().ptr + kPayloadOff, nullptr};
     int rc = measured_average(&m, 1, s, [&]() -> int {
-        HIP_TRY(launch_lerp(m.p, flat, m.peer, m.p.coef, 0.f, 0.f, s));
+        if (l->heal) HIP_TRY(launch_lerp_guarded(m.p, flat, m.peer, m.p.coef, &l->ctl->heal, s));
+        else HIP_TRY(launch_lerp(m.p, flat, m.peer, m.p.coef, 0.f, 0.f, s));
         return DPWA_OK;
     });
     if (rc) return rc;
@@ -1255,6 +1309,7 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
     if (l->dtype == DPWA_MIXED && !aligned16(flat))
         return set_error(DPWA_ERR_ARG, "dpwa_learner_average: a segmented payload is 16-byte aligned");
     if (int rc = l->measure.operands_problem("dpwa_learner_average", flat)) return rc;
+    if (int rc = heal_operands_problem(l, "dpwa_learner_average", flat)) return rc;
     p = AvgPlan();
     if (l->resident) {   // read where the parameters are (the published slot), write the next slot
         if (flat != slot_payload(l, l->res_slot))
@@ -1288,9 +1343,10 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
     } else {
         if (int rc = relay_materialize(l)) return rc;
         // a payload that is still packed: k_lerp_packed reads the landing image itself, unless something of this
-        // round needs the contiguous payload (a measurement, the non-finite check, a batched dispatch, the
-        // unaligned form), which expands it first
-        const bool plain = alone && !l->measure.whole() && !l->measure.param() && !l->finite_check && aligned16(flat, p.snap);
+        // round needs the contiguous payload (a measurement, the non-finite check, healing, a batched dispatch,
+        // the unaligned form), which expands it first
+        const bool plain = alone && !l->measure.whole() && !l->measure.param() && !l->finite_check && !l->heal &&
+                           aligned16(flat, p.snap);
         if (l->fetch.source().packed && plain) {
             p.image = l->fetch.source().packed;
         } else {
@@ -1340,9 +1396,13 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
     const Payload e = payload(l);
     const LaunchTiming *timing = e.segmented() || p.relay || aligned16(p.flat) ? take_timing(l) : nullptr;
     if (int rc = finite_pass(l, p.fa, p.peer, s)) return rc;   // (never with p.relay: relay_phase2 refuses)
-    const Measured m{&l->measure, e, p.flat, p.peer, p.snap, &p.fa, p.oop, timing};
+    // (a healing learner passes no FusedArgs: the tracked kernel has no guarded form, so the stand-alone
+    // distance pass runs first and the guarded average is the callback)
+    const Measured m{&l->measure, e, p.flat, p.peer, p.snap, l->heal ? nullptr : &p.fa, p.oop, timing};
     return measured_average(&m, 1, s, [&]() -> int {
-        if (p.relay) {   // (never a segmented payload: relay_phase2 refuses)
+        if (l->heal) {   // (never p.relay: relay_phase2 refuses; never p.emit or p.image: average_prepare)
+            HIP_TRY(launch_average_guarded(e, p.flat, p.peer, p.fa, p.snap, &l->ctl->heal, s, timing, p.oop));
+        } else if (p.relay) {   // (never a segmented payload: relay_phase2 refuses)
             HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
                                          timing, p.oop));
         } else if (p.emit) {   // (as p.image; p.peer or p.image, whichever average_prepare chose)
@@ -1367,10 +1427,10 @@ static int average_impl(dpwa_learner *l, void *flat, double loss, const double *
 }
 
 // Can plan p join a batched dispatch (k_lerp_batch)?  Contiguous source, 16-B aligned operands, one
-// element type (a segmented payload is not batched).
+// element type (a segmented payload is not batched), no healing (the batch has no guarded form).
 static bool batchable(const dpwa_learner *l, const AvgPlan &p)
 {
-    return !p.relay && !payload(l).segmented() && aligned16(p.flat, p.peer, p.snap);
+    return !p.relay && !l->heal && !payload(l).segmented() && aligned16(p.flat, p.peer, p.snap);
 }
 
 // Launches the batchable plans in groups of the same (dtype, write-through), up to
@@ -1549,6 +1609,32 @@ int dpwa_node_set_finite_check(dpwa_node *n, int on)
     if (!n || dpwa_node_handles(n, &l, nullptr) || !l)
         return set_error(DPWA_ERR_STATE, "dpwa_node_set_finite_check: node not bound");
     return dpwa_learner_set_finite_check(l, on);
+}
+
+int dpwa_learner_set_heal(dpwa_learner *l, int on)
+{
+    if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_heal: NULL learner");
+    if (on && l->relay_deferred)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_set_heal: a fused relay second phase is pending "
+                                         "(dpwa_learner_relay_phase2 with fuse != 0), whose average has no guarded form");
+    l->heal = on != 0;
+    return DPWA_OK;
+}
+
+int dpwa_node_set_heal(dpwa_node *n, int on)
+{
+    dpwa_learner *l = nullptr;
+    if (!n || dpwa_node_handles(n, &l, nullptr) || !l) return set_error(DPWA_ERR_STATE, "dpwa_node_set_heal: node not bound");
+    return dpwa_learner_set_heal(l, on);
+}
+
+int dpwa_learner_heal_record(dpwa_learner *l, dpwa_heal_record *out)
+{
+    if (!l || !out) return set_error(DPWA_ERR_ARG, "dpwa_learner_heal_record: NULL argument");
+    DeviceGuard dg(l->device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, &l->ctl->heal, sizeof(dpwa_heal_record), hipMemcpyDeviceToHost));
+    return DPWA_OK;
 }
 
 int dpwa_learner_finite_skips(dpwa_learner *l, uint64_t *count)
@@ -2026,6 +2112,10 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
         return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase reads no contiguous peer "
                                          "snapshot, so a learner that skips non-finite peers "
                                          "(dpwa_learner_set_finite_check) cannot use it; gather (fuse = 0)");
+    if (fuse && l->heal)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_relay_phase2: the fused second phase's average has no guarded "
+                                         "form, so a learner that heals non-finite elements (dpwa_learner_set_heal) "
+                                         "cannot use it; gather (fuse = 0)");
     RelayArgs a;
     int rc = relay_args(l, picks_dev, version, a);
     if (rc) return rc;

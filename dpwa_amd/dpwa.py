@@ -13,6 +13,7 @@ protocol and error behaviour as the reference.  What moves:
   raised at the next call (or at :meth:`synchronize`), because raising at the call itself
   would need a host sync every round.
 """
+import collections
 import ctypes
 import logging
 import os
@@ -367,10 +368,17 @@ FINITE_RELAY_AVG = ("pull='relay-avg' is not available with skip_nonfinite_peer=
                     "or inf; use 'relay' (the same relay, gathered first), 'kernel' or 'copy', or leave "
                     "skip_nonfinite_peer off")
 
+HEAL_RELAY_AVG = ("pull='relay-avg' is not available with heal_nonfinite=True: the relay's fused second phase "
+                  "averages with a kernel of its own that has no guarded form; use 'relay' (the same relay, "
+                  "gathered first), 'kernel' or 'copy', or leave heal_nonfinite off")
+
+# ``nonfinite_elements``: the cumulative record of heal_nonfinite=True
+NonfiniteElements = collections.namedtuple("NonfiniteElements", "healed refused rounds clock")
+
 
 class DpwaConnection:
     def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None, track_distance=False,
-                 parameter_ranges=None, distance_every=1, skip_nonfinite_peer=False):
+                 parameter_ranges=None, distance_every=1, skip_nonfinite_peer=False, heal_nonfinite=False):
         """layout (extension): ``FlatParameters.layout`` when the flat buffer given to update_send
         is the segmented ``torch.uint8`` buffer of a model that mixes dtypes (dpwa_amd/flat.py);
         every peer must hold the same layout.
@@ -403,7 +411,18 @@ class DpwaConnection:
         seam, where the caller does the arithmetic with the returned snapshot: there the factor of a
         skipped round is 0, and ``0 * nan`` is still ``nan`` -- call ``average()``.  A replica whose
         own parameters are non-finite is not healed (``b * p`` stays NaN); its peers stop taking
-        from it.  Not available with ``pull='relay-avg'``."""
+        from it.  Not available with ``pull='relay-avg'``.
+
+        heal_nonfinite (extension, off by default): the averaging kernel itself selects every result
+        element -- it never takes a NaN or an inf from the peer (the element keeps our value; counted
+        as ``refused``) and replaces a NaN or an inf of our own with the peer's finite element, bits
+        unchanged (``healed``); every other element is averaged exactly as before.  No extra read and
+        no extra launch; the counters are ``nonfinite_elements``.  Factor, clock and the round's
+        coefficients are the unguarded round's.  It covers ``update_wait_average`` (every form; inside
+        ``update_wait_average_many`` a healing learner gets a launch of its own) and ``update_wait()``
+        followed by ``average()``; the parameter buffer must be 16-byte aligned.  Optimizer state is
+        not touched.  With ``skip_nonfinite_peer`` too, the pre-pass and its veto stay as they are.
+        Not available with ``pull='relay-avg'``."""
         self.name = name
         self._layout = tuple(layout) if layout is not None else None
         if isinstance(track_distance, str) and track_distance != "per_parameter":
@@ -426,6 +445,9 @@ class DpwaConnection:
         self._skip_nonfinite = bool(skip_nonfinite_peer)
         if self._skip_nonfinite and pull is not None and pull.partition(":")[0] == "relay-avg":
             raise ValueError(FINITE_RELAY_AVG)
+        self._heal = bool(heal_nonfinite)
+        if self._heal and pull is not None and pull.partition(":")[0] == "relay-avg":
+            raise ValueError(HEAL_RELAY_AVG)
         if self._layout is not None and pull is not None and pull.partition(":")[0] in PACKED_PULLS:
             raise ValueError(MIXED_PACKED)
         self.config = DpwaConfiguration(config_file)
@@ -745,6 +767,16 @@ class DpwaConnection:
             return 0
         return int(self._learner.finite_skips())
 
+    @property
+    def nonfinite_elements(self):
+        """What ``heal_nonfinite=True`` has done so far: the named tuple ``(healed, refused, rounds,
+        clock)`` -- elements of our own replaced by the peer's, elements of the peer's not taken, the
+        guarded rounds that averaged and the clock the last of them left.  Zeros with the switch off
+        or before the first update_send.  Reading it waits for the device."""
+        if self._learner is None or not self._heal:
+            return NonfiniteElements(0, 0, 0, 0.0)
+        return NonfiniteElements(*self._learner.heal_record())
+
     def consensus(self, out=None, distance=True, members=None):
         """The group's consensus model and consensus distance (extension, opt-in, read-only;
         dpwa_amd/consensus.py): the element-wise mean of the snapshots this node and its peers
@@ -891,6 +923,10 @@ class DpwaConnection:
             if self._pull.partition(":")[0] == "relay-avg":
                 raise ValueError(FINITE_RELAY_AVG)
             _lib.call("dpwa_node_set_finite_check", self._node, 1)
+        if self._heal:
+            if self._pull.partition(":")[0] == "relay-avg":
+                raise ValueError(HEAL_RELAY_AVG)
+            _lib.call("dpwa_node_set_heal", self._node, 1)
         if self._per_parameter:                       # table, workspace and record: allocated here as well
             from .flat import c_param_ranges
             arr, where = c_param_ranges(self._param_ranges)
@@ -945,6 +981,8 @@ class DpwaConnection:
             raise ValueError(TRACKED_RELAY_AVG)
         if kind == "relay-avg" and self._skip_nonfinite:
             raise ValueError(FINITE_RELAY_AVG)
+        if kind == "relay-avg" and self._heal:
+            raise ValueError(HEAL_RELAY_AVG)
         self._pull = mode
         learner = self._learner
         if learner is None:

@@ -231,6 +231,17 @@ class Learner:
         """dpwa_learner_set_finite_check: skip (and count) a round whose peer snapshot holds a NaN or an inf."""
         _lib.call("dpwa_learner_set_finite_check", self._h, 1 if on else 0)
 
+    def set_heal(self, on):
+        """dpwa_learner_set_heal: the guarded kernels average -- never a non-finite element from the peer, a
+        non-finite element of our own replaced by the peer's finite one, both counted."""
+        _lib.call("dpwa_learner_set_heal", self._h, 1 if on else 0)
+
+    def heal_record(self):
+        """(healed, refused, rounds, clock) so far (dpwa_heal_record; waits for the device)."""
+        r = _lib.HealRecord()
+        _lib.call("dpwa_learner_heal_record", self._h, ctypes.byref(r))
+        return int(r.healed), int(r.refused), int(r.rounds), float(r.clock)
+
     def finite_skips(self):
         """Rounds skipped for a non-finite peer snapshot so far (waits for the device)."""
         c = ctypes.c_uint64()

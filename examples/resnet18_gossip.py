@@ -83,6 +83,9 @@ def main(argv=None):
                     help="skip (and count) a round whose peer snapshot holds a NaN or an inf, so that one replica that "
                          "overflowed does not spread through the gossip (skip_nonfinite_peer=True); the count is "
                          "printed at the end")
+    ap.add_argument("--heal", action="store_true",
+                    help="heal non-finite parameters from the peer inside the averaging kernel and never take a "
+                         "non-finite element from it (heal_nonfinite=True); the counters are printed every 100 steps")
     ap.add_argument("--consensus", action="store_true",
                     help="print the group's relative consensus distance every 100 steps and save the consensus model "
                          "(the mean of the replicas' snapshots, adapter.consensus()) as a state_dict at the end; "
@@ -133,6 +136,9 @@ def main(argv=None):
                     top = sorted(d.parameters.relative().items(), key=lambda kv: -kv[1])[:3]
                     print("step %d, clock %g: largest relative distance to the peer: %s"
                           % (step, d.parameters.clock, ", ".join("%s %.3g" % kv for kv in top)), file=sys.stderr)
+            if gossip and args.heal and step % 100 == 0 and rank == 0:     # (this read waits for the device)
+                print("step %d: healed %d, refused %d elements in %d rounds (clock %g)"
+                      % ((step,) + tuple(adapters[0].nonfinite_elements)), file=sys.stderr)
             if gossip:
                 for i, a in enumerate(adapters):
                     a.update_send(losses[i])       # a device tensor: no host sync
@@ -162,6 +168,8 @@ def main(argv=None):
         group.update(track_distance="per_parameter", distance_every=100)
     if args.skip_nonfinite:
         group.update(skip_nonfinite_peer=True)
+    if args.heal:
+        group.update(heal_nonfinite=True)
     adapters = [DpwaPyTorchAdapter(nets[i], names[g], cfg, seed=100 + g, resident=args.resident, **group)
                 for i, g in enumerate(mine)]
     run(args.warmup, False)

@@ -50,7 +50,10 @@ extern "C" {
  * Still 11, by additions only: the average straight from a packed image -- dpwa_average_packed, and
  * DPWA_PULL_PACKED_AVG, a new mode of dpwa_learner_set_pull (which alone accepts max_blocks = 0).
  * Still 11, by additions only: the average that packs the snapshot it writes -- dpwa_average_pack, dpwa_pack_if,
- * dpwa_learner_pack_counts, dpwa_learner_pack_image. */
+ * dpwa_learner_pack_counts, dpwa_learner_pack_image.
+ * Still 11, by additions only: healing non-finite elements inside the averaging kernel (dpwa_heal_record) --
+ * dpwa_average_guarded, dpwa_average_guarded_mixed, dpwa_learner_set_heal, dpwa_learner_heal_record,
+ * dpwa_node_set_heal. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -274,6 +277,43 @@ int dpwa_check_finite(int32_t dtype, const void *peer_payload, int64_t n, uint32
                       dpwa_stream_t stream, void *start_event, void *stop_event);
 int dpwa_check_finite_mixed(const dpwa_layout *layout, const void *peer_payload, uint32_t *veto_dev, uint32_t stamp,
                             dpwa_stream_t stream, void *start_event, void *stop_event);
+
+/* Healing (extension, opt-in; no reference interface): the averaging kernel itself never takes a non-finite
+ * element from the peer and replaces a non-finite element of our own with the peer's finite one, per element,
+ * from the q and p it holds in registers anyway -- no extra byte read, no extra launch.  An element is "bad"
+ * when its exponent field is all ones (dpwa_check_finite's test on bit patterns: NaNs of either kind and
+ * +-inf; a subnormal and the largest finite value are good).  With a, b the round's coefficients exactly as
+ * dpwa_average forms them, every element's result r is
+ *     own p   peer q   r                                                              counted as
+ *     good    good     dpwa_average's bits (separately rounded products and sum)      --
+ *     good    bad      p, its bits unchanged                                          refused
+ *     bad     good     q, its bits unchanged (-0.0 stays -0.0)                        healed
+ *     bad     bad      p, its bits unchanged                                          refused
+ * and goes wherever the form stores results: the parameters, the write-through snapshot, the resident next
+ * slot.  The two 16-bit elements of a dword are selected independently; the ragged tail follows the same
+ * rule.  A no-op (ZeroDivision or vetoed) round changes and counts nothing; a write-through snapshot still
+ * receives the unchanged parameters.  Factor, clock, header and *coef_dev are exactly those of dpwa_average:
+ * the round counts as averaged.  Optimizer state is not touched.
+ * dpwa_heal_record (device memory, 8-B aligned, zero before the first use, cumulative): healed and refused
+ * elements (integer atomics: bit-exact from run to run; a round with none issues no atomic), the guarded
+ * rounds that averaged and the new clock of the last of them.
+ *   dpwa_average_guarded        dpwa_average with the rule above (k_lerp_guarded).
+ *   dpwa_average_guarded_mixed  dpwa_average_mixed with it; each segment by its own type's test.
+ * DPWA_ERR_ARG, nothing queued: what dpwa_average / dpwa_average_mixed refuse, a NULL or misaligned record,
+ * and `param`, the peer slot or `snap_payload` not 16-byte aligned (there is no unaligned form). */
+typedef struct dpwa_heal_record {
+    uint64_t healed;
+    uint64_t refused;
+    uint64_t rounds;
+    double clock;
+} dpwa_heal_record;
+int dpwa_average_guarded(int32_t dtype, void *param, const void *peer_slot, int64_t n, const dpwa_interp *cfg,
+                         double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload,
+                         dpwa_heal_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
+int dpwa_average_guarded_mixed(const dpwa_layout *layout, void *param, const void *peer_slot, const dpwa_interp *cfg,
+                               double *clock_dev, double loss, dpwa_coef *coef_dev, void *snap_payload,
+                               dpwa_heal_record *record_dev, dpwa_stream_t stream, void *start_event,
+                               void *stop_event);
 
 /* The consensus of a group (extension, opt-in, read-only; no reference interface): the element-wise
  * mean of `count` (1..DPWA_CONSENSUS_MAX) payloads of one dtype and n -- the model a gossip run
@@ -683,6 +723,23 @@ int dpwa_learner_param_distance_rounds(dpwa_learner *l, int64_t *averaged, int64
  * second phase is pending.  dpwa_node_set_finite_check: the same on a bound node's learner. */
 int dpwa_learner_set_finite_check(dpwa_learner *l, int on);
 int dpwa_learner_finite_skips(dpwa_learner *l, uint64_t *count);
+/* Healing ("Healing" above; off by default, and off every launch is the launch it was).  With set_heal(on != 0)
+ * -- the record lives in the learner's control block: nothing is allocated, here or in a round -- a single
+ * average of this learner (dpwa_learner_average / average_through, resident and DPWA_MIXED included) launches
+ * the guarded kernel in place of the plain one, and dpwa_learner_lerp the guarded lerp with the device
+ * coefficients.  heal_record copies the cumulative record (since dpwa_learner_create) out; it waits for the
+ * device.  Beside the other options: a learner that also tracks the whole-model distance runs the stand-alone
+ * distance pass first and then the guarded average (the tracked kernel has no guarded form); a pack-enabled
+ * learner's guarded average does not emit the image, so its publish packs; a DPWA_PULL_PACKED_AVG fetch is
+ * expanded first; inside dpwa_learner_average_many a healing learner gets a launch of its own; after
+ * set_finite_check the pre-pass and its veto stay as they are -- a vetoed round does nothing, and in any other
+ * round only the own-bad / peer-good row can still occur.
+ * Refused, nothing queued: parameters that are not 16-byte aligned (DPWA_ERR_ARG: there is no unaligned
+ * form); dpwa_learner_relay_phase2 with fuse != 0 on a healing learner, and set_heal(on) while a fused second
+ * phase is pending (DPWA_ERR_STATE: the relay's fused average has no guarded form).  dpwa_node_set_heal: the
+ * same on a bound node's learner. */
+int dpwa_learner_set_heal(dpwa_learner *l, int on);
+int dpwa_learner_heal_record(dpwa_learner *l, dpwa_heal_record *out);
 /* The consensus of a group of learners (dpwa_consensus above) over the published snapshots of publish
  * number `version`: the slot (version - 1) % 2 of `l` and of the named attached peers, in the order
  * given; peer_id -1 stands for `l` itself.  Peers may be local learners of l's device or IPC / fd-mapped
@@ -1059,6 +1116,8 @@ int dpwa_node_set_resident(dpwa_node *n, const void *init, dpwa_stream_t stream)
 /* dpwa_learner_set_finite_check on the node's learner (DPWA_ERR_STATE before dpwa_node_bind).  The
  * scheduler is not told of a skipped round: the fetch outcome was reported before the device looked. */
 int dpwa_node_set_finite_check(dpwa_node *n, int on);
+/* dpwa_learner_set_heal on the node's learner (DPWA_ERR_STATE before dpwa_node_bind). */
+int dpwa_node_set_heal(dpwa_node *n, int on);
 /* State of the current/last round: fetching flag, fetched peer (-1: none), its publish
  * number, and the picks the last fetch took. */
 int dpwa_node_info(const dpwa_node *n, int *fetching, int *fetch_peer, uint64_t *fetch_version,
