@@ -169,6 +169,8 @@ SIGNATURES = {
     "dpwa_consensus_workspace": [ctypes.POINTER(_i64)],
     "dpwa_consensus": [_i32, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     "dpwa_consensus_mixed": [ctypes.POINTER(Layout), _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_consensus_trimmed": [_i32, _vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dpwa_consensus_trimmed_mixed": [ctypes.POINTER(Layout), _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "dpwa_pack_bytes": [_i32, _i64, ctypes.POINTER(_i64)],
     "dpwa_pack": [_i32, _vp, _i64, _vp, _vp, _vp, _vp],
     "dpwa_unpack": [_i32, _vp, _i64, _vp, _int, _vp, _vp, _vp],
@@ -177,6 +179,7 @@ SIGNATURES = {
                           _vp],
     "dpwa_pack_if": [_i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
     "dpwa_learner_consensus": [_vp, ctypes.POINTER(_i32), _int, _u64, _vp, _vp, _vp],
+    "dpwa_learner_consensus_trimmed": [_vp, ctypes.POINTER(_i32), _int, _int, _u64, _vp, _vp, _vp],
     "dpwa_learner_set_finite_check": [_vp, _int],
     "dpwa_learner_finite_skips": [_vp, ctypes.POINTER(_u64)],
     "dpwa_node_set_finite_check": [_vp, _int],

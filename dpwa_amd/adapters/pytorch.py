@@ -382,7 +382,7 @@ class DpwaPyTorchAdapter:
         read the device record and synchronise with the stream that averaged; ``.tensor()`` does not."""
         return self._conn.last_distance
 
-    def consensus(self, out=None, distance=True, members=None):
+    def consensus(self, out=None, distance=True, members=None, trim=0):
         """``DpwaConnection.consensus`` for the model (device transport): the returned object also has
         ``parameters()`` -> ``{name: tensor}``, views of the mean with the parameters' shapes and
         dtypes, and ``load_into(module)``, which copies them into a model of the same structure."""
@@ -390,7 +390,7 @@ class DpwaPyTorchAdapter:
             from ..consensus import WIRE
             raise ValueError(WIRE)
         from ..consensus import ModelConsensus
-        return ModelConsensus(self._conn.consensus(out, distance, members), self._flat)
+        return ModelConsensus(self._conn.consensus(out, distance, members, trim), self._flat)
 
     @property
     def connection(self):

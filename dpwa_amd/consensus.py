@@ -6,6 +6,11 @@ consensus distance ``sqrt(1/G * sum_i ||x_i - mean||^2)`` says how far apart the
 kernel pass reads the G snapshots where they are (the learners' published slots, local or mapped),
 stores the mean once and forms the sums from the operands it holds: (G + 1) * N * s bytes, no
 temporaries, and a rounding that does not depend on the order anything happened to run in.
+
+``trim`` replaces the mean by the coordinate-wise trimmed mean (``"median"``: its extreme case): per
+element the ``trim`` smallest and largest of the G values are dropped -- a NaN or an inf sorts to an end
+-- and the rest averaged, in the same single pass (dpwa_consensus_trimmed), so one bad replica neither
+reaches the saved model nor drags the centre every ``member_spread2`` is measured against.
 """
 import ctypes
 
@@ -28,10 +33,12 @@ class Consensus:
     consensus distance), ``relative`` (``sqrt(spread2 / (G * norm2))``) and ``version`` are Python
     values read from the device record, so each of them synchronises with the stream the call ran on.
     All sums are float64 against the float64 mean, not the stored one; they are added across
-    workgroups in no fixed order and so are reproducible to the summation bound, not bit-exact."""
+    workgroups in no fixed order and so are reproducible to the summation bound, not bit-exact.
+    ``trim``: the effective trim of the call (0: the mean); with a trim, "mean" above reads "trimmed mean"."""
 
-    def __init__(self, names, version, out, record, stream):
+    def __init__(self, names, version, out, record, stream, trim=0):
         self.members = list(names)
+        self.trim = trim
         self._version = version
         self._out = out
         self._record = record
@@ -91,7 +98,7 @@ class ModelConsensus(Consensus):
     with the parameters' shapes and dtypes, and ``load_into(module)``."""
 
     def __init__(self, base, flat):
-        super().__init__(base.members, base._version, base._out, base._record, base._stream)
+        super().__init__(base.members, base._version, base._out, base._record, base._stream, base.trim)
         self._flat = flat
 
     def parameters(self):
@@ -111,8 +118,28 @@ class ModelConsensus(Consensus):
         return module
 
 
-def consensus(conn, out=None, distance=True, members=None):
+def checked_trim(trim):
+    """``trim`` as given to ``consensus()``: an int >= 0 or ``"median"``, else a ValueError."""
+    if trim == "median" or (isinstance(trim, int) and not isinstance(trim, bool) and trim >= 0):
+        return trim
+    raise ValueError("consensus(trim=...) is an int >= 0 or 'median', got %r" % (trim,))
+
+
+def effective_trim(trim, G):
+    """The values dropped at each end of every element's G sorted values: ``"median"`` is
+    ``(G - 1) // 2``; an int must leave a value, ``2 * trim < G``."""
+    trim = checked_trim(trim)
+    if trim == "median":
+        return (G - 1) // 2
+    if trim and 2 * trim >= G:
+        raise ValueError("consensus(trim=%d) leaves no value of G = %d members: the largest trim is %d"
+                         % (trim, G, (G - 1) // 2))
+    return trim
+
+
+def consensus(conn, out=None, distance=True, members=None, trim=0):
     """``DpwaConnection.consensus``'s body."""
+    checked_trim(trim)
     if conn._pull.partition(":")[0] == "relay-avg" or getattr(conn._group, "relay_fused", False):
         raise ValueError(RELAY_AVG)
     refusal = getattr(conn._group, "consensus_refusal", WIRE)      # (a group without the attribute: the wire's)
@@ -128,6 +155,7 @@ def consensus(conn, out=None, distance=True, members=None):
         raise ValueError("consensus(): no member")
     if len(picked) > _lib.CONSENSUS_MAX:
         raise ValueError(TOO_MANY % len(picked))
+    trim = effective_trim(trim, len(picked))
     if out is False:
         out = None
         if not distance:
@@ -142,8 +170,10 @@ def consensus(conn, out=None, distance=True, members=None):
         if distance else None
     stream = torch.cuda.current_stream(learner.device)
     ids = (ctypes.c_int32 * len(picked))(*[pid for _, pid in picked])
-    _lib.call("dpwa_learner_consensus", learner.handle, ids, len(picked), version,
-              ctypes.c_void_p(out.data_ptr()) if out is not None else None,
-              ctypes.c_void_p(record.data_ptr()) if record is not None else None,
-              ctypes.c_void_p(stream.cuda_stream))
-    return Consensus([name for name, _ in picked], version, out, record, stream)
+    tail = (version, ctypes.c_void_p(out.data_ptr()) if out is not None else None,
+            ctypes.c_void_p(record.data_ptr()) if record is not None else None, ctypes.c_void_p(stream.cuda_stream))
+    if trim:
+        _lib.call("dpwa_learner_consensus_trimmed", learner.handle, ids, len(picked), trim, *tail)
+    else:                                       # today's path, unchanged: the mean, summed in member order
+        _lib.call("dpwa_learner_consensus", learner.handle, ids, len(picked), *tail)
+    return Consensus([name for name, _ in picked], version, out, record, stream, trim)

@@ -1,6 +1,7 @@
 // consensus.cpp -- the consensus of a group without a learner: the stateless entry points of
-// include/dpwa_hip.h (dpwa_consensus, dpwa_consensus_mixed).  A learner's own call over published
-// slots (dpwa_learner_consensus) is in learner.cpp, beside the slots and marks it reads.
+// include/dpwa_hip.h (dpwa_consensus, dpwa_consensus_mixed and their _trimmed forms).  A learner's own
+// call over published slots (dpwa_learner_consensus{,_trimmed}) is in learner.cpp, beside the slots and
+// marks it reads.
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -20,12 +21,15 @@ int dpwa_consensus_workspace(int64_t *bytes)
     return DPWA_OK;
 }
 
-// What both entries check before a launch: the rule broken, or null.  Host only.
-static const char *consensus_problem(const void *const *payloads, int count, int64_t bytes, const void *out,
-                                     const void *workspace, const dpwa_consensus_record *record_dev,
+// What every entry checks before a launch: the rule broken, or null.  Host only.  `trim`: of a trimmed
+// entry, null from the mean's.
+static const char *consensus_problem(const void *const *payloads, int count, const int *trim, int64_t bytes,
+                                     const void *out, const void *workspace, const dpwa_consensus_record *record_dev,
                                      const void *start_event, const void *stop_event)
 {
     if (count < 1 || count > DPWA_CONSENSUS_MAX) return "count is outside 1..8";
+    if (trim && count < 3) return "a trimmed consensus needs at least 3 members";
+    if (trim && (*trim < 1 || 2 * *trim >= count)) return "trim is outside 1..(count - 1) / 2";
     if (!payloads) return "NULL payloads";
     if ((!workspace) != (!record_dev)) return "a workspace and a record go together (both or neither)";
     if (!out && !record_dev) return "neither out nor a record: nothing to do";
@@ -40,40 +44,79 @@ static const char *consensus_problem(const void *const *payloads, int count, int
     return nullptr;
 }
 
-static int run_consensus(const Elems &e, const void *const *payloads, int count, void *out,
+static int run_consensus(const Elems &e, const void *const *payloads, int count, const int *trim, void *out,
                          void *workspace, dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event,
                          void *stop_event)
 {
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_consensus(e, payloads, count, 1.0 / (double)count, out, (double *)workspace, false, s,
-                             CallerTiming(start_event, stop_event)));
-    if (record_dev) HIP_TRY(launch_consensus_finish((double *)workspace, record_dev, e.elements(), count, 0, s));
+    if (trim)
+        HIP_TRY(launch_consensus_trimmed(e, payloads, count, *trim, 1.0 / (double)(count - 2 * *trim), out,
+                                         (double *)workspace, false, s, CallerTiming(start_event, stop_event)));
+    else
+        HIP_TRY(launch_consensus(e, payloads, count, 1.0 / (double)count, out, (double *)workspace, false, s,
+                                 CallerTiming(start_event, stop_event)));
+    if (record_dev)
+        HIP_TRY(launch_consensus_finish((double *)workspace, record_dev, e.elements(), count, 0, s, nullptr,
+                                        trim ? *trim : 0));
     return DPWA_OK;
+}
+
+static int consensus_single(const char *fn, int32_t dtype, const void *const *payloads, int count, const int *trim,
+                            int64_t n, void *out, void *workspace, dpwa_consensus_record *record_dev,
+                            dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (dtype == DPWA_MIXED)
+        return set_error(DPWA_ERR_ARG, "%s: a DPWA_MIXED payload needs its layout (%s_mixed)", fn, fn);
+    if (!is_float_dtype(dtype)) return set_error(DPWA_ERR_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (n < 0 || n > INT64_MAX / 4) return set_error(DPWA_ERR_ARG, "%s: n < 0 or too large", fn);
+    const Elems e{dtype, n, nullptr};
+    if (const char *why = consensus_problem(payloads, count, trim, e.bytes(), out, workspace, record_dev, start_event,
+                                            stop_event))
+        return set_error(DPWA_ERR_ARG, "%s: %s", fn, why);
+    return run_consensus(e, payloads, count, trim, out, workspace, record_dev, stream, start_event, stop_event);
+}
+
+static int consensus_mixed(const char *fn, const dpwa_layout *layout, const void *const *payloads, int count,
+                           const int *trim, void *out, void *workspace, dpwa_consensus_record *record_dev,
+                           dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (!layout) return set_error(DPWA_ERR_ARG, "%s: NULL layout", fn);
+    if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "%s: %s", fn, why);
+    const Elems e{DPWA_MIXED, layout_bytes(*layout), layout};
+    if (const char *why = consensus_problem(payloads, count, trim, e.bytes(), out, workspace, record_dev, start_event,
+                                            stop_event))
+        return set_error(DPWA_ERR_ARG, "%s: %s", fn, why);
+    return run_consensus(e, payloads, count, trim, out, workspace, record_dev, stream, start_event, stop_event);
 }
 
 int dpwa_consensus(int32_t dtype, const void *const *payloads, int count, int64_t n, void *out, void *workspace,
                    dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event)
 {
-    if (dtype == DPWA_MIXED)
-        return set_error(DPWA_ERR_ARG, "dpwa_consensus: a DPWA_MIXED payload needs its layout (dpwa_consensus_mixed)");
-    if (!is_float_dtype(dtype)) return set_error(DPWA_ERR_ARG, "dpwa_consensus: unknown dtype %d", dtype);
-    if (n < 0 || n > INT64_MAX / 4) return set_error(DPWA_ERR_ARG, "dpwa_consensus: n < 0 or too large");
-    const Elems e{dtype, n, nullptr};
-    if (const char *why = consensus_problem(payloads, count, e.bytes(), out, workspace, record_dev, start_event, stop_event))
-        return set_error(DPWA_ERR_ARG, "dpwa_consensus: %s", why);
-    return run_consensus(e, payloads, count, out, workspace, record_dev, stream, start_event, stop_event);
+    return consensus_single("dpwa_consensus", dtype, payloads, count, nullptr, n, out, workspace, record_dev, stream,
+                            start_event, stop_event);
 }
 
 int dpwa_consensus_mixed(const dpwa_layout *layout, const void *const *payloads, int count, void *out, void *workspace,
                          dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event)
 {
-    if (!layout) return set_error(DPWA_ERR_ARG, "dpwa_consensus_mixed: NULL layout");
-    if (const char *why = layout_problem(*layout, -1)) return set_error(DPWA_ERR_ARG, "dpwa_consensus_mixed: %s", why);
-    const Elems e{DPWA_MIXED, layout_bytes(*layout), layout};
-    if (const char *why = consensus_problem(payloads, count, e.bytes(), out, workspace, record_dev, start_event, stop_event))
-        return set_error(DPWA_ERR_ARG, "dpwa_consensus_mixed: %s", why);
-    return run_consensus(e, payloads, count, out, workspace, record_dev, stream, start_event,
-                         stop_event);
+    return consensus_mixed("dpwa_consensus_mixed", layout, payloads, count, nullptr, out, workspace, record_dev, stream,
+                           start_event, stop_event);
+}
+
+int dpwa_consensus_trimmed(int32_t dtype, const void *const *payloads, int count, int trim, int64_t n, void *out,
+                           void *workspace, dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event,
+                           void *stop_event)
+{
+    return consensus_single("dpwa_consensus_trimmed", dtype, payloads, count, &trim, n, out, workspace, record_dev,
+                            stream, start_event, stop_event);
+}
+
+int dpwa_consensus_trimmed_mixed(const dpwa_layout *layout, const void *const *payloads, int count, int trim, void *out,
+                                 void *workspace, dpwa_consensus_record *record_dev, dpwa_stream_t stream,
+                                 void *start_event, void *stop_event)
+{
+    return consensus_mixed("dpwa_consensus_trimmed_mixed", layout, payloads, count, &trim, out, workspace, record_dev,
+                           stream, start_event, stop_event);
 }
 
 }  // extern "C"

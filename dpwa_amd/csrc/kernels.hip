@@ -53,6 +53,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "kernels.hpp"
 #include "policy.hpp"
@@ -2669,14 +2670,239 @@ __global__ __launch_bounds__(kStreamBlock) void k_consensus_mixed(ConsensusArgs 
     if constexpr (TRACK) cons_commit<U>(a.acc, blockIdx.x, n2, sp);
 }
 
+// ---- the trimmed consensus (include/dpwa_hip.h dpwa_consensus_trimmed, where the rule is fixed to the bit)
+// The centre of U = 3..8 members with the t smallest and t largest values of every element dropped,
+// 1 <= t <= (U - 1) / 2 (the median at the upper end), and every sum against that centre:
+//   key(x) = bits ^ (sign ? all-ones : sign-bit), compared unsigned: -NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN
+//   y_0 <= .. <= y_{U-1}   the U values in key order (equal keys are equal bits: ties need no rule)
+//   s = ((y_t + y_{t+1}) + ..) + y_{U-t-1}    widened exactly to fp64, fp64 adds, ascending
+//   m = s * r              r = 1.0 / (U - 2t) from the host;  out = f32(m), then cons_pack: the mean's two roundings
+//   norm2 += m * m         spread2_i += (x_i - m) * (x_i - m) for EVERY member i, trimmed or not
+// k_consensus's shape (spans, loads first, one store, zeros past the end, tail in workgroup 0, commit);
+// what is new sits between the loads and the sums, one dword of every member at a time, all in VGPRs:
+//   keys     fp32: v_ashrrev_i32, v_or, v_xor.  bf16 / fp16: the same three PACKED 16-bit instructions on the
+//            dword, so both elements of a dword are keyed -- and then sorted -- at once (widening a 16-bit
+//            value to fp32 is monotone in the key order, so the 16-bit key orders as the fp32 one would)
+//   sort     a fixed compare-exchange network of optimal size (3, 5, 9, 12, 16, 19 exchanges for
+//            U = 3..8), fully unrolled: one v_min_u32 / v_max_u32 pair per exchange, or one
+//            v_pk_min_u16 / v_pk_max_u16 pair for two elements.  No LDS, no cross-lane traffic, no
+//            branch on data.  U = 3 fp32 needs the median only: one v_med3_u32, no network
+//   values   the inverse xor, and only y_1 .. y_{U-2} are widened: y_0 and y_{U-1} are trimmed by every t
+//   sum      t is a kernel argument (uniform), not a template argument: the middle values every t keeps
+//            are added unconditionally, the others under the uniform predicate t <= i < U - t, from
+//            s = -0.0 -- (-0.0) + x is x to the bit for every x, -0.0 and NaN included
+// A lane past the end holds zeros in every member: their centre is +0.0 and every term is 0.
+typedef uint16_t u16x2v __attribute__((ext_vector_type(2)));
+typedef int16_t i16x2v __attribute__((ext_vector_type(2)));
+
+struct CxPair { int a, b; };
+template <int U> struct SortNet;
+template <> struct SortNet<3> { static constexpr CxPair cx[3] = {{0, 2}, {0, 1}, {1, 2}}; };
+template <> struct SortNet<4> { static constexpr CxPair cx[5] = {{0, 2}, {1, 3}, {0, 1}, {2, 3}, {1, 2}}; };
+template <> struct SortNet<5> {
+    static constexpr CxPair cx[9] = {{0, 3}, {1, 4}, {0, 2}, {1, 3}, {0, 1}, {2, 4}, {1, 2}, {3, 4}, {2, 3}};
+};
+template <> struct SortNet<6> {
+    static constexpr CxPair cx[12] = {{0, 5}, {1, 3}, {2, 4}, {1, 2}, {3, 4}, {0, 3}, {2, 5}, {0, 1}, {2, 3}, {4, 5}, {1, 2},
+                                      {3, 4}};
+};
+template <> struct SortNet<7> {
+    static constexpr CxPair cx[16] = {{0, 6}, {2, 3}, {4, 5}, {0, 2}, {1, 4}, {3, 6}, {0, 1}, {2, 5},
+                                      {3, 4}, {1, 2}, {4, 6}, {2, 3}, {4, 5}, {1, 2}, {3, 4}, {5, 6}};
+};
+template <> struct SortNet<8> {
+    static constexpr CxPair cx[19] = {{0, 2}, {1, 3}, {4, 6}, {5, 7}, {0, 4}, {1, 5}, {2, 6}, {3, 7}, {0, 1}, {2, 3},
+                                      {4, 5}, {6, 7}, {2, 4}, {3, 5}, {1, 4}, {3, 6}, {1, 2}, {3, 4}, {5, 6}};
+};
+
+// The zero-one principle, at compile time: a network that sorts every 0/1 input sorts every input.
+template <int U> constexpr bool sorts_every_input()
+{
+    for (unsigned in = 0; in < (1u << U); ++in) {
+        unsigned v = in;
+        for (const CxPair &p : SortNet<U>::cx) {
+            const unsigned a = (v >> p.a) & 1, b = (v >> p.b) & 1;
+            v = (v & ~((1u << p.a) | (1u << p.b))) | ((a & b) << p.a) | ((a | b) << p.b);
+        }
+        for (int i = 0; i + 1 < U; ++i)
+            if (((v >> i) & 1) > ((v >> (i + 1)) & 1)) return false;
+    }
+    return true;
+}
+static_assert(sorts_every_input<3>() && sorts_every_input<4>() && sorts_every_input<5>() && sorts_every_input<6>() &&
+                  sorts_every_input<7>() && sorts_every_input<8>(),
+              "a consensus network does not sort");
+
+// A dword of the payload -> its key(s) and back; the exchange.  16-bit types: both halves at once.
+__device__ __forceinline__ uint32_t trim_key(OpsF32, uint32_t w) { return w ^ ((uint32_t)((int32_t)w >> 31) | 0x80000000u); }
+__device__ __forceinline__ uint32_t trim_unkey(OpsF32, uint32_t k) { return k ^ ((uint32_t)((int32_t)~k >> 31) | 0x80000000u); }
+__device__ __forceinline__ void trim_cx(OpsF32, uint32_t &a, uint32_t &b)
+{
+    const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+    a = lo;
+    b = hi;
+}
+__device__ __forceinline__ uint32_t trim_key16(uint32_t w)
+{
+    const u16x2v m = __builtin_bit_cast(u16x2v, __builtin_bit_cast(i16x2v, w) >> 15) | (uint16_t)0x8000;
+    return w ^ __builtin_bit_cast(uint32_t, m);
+}
+__device__ __forceinline__ void trim_cx16(uint32_t &a, uint32_t &b)
+{
+    const u16x2v x = __builtin_bit_cast(u16x2v, a), y = __builtin_bit_cast(u16x2v, b);
+    a = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(x, y));
+    b = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(x, y));
+}
+__device__ __forceinline__ uint32_t trim_key(OpsBF16, uint32_t w) { return trim_key16(w); }
+__device__ __forceinline__ uint32_t trim_key(OpsF16, uint32_t w) { return trim_key16(w); }
+__device__ __forceinline__ uint32_t trim_unkey16(uint32_t k)
+{
+    const u16x2v m = __builtin_bit_cast(u16x2v, __builtin_bit_cast(i16x2v, ~k) >> 15) | (uint16_t)0x8000;
+    return k ^ __builtin_bit_cast(uint32_t, m);
+}
+__device__ __forceinline__ uint32_t trim_unkey(OpsBF16, uint32_t k) { return trim_unkey16(k); }
+__device__ __forceinline__ uint32_t trim_unkey(OpsF16, uint32_t k) { return trim_unkey16(k); }
+__device__ __forceinline__ void trim_cx(OpsBF16, uint32_t &a, uint32_t &b) { trim_cx16(a, b); }
+__device__ __forceinline__ void trim_cx(OpsF16, uint32_t &a, uint32_t &b) { trim_cx16(a, b); }
+
+// the network of U over y, every index a constant
+template <class Ops, int U, size_t... J>
+__device__ __forceinline__ void trim_sort(uint32_t (&y)[U], std::index_sequence<J...>)
+{
+    (trim_cx(Ops{}, y[SortNet<U>::cx[J].a], y[SortNet<U>::cx[J].b]), ...);
+}
+
+// element h of a payload dword, widened exactly to fp64 (h = 0 for fp32)
+__device__ __forceinline__ double cons_word(OpsF32, uint32_t w, int) { return (double)__uint_as_float(w); }
+__device__ __forceinline__ double cons_word(OpsBF16, uint32_t w, int h) { return (double)(h ? bf_hi(w) : bf_lo(w)); }
+__device__ __forceinline__ double cons_word(OpsF16, uint32_t w, int h)
+{
+    const f16x2v v = __builtin_bit_cast(f16x2v, w);
+    return (double)(h ? v.y : v.x);
+}
+
+// One dword of every member, in member order: its H elements' centres into f[0..H), TRACK: their terms.
+template <class Ops, int U, bool TRACK, int H>
+__device__ __forceinline__ void trim_word(const uint32_t (&w)[U], int t, double r, float *f, double &n2, double (&sp)[U])
+{
+    constexpr int TMAX = (U - 1) / 2;   // y_i with TMAX <= i < U - TMAX is kept whatever t
+    uint32_t y[U];
+    if constexpr (U == 3 && std::is_same<Ops, OpsF32>::value) {
+        const uint32_t a = trim_key(Ops{}, w[0]), b = trim_key(Ops{}, w[1]), c = trim_key(Ops{}, w[2]);
+        const uint32_t lo = a < b ? a : b, hi = a < b ? b : a, up = lo < c ? c : lo;   // max(min(a, b), c)
+        y[1] = trim_unkey(Ops{}, hi < up ? hi : up);                                  // v_med3_u32
+    } else {
+#pragma unroll
+        for (int i = 0; i < U; ++i) y[i] = trim_key(Ops{}, w[i]);
+        trim_sort<Ops, U>(y, std::make_index_sequence<sizeof(SortNet<U>::cx) / sizeof(CxPair)>{});
+#pragma unroll
+        for (int i = 1; i < U - 1; ++i) y[i] = trim_unkey(Ops{}, y[i]);
+    }
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        double s = -0.0;
+#pragma unroll
+        for (int i = 1; i < U - 1; ++i) {
+            const double v = cons_word(Ops{}, y[i], h);
+            if (i >= TMAX && i < U - TMAX) s = s + v;
+            else s = (i >= t && i < U - t) ? s + v : s;
+        }
+        const double m = s * r;
+        if constexpr (TRACK) {
+            n2 = n2 + m * m;
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                const double d = cons_word(Ops{}, w[i], h) - m;
+                sp[i] = sp[i] + d * d;
+            }
+        }
+        f[h] = (float)m;
+    }
+}
+
+// A lane's item of every member -> the item of the centre.
+template <class Ops, int U, bool TRACK>
+__device__ __forceinline__ u32x4 trim_item(const u32x4 (&v)[U], int t, double r, double &n2, double (&sp)[U])
+{
+    constexpr int H = Ops::PER / 4;
+    float f[Ops::PER];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        uint32_t w[U];
+#pragma unroll
+        for (int i = 0; i < U; ++i) w[i] = v[i][d];
+        trim_word<Ops, U, TRACK, H>(w, t, r, f + d * H, n2, sp);
+    }
+    return cons_pack(Ops{}, f);
+}
+
+template <class Ops, int U, bool STORE, bool TRACK>
+__global__ __launch_bounds__(kStreamBlock) void k_consensus_trimmed(ConsensusArgs a, int64_t n, int t)
+{
+    using S = typename Ops::S;
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t vbytes = n / Ops::PER * 16;
+    const int64_t off = (int64_t)blockIdx.x * SPAN;
+    const int lane_off = threadIdx.x * 16;
+    u32x4 v[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j)   // all loads first
+        v[j] = span_load<u32x4>(span_rsrc<SPAN>(a.src[j], off, vbytes), lane_off);
+    __builtin_amdgcn_sched_barrier(0);
+    [[maybe_unused]] double n2 = 0.0, sp[U];
+#pragma unroll
+    for (int i = 0; i < U; ++i) sp[i] = 0.0;
+    const u32x4 centre = trim_item<Ops, U, TRACK>(v, t, a.r, n2, sp);
+    if constexpr (STORE) span_store<u32x4>(span_rsrc<SPAN>(a.out, off, vbytes), lane_off, centre);
+    const int64_t tail = n / Ops::PER * Ops::PER;
+    if (blockIdx.x == 0 && threadIdx.x < n - tail) {   // one element in the low half of a dword; the other half zeros
+        const int64_t j = tail + threadIdx.x;
+        uint32_t w[U];
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            const S x = reinterpret_cast<const S *>(a.src[i])[j];
+            if constexpr (sizeof(S) == 4) w[i] = __float_as_uint(x);
+            else w[i] = x;
+        }
+        float f;
+        trim_word<Ops, U, TRACK, 1>(w, t, a.r, &f, n2, sp);
+        if constexpr (STORE) reinterpret_cast<S *>(a.out)[j] = cons_pack_s(Ops{}, f);
+    }
+    if constexpr (TRACK) cons_commit<U>(a.acc, blockIdx.x, n2, sp);
+}
+
+// Over a segmented payload, as k_consensus_mixed: the span's element type under a uniform branch.
+template <int U, bool STORE, bool TRACK>
+__global__ __launch_bounds__(kStreamBlock) void k_consensus_trimmed_mixed(ConsensusArgs a, int64_t total, SegTable segs, int t)
+{
+    constexpr int SPAN = kStreamBlock * 16;
+    const int64_t off = (int64_t)blockIdx.x * SPAN;
+    const int lane_off = threadIdx.x * 16;
+    u32x4 v[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) v[j] = span_load<u32x4>(span_rsrc<SPAN>(a.src[j], off, total), lane_off);
+    __builtin_amdgcn_sched_barrier(0);
+    [[maybe_unused]] double n2 = 0.0, sp[U];
+#pragma unroll
+    for (int i = 0; i < U; ++i) sp[i] = 0.0;
+    const int32_t dtype = seg_dtype(segs, off);
+    u32x4 centre;
+    if (dtype == DPWA_F32) centre = trim_item<OpsF32, U, TRACK>(v, t, a.r, n2, sp);
+    else if (dtype == DPWA_BF16) centre = trim_item<OpsBF16, U, TRACK>(v, t, a.r, n2, sp);
+    else centre = trim_item<OpsF16, U, TRACK>(v, t, a.r, n2, sp);
+    if constexpr (STORE) span_store<u32x4>(span_rsrc<SPAN>(a.out, off, total), lane_off, centre);
+    if constexpr (TRACK) cons_commit<U>(a.acc, blockIdx.x, n2, sp);
+}
+
 // Finishing (one workgroup behind the pass on the same stream, as k_distance_finish): lane i loads
 // and zeroes row i, the sums are taken in a fixed order -- the butterfly inside each wave, then the
-// waves in order, then spread2 over the members in order -- and the record is written whole.
+// waves in order, then spread2 over the members in order -- and the record is written whole
+// (`reserved`: the trim of a trimmed pass, 0 from the mean's).
 constexpr int kConsensusSums = kMaxConsensus + 1;
 
 __global__ __launch_bounds__(kDistFinishBlock) void k_consensus_finish(double *__restrict__ acc,
                                                                        dpwa_consensus_record *__restrict__ out, int64_t n,
-                                                                       int32_t members, uint64_t version)
+                                                                       int32_t members, uint64_t version, int32_t reserved)
 {
     __shared__ double s_sum[kConsensusSums][kDistFinishBlock / 64];
     double *a = acc + (size_t)threadIdx.x * kDistAccStride;
@@ -2709,7 +2935,7 @@ __global__ __launch_bounds__(kDistFinishBlock) void k_consensus_finish(double *_
     out->spread2 = spread2;
     out->n = n;
     out->members = members;
-    out->reserved = 0;
+    out->reserved = reserved;
     out->version = version;
 #pragma unroll
     for (int k = 0; k < (int)(sizeof(out->pad) / sizeof(out->pad[0])); ++k) out->pad[k] = 0;
@@ -2722,21 +2948,29 @@ static bool overlaps(const void *p, const void *q, int64_t bytes)
     return a < b + (uintptr_t)bytes && b < a + (uintptr_t)bytes;
 }
 
-hipError_t launch_consensus(const Elems &e, const void *const *src, int count, double r, void *out, double *acc,
-                            bool remote, hipStream_t s, const LaunchTiming *timing)
+// What launch_consensus and launch_consensus_trimmed refuse alike; accepted, the kernels' arguments in `a`.
+static bool consensus_args(const Elems &e, const void *const *src, int count, double r, void *out, double *acc,
+                           ConsensusArgs &a)
 {
-    if (count < 1 || count > kMaxConsensus || !src || (!out && !acc) || !aligned16(out, acc)) return hipErrorInvalidValue;
-    if (!e.segmented() && (e.n < 0 || !is_float_dtype(e.dtype))) return hipErrorInvalidValue;
-    if (e.segmented() && (!e.layout || layout_problem(*e.layout, -1))) return hipErrorInvalidValue;
+    if (count < 1 || count > kMaxConsensus || !src || (!out && !acc) || !aligned16(out, acc)) return false;
+    if (!e.segmented() && (e.n < 0 || !is_float_dtype(e.dtype))) return false;
+    if (e.segmented() && (!e.layout || layout_problem(*e.layout, -1))) return false;
     const int64_t bytes = e.segmented() ? layout_bytes(*e.layout) : e.bytes();
-    ConsensusArgs a{};
     for (int i = 0; i < count; ++i) {
-        if (absent_or_unaligned(src[i]) || (out && (src[i] == out || overlaps(src[i], out, bytes)))) return hipErrorInvalidValue;
+        if (absent_or_unaligned(src[i]) || (out && (src[i] == out || overlaps(src[i], out, bytes)))) return false;
         a.src[i] = src[i];
     }
     a.out = out;
     a.acc = acc;
     a.r = r;
+    return true;
+}
+
+hipError_t launch_consensus(const Elems &e, const void *const *src, int count, double r, void *out, double *acc,
+                            bool remote, hipStream_t s, const LaunchTiming *timing)
+{
+    ConsensusArgs a{};
+    if (!consensus_args(e, src, count, r, out, acc, a)) return hipErrorInvalidValue;
     const bool store = out != nullptr, track = acc != nullptr;
     const auto acquire = [&] {   // (after every refusal: a refused launch queues nothing)
         if (remote) hipLaunchKernelGGL(k_acquire_system, dim3(256), dim3(64), 0, s);
@@ -2762,11 +2996,42 @@ hipError_t launch_consensus(const Elems &e, const void *const *src, int count, d
     });
 }
 
-hipError_t launch_consensus_finish(double *acc, dpwa_consensus_record *out, int64_t n, int members, uint64_t version,
-                                   hipStream_t s, const LaunchTiming *timing)
+hipError_t launch_consensus_trimmed(const Elems &e, const void *const *src, int count, int trim, double r, void *out,
+                                    double *acc, bool remote, hipStream_t s, const LaunchTiming *timing)
 {
-    if (!acc || !out || members < 1 || members > kMaxConsensus || n < 0) return hipErrorInvalidValue;
-    return launch(k_consensus_finish, dim3(1), dim3(kDistFinishBlock), s, timing, acc, out, n, members, version);
+    ConsensusArgs a{};
+    if (count < 3 || trim < 1 || 2 * trim >= count || !consensus_args(e, src, count, r, out, acc, a))
+        return hipErrorInvalidValue;
+    const bool store = out != nullptr, track = acc != nullptr;
+    const auto acquire = [&] {   // (after every refusal: a refused launch queues nothing)
+        if (remote) hipLaunchKernelGGL(k_acquire_system, dim3(256), dim3(64), 0, s);
+    };
+    return Choice<3, 4, 5, 6, 7, 8>::with(count, [&](auto members) {
+        constexpr int U = decltype(members)::value;
+        if (e.segmented())
+            return with_segments(e, false, [&](int64_t total, dim3 grid, const SegTable &tab) {
+                acquire();
+                return launch(store ? (track ? k_consensus_trimmed_mixed<U, true, true> : k_consensus_trimmed_mixed<U, true, false>)
+                                    : k_consensus_trimmed_mixed<U, false, true>,
+                              grid, dim3(kStreamBlock), s, timing, a, total, tab, trim);
+            });
+        if (e.n == 0) return hipSuccess;
+        return with_ops(e.dtype, [&](auto ops) {
+            using Ops = decltype(ops);
+            if (span_grid<Ops>(e.n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
+            acquire();
+            return launch(store ? (track ? k_consensus_trimmed<Ops, U, true, true> : k_consensus_trimmed<Ops, U, true, false>)
+                                : k_consensus_trimmed<Ops, U, false, true>,
+                          dim3((uint32_t)span_grid<Ops>(e.n, kStreamBlock)), dim3(kStreamBlock), s, timing, a, e.n, trim);
+        });
+    });
+}
+
+hipError_t launch_consensus_finish(double *acc, dpwa_consensus_record *out, int64_t n, int members, uint64_t version,
+                                   hipStream_t s, const LaunchTiming *timing, int reserved)
+{
+    if (!acc || !out || members < 1 || members > kMaxConsensus || n < 0 || reserved < 0) return hipErrorInvalidValue;
+    return launch(k_consensus_finish, dim3(1), dim3(kDistFinishBlock), s, timing, acc, out, n, members, version, reserved);
 }
 
 // ---------------------------------------------------------------- packed snapshots

@@ -133,12 +133,20 @@ hipError_t launch_lerp_guarded(const Elems &e, void *param, const void *peer, co
 // launch is preceded by the system-scope acquire of launch_pull.  hipErrorInvalidValue, nothing
 // queued: a count outside 1..8, a null or not 16-B aligned pointer, `out` overlapping a source,
 // neither `out` nor `acc`.  There is no unaligned form.
-//   consensus_finish   sums the rows into *out (members = count of the pass) and zeroes them
+//   consensus_trimmed  the trimmed mean in place of the mean (dpwa_consensus_trimmed; kernels.hip "the
+//                      trimmed consensus"): per element the `trim` smallest and largest values dropped,
+//                      the kept ones summed ascending, `r` the host's 1.0 / (count - 2 trim); the sums
+//                      over every member against that centre.  Also refused: count < 3, trim outside
+//                      1..(count - 1) / 2.  A refused launch queues nothing, the acquire of `remote` included
+//   consensus_finish   sums the rows into *out (members = count of the pass) and zeroes them;
+//                      `reserved`: the record's field of that name (the trim of a trimmed pass)
 constexpr int kMaxConsensus = 8;
 hipError_t launch_consensus(const Elems &e, const void *const *src, int count, double r, void *out, double *acc,
                             bool remote, hipStream_t s, const LaunchTiming *timing = nullptr);
+hipError_t launch_consensus_trimmed(const Elems &e, const void *const *src, int count, int trim, double r, void *out,
+                                    double *acc, bool remote, hipStream_t s, const LaunchTiming *timing = nullptr);
 hipError_t launch_consensus_finish(double *acc, dpwa_consensus_record *out, int64_t n, int members, uint64_t version,
-                                   hipStream_t s, const LaunchTiming *timing = nullptr);
+                                   hipStream_t s, const LaunchTiming *timing = nullptr, int reserved = 0);
 
 // The non-finite peer check (kernels.hip "non-finite peer check"): one read of the peer payload; a
 // lane that finds a NaN or an inf stores `stamp` (non-zero) into *veto (device memory, 4-B aligned).

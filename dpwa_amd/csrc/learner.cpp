@@ -2369,13 +2369,16 @@ int dpwa_learner_poll_status(dpwa_learner *l, int *done, int32_t *status)
 // reads is ordered as a zero-copy fetch's source is: behind a local peer's publish mark (RAW), and
 // registered as a reader of the peer's slot, so that the publish or write-through average that
 // rewrites it orders its stream behind this pass (WAR: the learner's consensus_read mark).
-int dpwa_learner_consensus(dpwa_learner *l, const int32_t *peer_ids, int count, uint64_t version, void *out,
-                           dpwa_consensus_record *record_dev, dpwa_stream_t stream)
+// `trim`: of dpwa_learner_consensus_trimmed (the trimmed mean of the same members), null from the mean's entry.
+static int learner_consensus(const char *fn, dpwa_learner *l, const int32_t *peer_ids, int count, const int *trim,
+                             uint64_t version, void *out, dpwa_consensus_record *record_dev, dpwa_stream_t stream)
 {
-    const char *fn = "dpwa_learner_consensus";
     if (!l || !peer_ids) return set_error(DPWA_ERR_ARG, "%s: NULL argument", fn);
     if (count < 1 || count > DPWA_CONSENSUS_MAX)
         return set_error(DPWA_ERR_ARG, "%s: %d members (1..%d)", fn, count, DPWA_CONSENSUS_MAX);
+    if (trim && (count < 3 || *trim < 1 || 2 * *trim >= count))
+        return set_error(DPWA_ERR_ARG, "%s: trim %d of %d members (3..%d members, trim 1..(members - 1) / 2)", fn, *trim,
+                         count, DPWA_CONSENSUS_MAX);
     if ((!out && !record_dev) || !aligned16(out) || ((uintptr_t)record_dev & 7))
         return set_error(DPWA_ERR_ARG, "%s: neither out nor a record, or a misaligned one", fn);
     if (version == 0) return set_error(DPWA_ERR_STATE, "%s: nothing published", fn);
@@ -2442,12 +2445,29 @@ int dpwa_learner_consensus(dpwa_learner *l, const int32_t *peer_ids, int count, 
         if (std::find(rv.begin(), rv.end(), l) == rv.end()) rv.push_back(l);
     }
     double *rows = record_dev ? (double *)l->consensus_rows.h : nullptr;
-    HIP_TRY(launch_consensus(p, src, count, 1.0 / (double)count, out, rows, remote, s));
-    if (record_dev) HIP_TRY(launch_consensus_finish(rows, record_dev, p.elements(), count, version, s));
+    if (trim)
+        HIP_TRY(launch_consensus_trimmed(p, src, count, *trim, 1.0 / (double)(count - 2 * *trim), out, rows, remote, s));
+    else
+        HIP_TRY(launch_consensus(p, src, count, 1.0 / (double)count, out, rows, remote, s));
+    if (record_dev)
+        HIP_TRY(launch_consensus_finish(rows, record_dev, p.elements(), count, version, s, nullptr, trim ? *trim : 0));
     // WAR: whoever rewrites a slot read here finds this learner among the slot's readers and orders its
     // stream behind this mark (wait_slot_readers), whatever the learner's fetches do to theirs meanwhile.
     l->consensus_read.note(s);
     return DPWA_OK;
+}
+
+int dpwa_learner_consensus(dpwa_learner *l, const int32_t *peer_ids, int count, uint64_t version, void *out,
+                           dpwa_consensus_record *record_dev, dpwa_stream_t stream)
+{
+    return learner_consensus("dpwa_learner_consensus", l, peer_ids, count, nullptr, version, out, record_dev, stream);
+}
+
+int dpwa_learner_consensus_trimmed(dpwa_learner *l, const int32_t *peer_ids, int count, int trim, uint64_t version,
+                                   void *out, dpwa_consensus_record *record_dev, dpwa_stream_t stream)
+{
+    return learner_consensus("dpwa_learner_consensus_trimmed", l, peer_ids, count, &trim, version, out, record_dev,
+                             stream);
 }
 
 }  // extern "C"

@@ -777,7 +777,7 @@ class DpwaConnection:
             return NonfiniteElements(0, 0, 0, 0.0)
         return NonfiniteElements(*self._learner.heal_record())
 
-    def consensus(self, out=None, distance=True, members=None):
+    def consensus(self, out=None, distance=True, members=None, trim=0):
         """The group's consensus model and consensus distance (extension, opt-in, read-only;
         dpwa_amd/consensus.py): the element-wise mean of the snapshots this node and its peers
         published in the current round -- the model to evaluate and save -- and how far the members
@@ -792,9 +792,17 @@ class DpwaConnection:
         (pulls 'copy', 'kernel', 'relay') every rank reads the mapped slots behind the round's
         barrier and gets the same bits.  ValueError: free-running ranks (AsyncDistGroup),
         ``pull='relay-avg'``, the wire transport, more than 8 members.  The call changes no
-        parameter, slot, clock, scheduler state or distance record."""
+        parameter, slot, clock, scheduler state or distance record.
+
+        ``trim`` (an int >= 0, or ``"median"`` = ``(G - 1) // 2``): the coordinate-wise trimmed mean
+        in place of the mean -- per element the ``trim`` smallest and largest of the G values are
+        dropped (a NaN or inf sorts to an end) and the rest averaged, and every ``member_spread2``
+        is taken against that centre, so one bad replica is named, not averaged in.  Same single
+        pass; an effective trim of 0 (also ``"median"`` of 1 or 2 members) is the mean's call,
+        unchanged.  ValueError before anything is launched: ``2 * trim >= G``.  ``Consensus.trim``
+        is the effective value."""
         from .consensus import consensus
-        return consensus(self, out, distance, members)
+        return consensus(self, out, distance, members, trim)
 
     def synchronize(self):
         """Waits for the device and raises a deferred ZeroDivisionError, if any."""

@@ -90,8 +90,13 @@ def main(argv=None):
                     help="print the group's relative consensus distance every 100 steps and save the consensus model "
                          "(the mean of the replicas' snapshots, adapter.consensus()) as a state_dict at the end; "
                          "several ranks need --gossip lockstep")
+    ap.add_argument("--consensus-trim", default="0", metavar="T|median",
+                    help="with --consensus: the trimmed mean in place of the mean -- per element the T smallest and "
+                         "largest values are dropped ('median': as many as the members allow), so that one bad replica "
+                         "is named by the spreads, not averaged in (adapter.consensus(trim=...)); 2 T < replicas")
     ap.add_argument("--consensus-out", default=None, help="where --consensus saves (default: a temporary directory)")
     args = ap.parse_args(argv)
+    trim = args.consensus_trim if args.consensus_trim == "median" else int(args.consensus_trim)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.consensus and world > 1 and args.gossip != "lockstep":      # (said by every rank, before any starts)
@@ -143,7 +148,7 @@ def main(argv=None):
                 for i, a in enumerate(adapters):
                     a.update_send(losses[i])       # a device tensor: no host sync
                 if args.consensus and step % 100 == 0 and rank == 0:     # (this read waits for the device)
-                    c = adapters[0].consensus(out=False)
+                    c = adapters[0].consensus(out=False, trim=trim)
                     print("step %d, version %d: relative consensus distance of %d replicas %.3g"
                           % (step, c.version, len(c.members), c.relative), file=sys.stderr)
             if not args.resident:                  # the reference's order (README.md:18-29)
@@ -190,7 +195,7 @@ def main(argv=None):
         for i, a in enumerate(adapters):
             a.update_send(2.3)
         if rank == 0:
-            c = adapters[0].consensus()
+            c = adapters[0].consensus(trim=trim)
             state = {k: v.detach().clone() for k, v in nets[0].state_dict().items()}     # buffers: replica 0's
             state.update({k: v.clone() for k, v in c.parameters().items()})
             path = args.consensus_out or os.path.join(tempfile.mkdtemp(), "resnet18_consensus.pt")

@@ -53,7 +53,9 @@ extern "C" {
  * dpwa_learner_pack_counts, dpwa_learner_pack_image.
  * Still 11, by additions only: healing non-finite elements inside the averaging kernel (dpwa_heal_record) --
  * dpwa_average_guarded, dpwa_average_guarded_mixed, dpwa_learner_set_heal, dpwa_learner_heal_record,
- * dpwa_node_set_heal. */
+ * dpwa_node_set_heal.
+ * Still 11, by additions only: the trimmed consensus (dpwa_consensus_record.reserved carries the trim) --
+ * dpwa_consensus_trimmed, dpwa_consensus_trimmed_mixed, dpwa_learner_consensus_trimmed. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -346,7 +348,7 @@ typedef struct dpwa_consensus_record {
     double member_spread2[DPWA_CONSENSUS_MAX];   /* in the order of the payloads; 0 beyond `members` */
     int64_t n;
     int32_t members;
-    int32_t reserved;
+    int32_t reserved;                            /* the trim of a trimmed pass (below), else 0 */
     uint64_t version;
     uint64_t pad[3];
 } dpwa_consensus_record;
@@ -355,6 +357,35 @@ int dpwa_consensus(int32_t dtype, const void *const *payloads, int count, int64_
                    dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
 int dpwa_consensus_mixed(const dpwa_layout *layout, const void *const *payloads, int count, void *out, void *workspace,
                          dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event, void *stop_event);
+
+/* The trimmed consensus (extension, opt-in, read-only): the coordinate-wise trimmed mean in place of the
+ * mean, so that one bad member -- a NaN, an inf, a replica that diverged finitely -- neither reaches the
+ * stored model nor drags the centre every member_spread2 is taken against.  Still one read of every
+ * payload, still bit-exact, and independent of the order of the members.  For count = G members
+ * (3..DPWA_CONSENSUS_MAX) and trim = t with 1 <= t <= (G - 1) / 2, for every element j:
+ *   order   the G values by the total order on their bit patterns: key(x) = bits ^ (sign ? all-ones :
+ *           sign-bit), compared unsigned, i.e. -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.  For bf16 and
+ *           fp16 the key is formed on the 16-bit pattern (widening to fp32 is monotone in this order).  Equal
+ *           keys are equal bit patterns, so ties need no rule.
+ *   kept    y_t ... y_{G-t-1} of the ascending sequence y_0 <= ... <= y_{G-1}
+ *   s = ((y_t + y_{t+1}) + ...) + y_{G-t-1}   each operand widened exactly to fp64, fp64 adds, ascending
+ *   m = s * r                                 r = the fp64 1.0 / (G - 2t), formed once on the host
+ *   out[j] = f32(m), round to nearest even, subnormals kept; a bf16 / fp16 payload then rounds that fp32
+ *            value to nearest even once more -- dpwa_consensus's two roundings
+ *   norm2 = sum m^2      member_spread2[i] = sum (x_i[j] - m)^2 for EVERY member i, trimmed or not
+ * all in fp64 against the fp64 m, added and finished as dpwa_consensus's (same workspace, left zero).  The
+ * median of an odd G is t = (G - 1) / 2, one value kept; of an even G the two middle values are kept.
+ * A non-finite value that is trimmed does not reach m; one that is kept makes m non-finite, as in the mean.
+ * A member's own NaN still makes its own member_spread2 (and spread2) NaN: that names the member.
+ * The record is dpwa_consensus's, with `reserved` = t (0 from the untrimmed entries).  Arguments and
+ * DPWA_ERR_ARG as dpwa_consensus / dpwa_consensus_mixed, and also, nothing queued: count < 3, trim < 1,
+ * 2 * trim >= count. */
+int dpwa_consensus_trimmed(int32_t dtype, const void *const *payloads, int count, int trim, int64_t n, void *out,
+                           void *workspace, dpwa_consensus_record *record_dev, dpwa_stream_t stream, void *start_event,
+                           void *stop_event);
+int dpwa_consensus_trimmed_mixed(const dpwa_layout *layout, const void *const *payloads, int count, int trim, void *out,
+                                 void *workspace, dpwa_consensus_record *record_dev, dpwa_stream_t stream,
+                                 void *start_event, void *stop_event);
 
 /* Packed snapshots (extension, opt-in): an int8 block-scaled image of a single-dtype payload, which a
  * publisher keeps beside each snapshot and a peer pulls in place of the payload (DPWA_PULL_PACKED), so
@@ -761,6 +792,10 @@ int dpwa_learner_heal_record(dpwa_learner *l, dpwa_heal_record *out);
  * with a fused relay phase pending (no contiguous snapshot exists). */
 int dpwa_learner_consensus(dpwa_learner *l, const int32_t *peer_ids, int count, uint64_t version, void *out,
                            dpwa_consensus_record *record_dev, dpwa_stream_t stream);
+/* The trimmed consensus (dpwa_consensus_trimmed above) of the same members: same ordering, reader
+ * registration and refusals, and DPWA_ERR_ARG also for count < 3, trim < 1 or 2 * trim >= count. */
+int dpwa_learner_consensus_trimmed(dpwa_learner *l, const int32_t *peer_ids, int count, int trim, uint64_t version,
+                                   void *out, dpwa_consensus_record *record_dev, dpwa_stream_t stream);
 
 /* always != 0: a write-through average never writes the next publish's header ahead; that
  * publish then writes it with the loss given to it (a snapshot served over the wire bridge
