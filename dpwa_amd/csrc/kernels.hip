@@ -19,10 +19,10 @@
 //             also writes the new clock (into the other half of a double-buffered clock,
 //             so no workgroup ever reads a clock another one is writing) and dpwa_coef.
 //  * mixed:   the same pass over the segmented payload of a model that mixes float32, bfloat16
-//             and float16 parameters (k_lerp_mixed): each one-wave span rounds as its segment's type.
+//             and float16 parameters (k_lerp<OpsMixed, ..., SegTable>): each one-wave span rounds as its segment's type.
 //  * distance: opt-in -- the round's distance to the peer, sum (q - p)^2 and sum p^2 in fp64, formed
 //             by a tracked form of the fused average from the operands it holds anyway
-//             (k_lerp_tracked), or by a stand-alone pass (k_distance*), added across workgroups with
+//             (k_lerp<..., DistTrack>), or by a stand-alone pass (k_distance*), added across workgroups with
 //             the hardware fp64 add and finished by k_distance_finish.
 //             Opt-in too: the same sums for every parameter tensor over its own elements, by a
 //             stand-alone pass that looks each span's tensors up in a device table
@@ -31,7 +31,7 @@
 //             (k_peer_finite*), a test on the exponent bits; a lane that finds a NaN or an inf
 //             stores the round's stamp into the learner's veto word, and the factor of a round
 //             whose stamp it finds there is the no-op's, with a status of its own.
-//  * healing: opt-in -- guarded forms of the single-learner average (k_lerp_guarded*) that select every
+//  * healing: opt-in -- guarded forms of the single-learner average (k_lerp<..., HealGuard>) that select every
 //             result element by the exponent bits of q and p: never a NaN or an inf from the peer, a NaN
 //             or an inf of our own replaced by the peer's finite element, both counted.
 //  * factor:  the same fp64 math as a one-thread kernel for the split API.
@@ -597,14 +597,16 @@ __device__ __forceinline__ void dist_commit(double *acc, uint32_t index, double 
     if (lane < 2) unsafeAtomicAdd(acc + (size_t)(index % kDistAccs) * kDistAccStride + lane, lane ? n2 : d2);
 }
 
-// What lerp_span does about the distance: nothing (every averaging kernel but k_lerp_tracked), or
-// the sums above into `acc`.
+// What lerp_span does about the distance: nothing (every averaging kernel but the tracked k_lerp), or
+// the sums above into `acc`.  (Arg: what k_lerp takes for it as a kernel argument.)
 struct NoTrack {
     static constexpr bool ON = false;
 };
 struct DistTrack {
     static constexpr bool ON = true;
+    using Arg = double *__restrict__;
     double *acc;
+    operator double *() const { return acc; }
 };
 
 // ---------------------------------------------------------------- healing non-finite elements
@@ -631,7 +633,9 @@ struct NoGuard {
 };
 struct HealGuard {
     static constexpr bool ON = true;
+    using Arg = dpwa_heal_record *__restrict__;
     dpwa_heal_record *rec;
+    operator dpwa_heal_record *() const { return rec; }
 };
 
 __device__ __forceinline__ uint32_t bad_mask_f32(uint32_t w) { return (w & 0x7f800000u) == 0x7f800000u ? 0xffffffffu : 0u; }
@@ -780,20 +784,13 @@ __device__ __forceinline__ void lerp_span(uint32_t blk, typename Ops::V *__restr
     if constexpr (Guard::ON) heal_commit(guard.rec, blk == 0, counts, new_clock);
 }
 
-template <class Ops, int MODE, bool DUAL, int BLOCK = kBlock, int POLICY = 0, bool OOP = false>
-__global__ __launch_bounds__(BLOCK) void k_lerp(typename Ops::V *__restrict__ param,
-                                                const typename Ops::V *__restrict__ peer, int64_t n, LerpArgs args)
-{
-    lerp_span<Ops, MODE, DUAL, BLOCK, POLICY, ContigSrc, OOP>(blockIdx.x, param, ContigSrc{(const char *)peer}, n,
-                                                              args);
-}
-
 // ---------------------------------------------------------------- segmented (DPWA_MIXED) payloads
 // A model that mixes float32, bfloat16 and float16 parameters has a payload of up to three
 // segments, one per type, each a whole number of 4-KiB blocks (dpwa_layout, include/dpwa_hip.h): a
 // 1-KiB span lies inside one segment.  The table travels by value; unused entries begin at
 // INT64_MAX, so the lookup is two compares whatever the count.
 struct SegTable {
+    using Arg = SegTable;
     int64_t begin[DPWA_LAYOUT_MAX_SEGMENTS];   // ascending, begin[0] = 0
     int32_t dtype[DPWA_LAYOUT_MAX_SEGMENTS];
 };
@@ -828,37 +825,8 @@ struct OpsMixed {
     }
 };
 
-// The single-dtype span code (lerp_span: one 16-byte item per lane, loads first, the fp64 factor
-// by every lane while they are in flight, the commit by one lane of the grid -- of global
-// workgroup 0, not of the first workgroup of each segment -- and the no-op round) for a
-// segmented payload: the span's element op is chosen by the span's byte offset (not by the
-// workgroup index: right for any span order).  No unaligned form, and the grid is exact.
-// One-wave workgroups.
-template <int MODE, bool DUAL, int POLICY, bool OOP>
-__global__ __launch_bounds__(kStreamBlock) void k_lerp_mixed(u32x4 *__restrict__ param,
-                                                             const u32x4 *__restrict__ peer, int64_t total,
-                                                             LerpArgs args, SegTable segs)
-{
-    const ContigSrc src{(const char *)peer};
-    const OpsMixed ops{segs, src.span_of<kStreamBlock * 16>(blockIdx.x)};
-    lerp_span<OpsMixed, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP>(blockIdx.x, param, src, total, args, ops);
-}
-
-// The guarded forms of the single-learner average ("healing non-finite elements"): k_lerp's span code with
-// HealGuard, so a good/good element has k_lerp's bits.  Fused (MODE COEF_FUSED: plain, write-through DUAL,
-// resident OOP) and device coefficients (COEF_DEV, the lerp of a split round); one-wave workgroups; the cache
-// policy k_lerp would take (by size; resident: kProductPolicy).  16-B aligned operands only.
-template <class Ops, int MODE, bool DUAL, bool OOP, int POLICY>
-__global__ __launch_bounds__(kStreamBlock) void k_lerp_guarded(typename Ops::V *__restrict__ param,
-                                                               const typename Ops::V *__restrict__ peer, int64_t n,
-                                                               LerpArgs args, dpwa_heal_record *__restrict__ rec)
-{
-    lerp_span<Ops, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP, NoTrack, HealGuard>(
-        blockIdx.x, param, ContigSrc{(const char *)peer}, n, args, Ops{}, NoTrack{}, HealGuard{rec});
-}
-
-// The same over a segmented payload: the span's test, like its lerp, is its segment's (seg_dtype from the
-// span's byte offset, as k_lerp_mixed; padding bytes are zeros on both sides: good, and they stay zeros).
+// The same test over a segmented payload: the span's test, like its lerp, is its segment's (seg_dtype from the
+// span's byte offset; padding bytes are zeros on both sides: good, and they stay zeros).
 __device__ __forceinline__ u32x4 heal_item(const OpsMixed &ops, u32x4 q, u32x4 p, u32x4 r, uint32_t &counts)
 {
     const int32_t dtype = seg_dtype(ops.segs, ops.span_off);
@@ -869,29 +837,48 @@ __device__ __forceinline__ u32x4 heal_item(const OpsMixed &ops, u32x4 q, u32x4 p
     return heal_item(OpsF16{}, q, p, r, counts);
 }
 
-template <int MODE, bool DUAL, int POLICY, bool OOP>
-__global__ __launch_bounds__(kStreamBlock) void k_lerp_guarded_mixed(u32x4 *__restrict__ param,
-                                                                     const u32x4 *__restrict__ peer, int64_t total,
-                                                                     LerpArgs args, SegTable segs,
-                                                                     dpwa_heal_record *__restrict__ rec)
+// A trailing kernel argument (Form::Arg) as lerp_span takes it: the table itself, DistTrack{acc}, HealGuard{rec}.
+template <class Form> __device__ __forceinline__ decltype(auto) as_form(const typename Form::Arg &a)
 {
-    const ContigSrc src{(const char *)peer};
-    const OpsMixed ops{segs, src.span_of<kStreamBlock * 16>(blockIdx.x)};
-    lerp_span<OpsMixed, MODE, DUAL, kStreamBlock, POLICY, ContigSrc, OOP, NoTrack, HealGuard>(
-        blockIdx.x, param, src, total, args, ops, NoTrack{}, HealGuard{rec});
+    if constexpr (std::is_same_v<Form, typename Form::Arg>) return (a);
+    else return Form{a};
+}
+// The one of type T among xs (a kernel's trailing arguments, then the defaults of those a form leaves out).
+template <class T, class X, class... Xs> __device__ __forceinline__ const T &arg_of(const X &x, const Xs &...xs)
+{
+    if constexpr (std::is_same_v<T, X>) return x;
+    else return arg_of<T>(xs...);
+}
+// The element op of workgroup `blk`'s span: a segmented payload's finds its segment in the SegTable among xs.
+template <class Ops, int SPAN, class... Xs>
+__device__ __forceinline__ Ops span_ops(const ContigSrc &src, uint32_t blk, const Xs &...xs)
+{
+    if constexpr (std::is_same_v<Ops, OpsMixed>) return OpsMixed{arg_of<SegTable>(xs...), src.span_of<SPAN>(blk)};
+    else return Ops{};
 }
 
-// The tracked form of the single-learner fused average (k_lerp's span code with DistTrack, so the
-// averaged bits are k_lerp's): plain, write-through (DUAL) and resident (OOP), one-wave
-// workgroups, the cache policy k_lerp would take (by size; resident: kProductPolicy).  `acc`: the
-// distance accumulators.
-template <class Ops, bool DUAL, bool OOP, int POLICY>
-__global__ __launch_bounds__(kStreamBlock) void k_lerp_tracked(typename Ops::V *__restrict__ param,
-                                                               const typename Ops::V *__restrict__ peer, int64_t n,
-                                                               LerpArgs args, double *__restrict__ acc)
+// The single-learner average over a contiguous peer payload, every form of it: lerp_span behind the kernel
+// arguments (param, peer, n, args) and, only in the instantiations that use them, in this order
+//     SegTable   a segmented payload (Ops = OpsMixed; `n` counts its bytes): the span's element op is chosen by
+//                the span's byte offset -- not by the workgroup index: right for any span order -- and the
+//                commit is by one lane of the grid, of global workgroup 0, not of each segment's first workgroup;
+//                no ragged tail, no unaligned form, an exact grid, one-wave workgroups
+//     DistTrack  the tracked form of the fused average: the averaged bits are the untracked ones
+//     HealGuard  the guarded forms ("healing non-finite elements"): a good/good element has the unguarded bits;
+//                fused or device coefficients (the lerp of a split round)
+// DistTrack and HealGuard run one-wave workgroups over 16-B aligned operands, and never together: there is no
+// guarded tracked form.  What is launched for which call: "averaging launches" below.
+template <class Ops, int MODE, bool DUAL, int BLOCK = kBlock, int POLICY = 0, bool OOP = false, class... Form>
+__global__ __launch_bounds__(BLOCK) void k_lerp(typename Ops::V *__restrict__ param,
+                                                const typename Ops::V *__restrict__ peer, int64_t n, LerpArgs args,
+                                                typename Form::Arg... form)
 {
-    lerp_span<Ops, COEF_FUSED, DUAL, kStreamBlock, POLICY, ContigSrc, OOP, DistTrack>(
-        blockIdx.x, param, ContigSrc{(const char *)peer}, n, args, Ops{}, DistTrack{acc});
+    using Track = std::conditional_t<(std::is_same_v<Form, DistTrack> || ...), DistTrack, NoTrack>;
+    using Guard = std::conditional_t<(std::is_same_v<Form, HealGuard> || ...), HealGuard, NoGuard>;
+    const ContigSrc src{(const char *)peer};
+    lerp_span<Ops, MODE, DUAL, BLOCK, POLICY, ContigSrc, OOP, Track, Guard>(
+        blockIdx.x, param, src, n, args, span_ops<Ops, BLOCK * 16>(src, blockIdx.x, as_form<Form>(form)...),
+        arg_of<Track>(as_form<Form>(form)..., NoTrack{}), arg_of<Guard>(as_form<Form>(form)..., NoGuard{}));
 }
 
 // The stand-alone distance pass: the same sums with no store to either operand, for the averaging
@@ -1059,7 +1046,7 @@ __global__ __launch_bounds__(kStreamBlock) void k_peer_finite(const void *__rest
 }
 
 // The same over a segmented payload: the span's test is its segment's (seg_dtype from the span's
-// byte offset, as k_lerp_mixed; no ragged tail; padding bytes are zeros, which are finite).
+// byte offset, as the segmented k_lerp; no ragged tail; padding bytes are zeros, which are finite).
 template <int AUX>
 __global__ __launch_bounds__(kStreamBlock) void k_peer_finite_mixed(const u32x4 *__restrict__ peer, int64_t total,
                                                                     SegTable segs, uint32_t *veto, uint32_t stamp)
@@ -1522,7 +1509,7 @@ using PairF32Policies = Choice<kProductPolicy, 0, 1, 2, 16>;   // k_lerp_pair, f
 using Pair16Policies = Choice<kProductPolicy, 0>;              // k_lerp_pair, bfloat16 / float16
 using GroupPolicies = Choice<kProductPolicy, 0>;               // k_lerp_group
 using RelayPolicies = Choice<0, 8>;                            // k_lerp_relay
-// k_lerp_tracked and k_lerp_mixed (not resident), k_stream_mix: the two policies the size chooses between
+// the tracked, guarded and segmented k_lerp (not resident), k_stream_mix: the two policies the size chooses between
 using BySizePolicies = Choice<kProductPolicy, kFitPolicy>;
 
 template <class Policies, int... Ps> constexpr bool launches_as_itself() { return ((Policies::launched(Ps) == Ps) && ...); }
@@ -1542,78 +1529,10 @@ static_assert(launches_as_itself<Lerp64Policies, kFitPolicy, kProductPolicy>() &
 
 // ---------------------------------------------------------------- averaging launches
 // Workgroups of one 16-byte item per lane over n elements; the last span may be empty
-// (range-checked).
-template <class Ops> static int64_t span_grid(int64_t n, int block) { return (n / Ops::PER) / block + 1; }
+// (range-checked).  A payload with no ragged tail (segmented: whole 4-KiB blocks) has an exact grid.
+template <class Ops> static int64_t span_grid(int64_t n, int block) { return (n / Ops::PER) / block + (Ops::TAIL ? 1 : 0); }
 // Workgroups of the grid-stride kernels for operands that are not 16-B aligned.
 static dim3 unaligned_grid(int64_t n) { return dim3((uint32_t)std::min<int64_t>(blocks_for(n), 8192)); }
-
-template <class Ops, int MODE, bool DUAL>
-static hipError_t launch_mode(void *param, const void *peer, int64_t n, const LerpArgs &args, hipStream_t s,
-                              const LaunchTiming *timing)
-{
-    if (!aligned16(param) || !aligned16(peer) || !aligned16(args.snap)) {
-        // (callers time only the aligned product kernel; an unaligned launch is not timed)
-        return launch(k_lerp_unaligned<Ops, MODE, DUAL>, unaligned_grid(n), dim3(kBlock), s, nullptr, param, peer, n, args);
-    }
-    return Choice<256, 64, 128, 512>::with(lerp_block(), [&](auto block) {
-        constexpr int BLOCK = decltype(block)::value;
-        using Policies = std::conditional_t<BLOCK == 64, Lerp64Policies, LerpWidePolicies>;
-        return Policies::with(lerp_policy(n * (int64_t)sizeof(typename Ops::S)), [&](auto policy) {
-            return launch(k_lerp<Ops, MODE, DUAL, BLOCK, decltype(policy)::value>, dim3((uint32_t)span_grid<Ops>(n, BLOCK)),
-                          dim3(BLOCK), s, timing, param, peer, n, args);
-        });
-    });
-}
-
-// (a segmented payload's k_lerp_mixed launches, behind with_segments below)
-static hipError_t launch_any_mixed(const Elems &e, int mode, bool oop, void *param, const void *peer, const LerpArgs &args,
-                                   hipStream_t s, const LaunchTiming *t);
-
-static hipError_t launch_any(const Elems &e, int mode, void *param, const void *peer, const LerpArgs &args, hipStream_t s,
-                             const LaunchTiming *t = nullptr)
-{
-    if (e.segmented()) return launch_any_mixed(e, mode, false, param, peer, args, s, t);
-    const int64_t n = e.n;
-    if (n < 0) return hipErrorInvalidValue;
-    if (n == 0 && mode != COEF_FUSED) return hipSuccess;
-    return with_ops(e.dtype, [&](auto ops) {
-        using Ops = decltype(ops);
-        if (mode == COEF_HOST) return launch_mode<Ops, COEF_HOST, false>(param, peer, n, args, s, t);
-        if (mode == COEF_DEV) return launch_mode<Ops, COEF_DEV, false>(param, peer, n, args, s, t);
-        if (args.snap) return launch_mode<Ops, COEF_FUSED, true>(param, peer, n, args, s, t);
-        return launch_mode<Ops, COEF_FUSED, false>(param, peer, n, args, s, t);
-    });
-}
-
-hipError_t launch_lerp(const Elems &e, void *param, const void *peer, const dpwa_coef *coef, float a, float b,
-                       hipStream_t s)
-{
-    LerpArgs args{};
-    args.a = a;
-    args.b = b;
-    args.coef = coef;
-    return launch_any(e, coef ? COEF_DEV : COEF_HOST, param, peer, args, s);
-}
-
-hipError_t launch_average(const Elems &e, void *param, const void *peer, const FusedArgs &fa, void *snap, hipStream_t s,
-                          const LaunchTiming *timing, bool oop)
-{
-    LerpArgs args{};
-    args.fused = fa;
-    args.snap = snap;
-    if (!oop) return launch_any(e, COEF_FUSED, param, peer, args, s, timing);
-    if (e.segmented()) return launch_any_mixed(e, COEF_FUSED, true, param, peer, args, s, timing);
-    // resident: 16-B aligned slot payloads only, one-wave workgroups
-    const int64_t n = e.n;
-    if (n < 0 || (!snap && n > 0) || !aligned16(param) || !aligned16(peer) || !aligned16(snap)) return hipErrorInvalidValue;
-    return with_ops(e.dtype, [&](auto ops) {
-        using Ops = decltype(ops);
-        return ResidentPolicies::with(lerp_policy(), [&](auto policy) {
-            return launch(k_lerp<Ops, COEF_FUSED, true, kStreamBlock, decltype(policy)::value, true>,
-                          dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, timing, param, peer, n, args);
-        });
-    });
-}
 
 const char *layout_problem(const dpwa_layout &layout, int64_t total_bytes)
 {
@@ -1657,111 +1576,153 @@ template <class Run> static hipError_t with_segments(const Elems &e, bool operan
 // (a segmented payload's operand: there, and 16-B aligned)
 static bool absent_or_unaligned(const void *p) { return !p || !aligned16(p); }
 
-template <int MODE, bool DUAL, bool OOP>
-static hipError_t launch_mixed(const Elems &e, void *param, const void *peer, const LerpArgs &args, hipStream_t s,
-                               const LaunchTiming *timing)
+// One single-learner average or lerp over a contiguous peer payload (k_lerp), as the entry points below describe
+// it: which form, what is averaged, where the coefficients come from (COEF_*), `oop` (resident: the result goes
+// to args.snap only), the operands, and what the form adds -- `acc` (tracked), `rec` (guarded).
+enum class SpanForm { plain, tracked, guarded };
+struct SpanAverage {
+    SpanForm form;
+    const Elems &e;
+    int mode;
+    bool oop;
+    void *param;
+    const void *peer;
+    LerpArgs args;
+    double *acc;
+    dpwa_heal_record *rec;
+    hipStream_t s;
+    const LaunchTiming *timing;
+};
+
+// What each path to k_lerp launches and refuses (one dtype / segmented: Elems; a valid layout is never empty, so
+// n == 0 is a single-dtype case).  Refusals are hipErrorInvalidValue with nothing queued.
+//
+//   path                    | coefficients | lanes        | policy table (requested)          resident (oop)
+//   plain, one dtype        | host/dev/fus.| lerp_block() | Lerp64- / LerpWidePolicies (bytes)  ResidentPolicies (knob)
+//   plain, segmented        | dev / fused  | 64           | BySizePolicies (bytes)              kProductPolicy, fixed
+//   tracked, one dtype      | fused        | 64           | BySizePolicies (bytes)              kProductPolicy, fixed
+//   guarded, either payload | dev / fused  | 64           | BySizePolicies (bytes)              kProductPolicy, fixed
+//
+//   path                    | n == 0             | misaligned operand     | null param / peer | spans > 2^31 - 1
+//   plain, one dtype        | fused: launched *  | k_lerp_unaligned **    | launched          | launched
+//   plain, one dtype, oop   | launched           | refused                | launched          | launched
+//   plain, segmented        | --                 | refused                | refused           | refused
+//   tracked, one dtype      | launched           | refused                | launched          | refused
+//   guarded, one dtype      | fused: launched *  | refused                | refused if n > 0  | refused
+//   guarded, segmented      | --                 | refused                | refused           | refused
+//   *  host and device coefficients: success with no launch, before the dtype is looked at
+//   ** never timed
+//
+// Every path refuses n < 0, an unknown dtype, a segmented payload without a valid layout, `oop` without args.snap
+// when n > 0, and coefficients its form has no kernel for; tracked refuses no `acc`, guarded no `rec` or one not
+// 8-B aligned.  DUAL is args.snap != null of a fused launch, and always of an `oop` one.
+//
+// The form's trailing kernel arguments, then the launch of <Ops, that form>: coefficients, lanes, policy.
+template <class Ops, class... Table> static hipError_t launch_spans(const SpanAverage &l, int64_t n, const Table &...table)
 {
-    const bool bad = absent_or_unaligned(param) || absent_or_unaligned(peer) || !aligned16(args.snap) || (DUAL && !args.snap);
-    return with_segments(e, bad, [&](int64_t total, dim3 grid, const SegTable &t) {
-        // (resident: the product policy, as the single-dtype resident kernels without the knob)
-        return BySizePolicies::with(OOP ? kProductPolicy : lerp_policy(total), [&](auto policy) {
-            constexpr int P = OOP ? kProductPolicy : decltype(policy)::value;
-            return launch(k_lerp_mixed<MODE, DUAL, P, OOP>, grid, dim3(kStreamBlock), s, timing, param, peer, total, args, t);
-        });
-    });
+    const auto launch_form = [&](const auto &...form) -> hipError_t {
+        constexpr bool kSolo = sizeof...(Table) + sizeof...(form) == 0;   // k_lerp's own argument list
+        constexpr bool kTracked = (std::is_same_v<std::decay_t<decltype(form)>, DistTrack> || ...);
+        const auto shaped = [&](auto mode, auto dual, auto oop) -> hipError_t {
+            constexpr int MODE = decltype(mode)::value;
+            constexpr bool DUAL = decltype(dual)::value, OOP = decltype(oop)::value;
+            if constexpr ((MODE == COEF_HOST && !kSolo) || (MODE != COEF_FUSED && kTracked)) {
+                return hipErrorInvalidValue;   // (no such kernel)
+            } else {
+                if constexpr (kSolo && !OOP)
+                    if (!aligned16(l.param) || !aligned16(l.peer) || !aligned16(l.args.snap))
+                        return launch(k_lerp_unaligned<Ops, MODE, DUAL>, unaligned_grid(n), dim3(kBlock), l.s, nullptr,
+                                      l.param, l.peer, n, l.args);
+                using Blocks = std::conditional_t<kSolo && !OOP, Choice<256, 64, 128, 512>, Choice<kStreamBlock>>;
+                return Blocks::with(lerp_block(), [&](auto block) {
+                    constexpr int BLOCK = decltype(block)::value;
+                    using Sized = std::conditional_t<!kSolo, BySizePolicies,
+                                                     std::conditional_t<BLOCK == 64, Lerp64Policies, LerpWidePolicies>>;
+                    using Policies = std::conditional_t<!OOP, Sized, std::conditional_t<kSolo, ResidentPolicies, Choice<kProductPolicy>>>;
+                    const int64_t grid = span_grid<Ops>(n, BLOCK);
+                    if (!kSolo && grid > 0x7fffffffLL) return hipErrorInvalidValue;
+                    return Policies::with(OOP ? lerp_policy() : lerp_policy(n * (16 / Ops::PER)), [&](auto policy) {
+                        return launch(k_lerp<Ops, MODE, DUAL, BLOCK, decltype(policy)::value, OOP, Table...,
+                                             std::decay_t<decltype(form)>...>,
+                                      dim3((uint32_t)grid), dim3(BLOCK), l.s, l.timing, l.param, l.peer, n, l.args, table...,
+                                      form...);
+                    });
+                });
+            }
+        };
+        using std::false_type, std::true_type;
+        if (l.mode == COEF_HOST) return shaped(std::integral_constant<int, COEF_HOST>{}, false_type{}, false_type{});
+        if (l.mode == COEF_DEV) return shaped(std::integral_constant<int, COEF_DEV>{}, false_type{}, false_type{});
+        const std::integral_constant<int, COEF_FUSED> fused;
+        if (l.oop) return shaped(fused, true_type{}, true_type{});
+        return l.args.snap ? shaped(fused, true_type{}, false_type{}) : shaped(fused, false_type{}, false_type{});
+    };
+    switch (l.form) {
+    case SpanForm::plain: return launch_form();
+    case SpanForm::guarded: return launch_form(HealGuard{l.rec});
+    case SpanForm::tracked:
+        if constexpr (sizeof...(Table) == 0) return launch_form(DistTrack{l.acc});   // (a single dtype only)
+    }
+    return hipErrorInvalidValue;
 }
 
-static hipError_t launch_any_mixed(const Elems &e, int mode, bool oop, void *param, const void *peer, const LerpArgs &args,
-                                   hipStream_t s, const LaunchTiming *t)
+static hipError_t launch_span_average(const SpanAverage &l)
 {
-    if (mode == COEF_HOST) return hipErrorInvalidValue;   // (a segmented lerp reads its coefficients on the device)
-    if (mode == COEF_DEV) return launch_mixed<COEF_DEV, false, false>(e, param, peer, args, s, t);
-    if (oop) return launch_mixed<COEF_FUSED, true, true>(e, param, peer, args, s, t);
-    if (args.snap) return launch_mixed<COEF_FUSED, true, false>(e, param, peer, args, s, t);
-    return launch_mixed<COEF_FUSED, false, false>(e, param, peer, args, s, t);
+    const bool segmented = l.e.segmented(), plain = l.form == SpanForm::plain;
+    const bool some = segmented || l.e.n > 0;
+    if (l.form == SpanForm::tracked && !l.acc) return hipErrorInvalidValue;
+    if (l.form == SpanForm::guarded && (!l.rec || ((uintptr_t)l.rec & 7))) return hipErrorInvalidValue;
+    if (!segmented && l.e.n < 0) return hipErrorInvalidValue;
+    if ((segmented || l.oop || !plain) && (!aligned16(l.param) || !aligned16(l.peer) || !aligned16(l.args.snap)))
+        return hipErrorInvalidValue;   // (else: k_lerp_unaligned)
+    if (l.oop && !l.args.snap && some) return hipErrorInvalidValue;
+    if ((segmented || l.form == SpanForm::guarded) && some && (!l.param || !l.peer)) return hipErrorInvalidValue;
+    if (segmented)
+        return with_segments(l.e, false, [&](int64_t total, dim3, const SegTable &t) { return launch_spans<OpsMixed>(l, total, t); });
+    if (l.e.n == 0 && l.mode != COEF_FUSED) return hipSuccess;
+    return with_ops(l.e.dtype, [&](auto ops) { return launch_spans<decltype(ops)>(l, l.e.n); });
+}
+
+static LerpArgs fused_lerp_args(const FusedArgs &fa, void *snap)
+{
+    LerpArgs args{};
+    args.fused = fa;
+    args.snap = snap;
+    return args;
+}
+
+hipError_t launch_lerp(const Elems &e, void *param, const void *peer, const dpwa_coef *coef, float a, float b,
+                       hipStream_t s)
+{
+    LerpArgs args{};
+    args.a = a;
+    args.b = b;
+    args.coef = coef;
+    return launch_span_average({SpanForm::plain, e, coef ? COEF_DEV : COEF_HOST, false, param, peer, args, nullptr, nullptr, s, nullptr});
+}
+
+hipError_t launch_average(const Elems &e, void *param, const void *peer, const FusedArgs &fa, void *snap, hipStream_t s,
+                          const LaunchTiming *timing, bool oop)
+{
+    return launch_span_average(
+        {SpanForm::plain, e, COEF_FUSED, oop, param, peer, fused_lerp_args(fa, snap), nullptr, nullptr, s, timing});
 }
 
 // ---------------------------------------------------------------- distance launches
 hipError_t launch_average_tracked(int32_t dtype, void *param, const void *peer, int64_t n, const FusedArgs &fa,
                                   void *snap, bool oop, double *acc, hipStream_t s, const LaunchTiming *timing)
 {
-    if (n < 0 || !acc || (oop && !snap && n > 0) || !aligned16(param) || !aligned16(peer) || !aligned16(snap))
-        return hipErrorInvalidValue;
-    LerpArgs args{};
-    args.fused = fa;
-    args.snap = snap;
-    return with_ops(dtype, [&](auto ops) {
-        using Ops = decltype(ops);
-        using V = typename Ops::V;
-        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
-        const auto run = [&](void (*kernel)(V *, const V *, int64_t, LerpArgs, double *)) {
-            return launch(kernel, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, timing, param,
-                          peer, n, args, acc);
-        };
-        if (oop) return run(k_lerp_tracked<Ops, true, true, kProductPolicy>);   // resident: no choice by size
-        return BySizePolicies::with(lerp_policy(n * (int64_t)sizeof(typename Ops::S)), [&](auto policy) {
-            constexpr int P = decltype(policy)::value;
-            return snap ? run(k_lerp_tracked<Ops, true, false, P>) : run(k_lerp_tracked<Ops, false, false, P>);
-        });
-    });
+    const Elems e{dtype, n, nullptr};
+    return launch_span_average(
+        {SpanForm::tracked, e, COEF_FUSED, oop, param, peer, fused_lerp_args(fa, snap), acc, nullptr, s, timing});
 }
 
 // ---------------------------------------------------------------- guarded (healing) launches
-// One guarded launch, fused (MODE COEF_FUSED; `oop`: resident) or with device coefficients (COEF_DEV).  Refused
-// before anything is queued: no record or a misaligned one, n < 0, an operand that is not 16-B aligned (there
-// is no unaligned form), a resident launch without its destination, more than 2^31 - 1 spans, and what
-// with_ops / with_segments refuse.
-template <int MODE>
-static hipError_t launch_guarded(const Elems &e, void *param, const void *peer, const LerpArgs &args, bool oop,
-                                 dpwa_heal_record *rec, hipStream_t s, const LaunchTiming *timing)
-{
-    void *const snap = args.snap;
-    if (!rec || ((uintptr_t)rec & 7) || !aligned16(param) || !aligned16(peer) || !aligned16(snap)) return hipErrorInvalidValue;
-    if (e.segmented()) {
-        const bool bad = !param || !peer || (oop && !snap);
-        return with_segments(e, bad, [&](int64_t total, dim3 grid, const SegTable &t) {
-            const auto run = [&](void (*kernel)(u32x4 *, const u32x4 *, int64_t, LerpArgs, SegTable, dpwa_heal_record *)) {
-                return launch(kernel, grid, dim3(kStreamBlock), s, timing, param, peer, total, args, t, rec);
-            };
-            if constexpr (MODE == COEF_FUSED)
-                if (oop) return run(k_lerp_guarded_mixed<MODE, true, kProductPolicy, true>);
-            return BySizePolicies::with(lerp_policy(total), [&](auto policy) {
-                constexpr int P = decltype(policy)::value;
-                if constexpr (MODE == COEF_FUSED)   // (a lerp with device coefficients writes the parameters only)
-                    if (snap) return run(k_lerp_guarded_mixed<MODE, true, P, false>);
-                return run(k_lerp_guarded_mixed<MODE, false, P, false>);
-            });
-        });
-    }
-    const int64_t n = e.n;
-    if (n < 0 || (oop && !snap && n > 0) || (n > 0 && (!param || !peer))) return hipErrorInvalidValue;
-    if (n == 0 && MODE != COEF_FUSED) return hipSuccess;
-    return with_ops(e.dtype, [&](auto ops) {
-        using Ops = decltype(ops);
-        using V = typename Ops::V;
-        if (span_grid<Ops>(n, kStreamBlock) > 0x7fffffffLL) return hipErrorInvalidValue;
-        const auto run = [&](void (*kernel)(V *, const V *, int64_t, LerpArgs, dpwa_heal_record *)) {
-            return launch(kernel, dim3((uint32_t)span_grid<Ops>(n, kStreamBlock)), dim3(kStreamBlock), s, timing, param,
-                          peer, n, args, rec);
-        };
-        if constexpr (MODE == COEF_FUSED)
-            if (oop) return run(k_lerp_guarded<Ops, MODE, true, true, kProductPolicy>);   // resident: no choice by size
-        return BySizePolicies::with(lerp_policy(n * (int64_t)sizeof(typename Ops::S)), [&](auto policy) {
-            constexpr int P = decltype(policy)::value;
-            if constexpr (MODE == COEF_FUSED)
-                if (snap) return run(k_lerp_guarded<Ops, MODE, true, false, P>);
-            return run(k_lerp_guarded<Ops, MODE, false, false, P>);
-        });
-    });
-}
-
 hipError_t launch_average_guarded(const Elems &e, void *param, const void *peer, const FusedArgs &fa, void *snap,
                                   dpwa_heal_record *rec, hipStream_t s, const LaunchTiming *timing, bool oop)
 {
-    LerpArgs args{};
-    args.fused = fa;
-    args.snap = snap;
-    return launch_guarded<COEF_FUSED>(e, param, peer, args, oop, rec, s, timing);
+    return launch_span_average(
+        {SpanForm::guarded, e, COEF_FUSED, oop, param, peer, fused_lerp_args(fa, snap), nullptr, rec, s, timing});
 }
 
 hipError_t launch_lerp_guarded(const Elems &e, void *param, const void *peer, const dpwa_coef *coef,
@@ -1770,7 +1731,7 @@ hipError_t launch_lerp_guarded(const Elems &e, void *param, const void *peer, co
     if (!coef) return hipErrorInvalidValue;
     LerpArgs args{};
     args.coef = coef;
-    return launch_guarded<COEF_DEV>(e, param, peer, args, false, rec, s, nullptr);
+    return launch_span_average({SpanForm::guarded, e, COEF_DEV, false, param, peer, args, nullptr, rec, s, nullptr});
 }
 
 hipError_t launch_distance(const Elems &e, const void *param, const void *peer, double *acc, hipStream_t s)
@@ -2646,7 +2607,7 @@ __global__ __launch_bounds__(kStreamBlock) void k_consensus(ConsensusArgs a, int
 }
 
 // The same span code over a segmented payload: the span's element type is its segment's, looked up
-// from the span's byte offset after the loads were issued (as k_lerp_mixed); no ragged tail;
+// from the span's byte offset after the loads were issued (as the segmented k_lerp); no ragged tail;
 // padding bytes are zeros in every member, whose mean is zero and which add 0.
 template <int U, bool STORE, bool TRACK>
 __global__ __launch_bounds__(kStreamBlock) void k_consensus_mixed(ConsensusArgs a, int64_t total, SegTable segs)

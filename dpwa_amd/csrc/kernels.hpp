@@ -99,7 +99,7 @@ hipError_t launch_average(const Elems &e, void *param, const void *peer, const F
 // The distance to the peer (dpwa_distance, include/dpwa_hip.h; kernels.hip "distance to the peer").
 // `acc`: kDistanceWorkspaceBytes of device memory, zero before the first use; every finish leaves
 // it zero again.
-//   average_tracked   launch_average with the sums added by the same kernel (k_lerp_tracked):
+//   average_tracked   launch_average with the sums added by the same kernel (k_lerp<..., DistTrack>):
 //                     16-B aligned operands and a single dtype only, else hipErrorInvalidValue
 //   distance          the stand-alone pass over (param, peer payload); any element alignment for a single
 //                     dtype
@@ -114,7 +114,7 @@ hipError_t launch_distance_finish(double *acc, dpwa_distance *out, const dpwa_co
                                   const LaunchTiming *timing = nullptr);
 
 // The guarded averages (include/dpwa_hip.h "healing"; kernels.hip "healing non-finite elements"): launch_average
-// (k_lerp_guarded / k_lerp_guarded_mixed) and launch_lerp with device coefficients, every result element selected
+// (k_lerp<..., HealGuard>, single dtype or segmented) and launch_lerp with device coefficients, every result element selected
 // by the healing rule and the healed / refused elements added to *rec (device memory, 8-B aligned; rounds and
 // clock written when the round averaged).  hipErrorInvalidValue, nothing queued: no record, no `coef`, n < 0, a
 // `param`, `peer` or `snap` that is not 16-B aligned (there is no unaligned form), `oop` without `snap`, more

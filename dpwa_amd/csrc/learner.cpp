@@ -1249,10 +1249,13 @@ int dpwa_learner_factor(dpwa_learner *l, double loss, const double *loss_dev, dp
     return DPWA_OK;
 }
 
-// The guarded kernels have no form for parameters that are not 16-byte aligned (the peer payload and the
-// snapshot slots always are): refused before anything is queued.
-static int heal_operands_problem(const dpwa_learner *l, const char *fn, const void *flat)
+// What the learner's payload and options ask of the parameters' address, refused before anything is queued or
+// counted: a segmented payload, the per-parameter distance and the guarded kernels have no form for parameters
+// that are not 16-byte aligned (the peer payload and the snapshot slots always are).
+static int operands_problem(const dpwa_learner *l, const char *fn, const void *flat)
 {
+    if (l->dtype == DPWA_MIXED && !aligned16(flat)) return set_error(DPWA_ERR_ARG, "%s: a segmented payload is 16-byte aligned", fn);
+    if (int rc = l->measure.operands_problem(fn, flat)) return rc;
     if (!l->heal || aligned16(flat)) return DPWA_OK;
     return set_error(DPWA_ERR_ARG, "%s: healing (dpwa_learner_set_heal) has no form for parameters that are not "
                                    "16-byte aligned", fn);
@@ -1266,10 +1269,7 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
         return set_error(DPWA_ERR_STATE, "dpwa_learner_lerp: a resident learner averages with dpwa_learner_average");
     DeviceGuard dg(l->device);
     hipStream_t s = (hipStream_t)stream;
-    if (l->dtype == DPWA_MIXED && !aligned16(flat))   // (its layout is known: the factor was computed)
-        return set_error(DPWA_ERR_ARG, "dpwa_learner_lerp: a segmented payload is 16-byte aligned");
-    if (int rc = l->measure.operands_problem("dpwa_learner_lerp", flat)) return rc;
-    if (int rc = heal_operands_problem(l, "dpwa_learner_lerp", flat)) return rc;
+    if (int rc = operands_problem(l, "dpwa_learner_lerp", flat)) return rc;   // (the layout is known: the factor was computed)
     if (int rc = pack_materialize(l, s)) return rc;   // (a second pull since the factor)
     const Measured m{&l->measure, payload(l), flat, l->fetch.source().ptr + kPayloadOff, nullptr};
     int rc = measured_average(&m, 1, s, [&]() -> int {
@@ -1284,21 +1284,41 @@ int dpwa_learner_lerp(dpwa_learner *l, void *flat, dpwa_stream_t stream)
     return DPWA_OK;
 }
 
+// The form of a round's launch, chosen once (choose_form): the relay's phase 2 fused into the average
+// (k_lerp_relay), the guarded average of a healing learner, the average straight from the packed image the payload
+// is still in (k_lerp_packed), or the average of a contiguous peer payload, which alone can join a batch.
+enum class AvgForm { contiguous, relay, guarded, packed };
+
 // One fused average, split so that several learners' averages can share a dispatch:
 // average_prepare orders `s` after everything the kernel reads or overwrites and builds its
 // arguments; the caller launches; average_commit does the learner's bookkeeping.
 struct AvgPlan {
+    AvgForm form = AvgForm::contiguous;
     void *flat = nullptr;
-    const char *peer = nullptr;   // payload averaged with (contiguous source)
-    const char *image = nullptr;  // ... or the packed image it is still in (k_lerp_packed); then `peer` is null
+    const char *peer = nullptr;   // payload averaged with (contiguous and guarded)
+    const char *image = nullptr;  // ... or the packed image (packed); then `peer` is null
     char *snap = nullptr;         // write-through destination
     FusedArgs fa{};
-    bool relay = false;           // the relay's phase 2 fused into this average (k_lerp_relay)
     bool write_through = false;
     bool oop = false;             // resident: the result goes to `snap` only
     char *emit = nullptr;         // the snapshot's packed image, written by this launch too (k_lerp_emit)
     int snap_slot = -1;
 };
+
+// The round's form.  `relay`: a fused relay second phase is deferred and the operands are aligned; `plain`: see
+// average_prepare.  A relay comes first, then healing, then the image of a payload that is still packed.  What a
+// form has no kernel for is refused where the option is switched on (dpwa_learner_relay_phase2, the set_*
+// entries, pack_enable), and `plain` is false for all of it: a combination that arrives here all the same is a
+// state error, not a launch of some other form.
+static int choose_form(const dpwa_learner *l, bool relay, bool plain, AvgForm &form)
+{
+    form = relay ? AvgForm::relay : l->heal ? AvgForm::guarded : l->fetch.source().packed && plain ? AvgForm::packed : AvgForm::contiguous;
+    const bool contiguous_only = l->heal || l->measure.whole() || l->measure.param() || l->finite_check || l->dtype == DPWA_MIXED;
+    if (!contiguous_only || form == AvgForm::guarded || form == AvgForm::contiguous) return DPWA_OK;
+    return set_error(DPWA_ERR_STATE, "dpwa_learner_average: the average from %s has no form for a learner that heals, "
+                                     "measures, checks for non-finite peers or has a segmented payload",
+                     form == AvgForm::relay ? "the relay's stripes" : "a packed image");
+}
 
 // `alone`: the plan is launched by average_launch, never as a member of a batched, pair or group dispatch.
 static int average_prepare(dpwa_learner *l, void *flat, double loss, const double *loss_dev, hipStream_t s,
@@ -1306,10 +1326,7 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
 {
     if (!l->fetch.fetched() || l->fetch.factored()) return set_error(DPWA_ERR_STATE, "dpwa_learner_average: no fetch in flight");
     if (int rc = need_layout(l, "dpwa_learner_average")) return rc;
-    if (l->dtype == DPWA_MIXED && !aligned16(flat))
-        return set_error(DPWA_ERR_ARG, "dpwa_learner_average: a segmented payload is 16-byte aligned");
-    if (int rc = l->measure.operands_problem("dpwa_learner_average", flat)) return rc;
-    if (int rc = heal_operands_problem(l, "dpwa_learner_average", flat)) return rc;
+    if (int rc = operands_problem(l, "dpwa_learner_average", flat)) return rc;
     p = AvgPlan();
     if (l->resident) {   // read where the parameters are (the published slot), write the next slot
         if (flat != slot_payload(l, l->res_slot))
@@ -1335,30 +1352,31 @@ static int average_prepare(dpwa_learner *l, void *flat, double loss, const doubl
             p.fa.dtype = l->dtype;
         }
     }
-    if (l->relay_deferred && aligned16(flat, p.snap)) {
-        // the relay's phase 2 fused into the average: stripes read where phase 1 left them
+    const bool relay = l->relay_deferred && aligned16(flat, p.snap);
+    if (!relay)
+        if (int rc = relay_materialize(l)) return rc;
+    // plain: nothing of this round needs the peer's contiguous payload (a measurement, the non-finite check,
+    // healing, a batched dispatch, the unaligned form), so a payload that is still packed stays packed
+    const bool plain = alone && !l->measure.whole() && !l->measure.param() && !l->finite_check && !l->heal &&
+                       aligned16(flat, p.snap);
+    if (int rc = choose_form(l, relay, plain, p.form)) return rc;
+    switch (p.form) {
+    case AvgForm::relay: {   // stripes read where phase 1 left them
         const RelayArgs &a = l->relay_saved;
         p.fa.hdr = (const dpwa_header *)(a.slots[l->relay_saved_pick] + a.slot_off);
-        p.relay = true;
-    } else {
-        if (int rc = relay_materialize(l)) return rc;
-        // a payload that is still packed: k_lerp_packed reads the landing image itself, unless something of this
-        // round needs the contiguous payload (a measurement, the non-finite check, healing, a batched dispatch,
-        // the unaligned form), which expands it first
-        const bool plain = alone && !l->measure.whole() && !l->measure.param() && !l->finite_check && !l->heal &&
-                           aligned16(flat, p.snap);
-        if (l->fetch.source().packed && plain) {
-            p.image = l->fetch.source().packed;
-        } else {
-            if (int rc = pack_materialize(l, s)) return rc;
-            p.peer = l->fetch.source().ptr + kPayloadOff;
-        }
-        // a round that writes slot k of a pack-enabled learner writes image k in the same launch, under the
-        // conditions that leave the launch to k_lerp / k_lerp_packed (never a segmented payload: pack_enable)
-        // and never a resident learner: its step writes the slot after the average, behind the image's back
-        if (l->pack_on && write_through && !l->resident && plain && aligned16(p.peer) && pack_fused())
-            p.emit = l->pack_mem.ptr + (size_t)p.snap_slot * (size_t)l->pack_stride;
+        break;
     }
+    case AvgForm::packed: p.image = l->fetch.source().packed; break;
+    case AvgForm::guarded:
+    case AvgForm::contiguous:
+        if (int rc = pack_materialize(l, s)) return rc;
+        p.peer = l->fetch.source().ptr + kPayloadOff;
+    }
+    // a round that writes slot k of a pack-enabled learner writes image k in the same launch, under the
+    // conditions that leave the launch to k_lerp / k_lerp_packed (never a segmented payload: pack_enable)
+    // and never a resident learner: its step writes the slot after the average, behind the image's back
+    if (l->pack_on && write_through && !l->resident && p.form != AvgForm::relay && plain && aligned16(p.peer) && pack_fused())
+        p.emit = l->pack_mem.ptr + (size_t)p.snap_slot * (size_t)l->pack_stride;
     HIP_TRY(l->fetch.wait_landed(s));
     return DPWA_OK;
 }
@@ -1370,7 +1388,7 @@ static const LaunchTiming *take_timing(dpwa_learner *l)
 
 static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
-    if (p.relay) {
+    if (p.form == AvgForm::relay) {
         HIP_TRY(l->relay_done.record(s));   // the next round's barrier waits for these reads
         l->relay_deferred = false;
         l->fetch.note_consumed_in_place(s);
@@ -1391,26 +1409,31 @@ static int average_commit(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 // fused whole-model record gets the tracked kernel in its place.
 static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
 {
-    // (the unaligned launch_average is not timed; p.relay: relay_phase2 refuses to defer for a
-    // segmented payload or a measuring learner)
+    // (the unaligned launch_average is not timed)
     const Payload e = payload(l);
-    const LaunchTiming *timing = e.segmented() || p.relay || aligned16(p.flat) ? take_timing(l) : nullptr;
-    if (int rc = finite_pass(l, p.fa, p.peer, s)) return rc;   // (never with p.relay: relay_phase2 refuses)
-    // (a healing learner passes no FusedArgs: the tracked kernel has no guarded form, so the stand-alone
+    const LaunchTiming *timing = e.segmented() || p.form == AvgForm::relay || aligned16(p.flat) ? take_timing(l) : nullptr;
+    if (int rc = finite_pass(l, p.fa, p.peer, s)) return rc;
+    // (a guarded average passes no FusedArgs: the tracked kernel has no guarded form, so the stand-alone
     // distance pass runs first and the guarded average is the callback)
-    const Measured m{&l->measure, e, p.flat, p.peer, p.snap, l->heal ? nullptr : &p.fa, p.oop, timing};
+    const Measured m{&l->measure, e, p.flat, p.peer, p.snap, p.form == AvgForm::guarded ? nullptr : &p.fa, p.oop, timing};
     return measured_average(&m, 1, s, [&]() -> int {
-        if (l->heal) {   // (never p.relay: relay_phase2 refuses; never p.emit or p.image: average_prepare)
+        switch (p.form) {
+        case AvgForm::guarded:
             HIP_TRY(launch_average_guarded(e, p.flat, p.peer, p.fa, p.snap, &l->ctl->heal, s, timing, p.oop));
-        } else if (p.relay) {   // (never a segmented payload: relay_phase2 refuses)
+            break;
+        case AvgForm::relay:
             HIP_TRY(launch_average_relay(l->dtype, p.flat, l->n, p.fa, p.snap, l->relay_saved, l->relay_saved_pick, s,
                                          timing, p.oop));
-        } else if (p.emit) {   // (as p.image; p.peer or p.image, whichever average_prepare chose)
-            HIP_TRY(launch_average_emit(l->dtype, p.flat, l->n, p.peer, p.image, p.fa, p.snap, p.emit, s, timing));
-        } else if (p.image) {   // (never a segmented payload or a measuring learner: average_prepare)
-            HIP_TRY(launch_average_packed(l->dtype, p.flat, l->n, p.image, p.fa, p.snap, s, timing, p.oop));
-        } else {
-            HIP_TRY(launch_average(e, p.flat, p.peer, p.fa, p.snap, s, timing, p.oop));
+            break;
+        case AvgForm::packed:
+        case AvgForm::contiguous:
+            if (p.emit) {   // (that average, emitting: p.peer or p.image, whichever the form has)
+                HIP_TRY(launch_average_emit(l->dtype, p.flat, l->n, p.peer, p.image, p.fa, p.snap, p.emit, s, timing));
+            } else if (p.form == AvgForm::packed) {
+                HIP_TRY(launch_average_packed(l->dtype, p.flat, l->n, p.image, p.fa, p.snap, s, timing, p.oop));
+            } else {
+                HIP_TRY(launch_average(e, p.flat, p.peer, p.fa, p.snap, s, timing, p.oop));
+            }
         }
         return DPWA_OK;
     });
@@ -1426,11 +1449,11 @@ static int average_impl(dpwa_learner *l, void *flat, double loss, const double *
     return average_commit(l, p, s);
 }
 
-// Can plan p join a batched dispatch (k_lerp_batch)?  Contiguous source, 16-B aligned operands, one
-// element type (a segmented payload is not batched), no healing (the batch has no guarded form).
+// Can plan p join a batched dispatch (k_lerp_batch)?  The contiguous form (the batch has no relay and no guarded
+// form), 16-B aligned operands, one element type (a segmented payload is not batched).
 static bool batchable(const dpwa_learner *l, const AvgPlan &p)
 {
-    return !p.relay && !l->heal && !payload(l).segmented() && aligned16(p.flat, p.peer, p.snap);
+    return p.form == AvgForm::contiguous && !payload(l).segmented() && aligned16(p.flat, p.peer, p.snap);
 }
 
 // Launches the batchable plans in groups of the same (dtype, write-through), up to

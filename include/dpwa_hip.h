@@ -299,7 +299,7 @@ int dpwa_check_finite_mixed(const dpwa_layout *layout, const void *peer_payload,
  * dpwa_heal_record (device memory, 8-B aligned, zero before the first use, cumulative): healed and refused
  * elements (integer atomics: bit-exact from run to run; a round with none issues no atomic), the guarded
  * rounds that averaged and the new clock of the last of them.
- *   dpwa_average_guarded        dpwa_average with the rule above (k_lerp_guarded).
+ *   dpwa_average_guarded        dpwa_average with the rule above (k_lerp<..., HealGuard>).
  *   dpwa_average_guarded_mixed  dpwa_average_mixed with it; each segment by its own type's test.
  * DPWA_ERR_ARG, nothing queued: what dpwa_average / dpwa_average_mixed refuse, a NULL or misaligned record,
  * and `param`, the peer slot or `snap_payload` not 16-byte aligned (there is no unaligned form). */

@@ -1,5 +1,5 @@
 """The averaging forms whose cache policy follows the bytes of the launch (kernels.hip lerp_policy:
-k_lerp plain and write-through, k_lerp_batch, k_lerp_tracked, k_lerp_mixed -- none of them resident),
+k_lerp plain and write-through, k_lerp_batch, the tracked and the segmented k_lerp -- none of them resident),
 at span edges, in a process of its own: DPWA_CACHE_FIT_BYTES and DPWA_LERP_POLICY are read once per
 process, so tests/test_gpu_policy_by_size.py starts one worker per setting.  A policy is cache bits on
 the same loads and stores, so every setting must give the host references' bits (oracle.lerp through

@@ -18,8 +18,9 @@ Which case runs which kernel beyond 2^32 bytes:
   k_lerp (COEF_FUSED, plain and DUAL)   test_average (bf16, f32; plain and write-through)
   k_lerp (out of place)                 test_resident[one]
   k_lerp_unaligned                      test_average_unaligned
-  k_lerp_tracked, k_distance_finish     test_average_tracked (bf16, f32)
-  k_lerp_mixed (plain and DUAL)         test_average_mixed
+  k_lerp<.., DistTrack>                 test_average_tracked (bf16, f32)
+  k_distance_finish                     test_average_tracked (bf16, f32)
+  k_lerp<OpsMixed, .., SegTable>        test_average_mixed (plain and DUAL)
   k_lerp_pair                           test_resident[mutual-pair]
   k_lerp_group                          test_resident[U3]
   k_distance, k_distance_unaligned      test_distance (bf16, f32; aligned and one element on)
@@ -315,7 +316,7 @@ def test_average_tracked(dtype):
 @pytest.mark.parametrize("through", [False, True], ids=["plain", "write-through"])
 @latched
 def test_average_mixed(through):
-    """dpwa_average_mixed (k_lerp_mixed): the second and third segments begin beyond byte 2^32."""
+    """dpwa_average_mixed (k_lerp<OpsMixed, ..., SegTable>): the second and third segments begin beyond byte 2^32."""
     fused(None, ref.mixed(), "hard", through)
 
 

@@ -77,7 +77,7 @@ def test_average_unaligned(dtype, write_through):
 @pytest.mark.parametrize("write_through", [False, True], ids=["plain", "write-through"])
 @pytest.mark.parametrize("dtype", ref.DTYPES)
 def test_average_tracked_kernel(dtype, write_through):
-    """dpwa_average_tracked (k_lerp_tracked): coef, clock and parameters are dpwa_average's.  (What
+    """dpwa_average_tracked (k_lerp<..., DistTrack>): coef, clock and parameters are dpwa_average's.  (What
     the distance record holds after a NaN or zero-division round is tests/test_gpu_distance.py's.)"""
     for n in forms.sizes(dtype):
         for case in fr.CATCHING:
