@@ -15,7 +15,8 @@ ROUNDS = 4
 
 
 def run_lockstep(shared, rank, world, args):
-    pull, port, cfg_path, out_dir, vmm = args
+    pull, port, cfg_path, out_dir, vmm = args[:5]
+    trim = args[5] if len(args) > 5 else 0        # (consensus(trim=...): tests/test_gpu_consensus_trim.py)
     import torch
     dist, dev = _init_group(rank, world, port)
     from dpwa_amd import DpwaConnection
@@ -29,7 +30,7 @@ def run_lockstep(shared, rank, world, args):
     for r in range(ROUNDS):
         snaps[r] = flat.view(torch.int16).cpu().numpy().view(np.uint16)
         conn.update_send(flat, 1.0)
-        c = conn.consensus()
+        c = conn.consensus(trim=trim)
         assert c.members == names and c.version == r + 1, (c.members, c.version)
         means[r] = c.tensor().view(torch.int16).cpu().numpy().view(np.uint16)
         rec = c.read()
