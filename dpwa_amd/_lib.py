@@ -178,6 +178,9 @@ SIGNATURES = {
     "dpwa_average_pack": [_i32, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp, _vp, _vp,
                           _vp],
     "dpwa_pack_if": [_i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
+    "dpwa_pack_stochastic": [_i32, _vp, _i64, _vp, _u64, _vp, _vp, _vp],
+    "dpwa_average_pack_stochastic": [_i32, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(Interp), _vp, _dbl, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _u64],
     "dpwa_learner_consensus": [_vp, ctypes.POINTER(_i32), _int, _u64, _vp, _vp, _vp],
     "dpwa_learner_consensus_trimmed": [_vp, ctypes.POINTER(_i32), _int, _int, _u64, _vp, _vp, _vp],
     "dpwa_learner_set_finite_check": [_vp, _int],
@@ -238,6 +241,7 @@ SIGNATURES = {
     "dpwa_learner_relay_attach": [_vp, _int, _int, _vp, _i64],
     "dpwa_learner_relay_attach_fds": [_vp, _int, _int, _vp, _i64, _pint, _int, _i64],
     "dpwa_learner_pack_enable": [_vp],
+    "dpwa_learner_set_pack_rounding": [_vp, _int, _u64],
     "dpwa_learner_pack_counts": [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
     "dpwa_learner_pack_image": [_vp, _int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)],
     "dpwa_learner_pack_handle": [_vp, _vp, _i64],

@@ -3088,10 +3088,72 @@ __device__ __forceinline__ uint32_t pack_q(float x, float inv)
     return (uint32_t)(int)r & 0xffu;
 }
 
+// pack_q's stochastic sibling (include/dpwa_hip.h "stochastic rounding"): floor(t) plus one where the
+// element's noise u in [0, 1) lies below frac(t).  t, f and frac are three separately rounded operations
+// (v_mul_f32, v_floor_f32, v_sub_f32); f is an integer of [-128, 127], so f + 1.0f is the integer sum.
+// A zero gives frac = 0 and stays 0 whatever u is.
+__device__ __forceinline__ uint32_t pack_q_sr(float x, float inv, float u)
+{
+    const float t = x * inv;
+    const float f = __builtin_floorf(t);
+    const float frac = t - f;
+    float r = f + (u < frac ? 1.0f : 0.0f);
+    r = __builtin_fminf(__builtin_fmaxf(r, -127.0f), 127.0f);
+    return (uint32_t)(int)r & 0xffu;
+}
+
+// murmur3's 32-bit finaliser: two multiplies and three shift-xors, all uint32.
+__device__ __forceinline__ uint32_t fmix32(uint32_t h)
+{
+    h ^= h >> 16, h *= 0x85ebca6bu, h ^= h >> 13, h *= 0xc2b2ae35u, h ^= h >> 16;
+    return h;
+}
+
+// How an image-writing kernel rounds (k_pack, k_pack_if, k_lerp_emit): a policy object that travels as the
+// kernel's last argument.  noise<E>(j0) is what the lane needs for its E elements j0 .. j0 + E - 1 before it
+// knows anything about their values, and Noise::q(e, x, inv) the q byte of element e.  RoundNearest holds
+// nothing and q is pack_q: those instantiations have no branch on the policy and are the kernels as they
+// were, instruction for instruction (gfx950: k_pack_if and k_lerp_emit to the register; k_pack's one-byte
+// argument moved its allocation by one VGPR, 24 / 51 / 41 for 23 / 50 / 40, the instructions being the same).
+// RoundStochastic holds the image's nonce; its noise is the counter-based hash of (element index, nonce) of
+// the header's rule, two fmix32 per element in registers -- no memory, no LDS, no state -- and since it
+// depends on indices and the nonce alone every caller asks for it right behind its loads, ahead of the
+// cross-lane amax, so the integer pipe can work while the loads are in flight (k_pack's does; in k_lerp_emit
+// the compiler sinks it below the factor's branch, ahead of row_umax -- DESIGN §3).  j0 is a multiple of E and E a
+// power of two, so element e's index is j0 | e: the high word, and with it hi, is the lane's one value (in
+// fact the wave's) and the low words differ in the low bits only.
+struct RoundNearest {
+    template <int E> struct Noise {
+        __device__ __forceinline__ uint32_t q(int, float x, float inv) const { return pack_q(x, inv); }
+    };
+    template <int E> __device__ __forceinline__ Noise<E> noise(uint64_t) const { return {}; }
+};
+struct RoundStochastic {
+    uint64_t nonce;
+    template <int E> struct Noise {
+        float u[E];
+        __device__ __forceinline__ uint32_t q(int e, float x, float inv) const { return pack_q_sr(x, inv, u[e]); }
+    };
+    template <int E> __device__ __forceinline__ Noise<E> noise(uint64_t j0) const
+    {
+        static_assert((E & (E - 1)) == 0, "the lane's elements share all index bits above log2 E");
+        const uint32_t lo = (uint32_t)j0 ^ (uint32_t)nonce;
+        const uint32_t hi = (uint32_t)(j0 >> 32) ^ (uint32_t)(nonce >> 32);
+        Noise<E> z;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t h = fmix32(fmix32(lo ^ (uint32_t)e) ^ hi);
+            z.u[e] = (float)(h >> 8) * 0x1p-24f;   // 24 bits: the conversion and the product are exact
+        }
+        return z;
+    }
+};
+
 // One wave packs payload block `blk`.
-template <class Ops>
+template <class Ops, class Round>
 DPWA_NO_PK_F32 __device__ __forceinline__ void pack_block(int64_t blk, const char *__restrict__ payload, int64_t nbytes,
-                                                          char *__restrict__ q_plane, float *__restrict__ scales)
+                                                          char *__restrict__ q_plane, float *__restrict__ scales,
+                                                          const Round &round)
 {
     constexpr int PER = Ops::PER;          // elements of a 16-byte item
     constexpr int QB = 4 * PER;            // q bytes of a lane
@@ -3102,6 +3164,8 @@ DPWA_NO_PK_F32 __device__ __forceinline__ void pack_block(int64_t blk, const cha
     u32x4 v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = span_load<u32x4, 0>(r, lane * kPackLane + j * 16);
+    // (the lane's first element, counted from the payload's first: 4 PER elements a lane)
+    const auto noise = round.template noise<4 * PER>((uint64_t)(blk * kStreamBlock + lane) * (4 * PER));
     const Ragged rg = ragged_at(off, nbytes);
     if (rg.lane == lane) {
         const uint16_t *p = reinterpret_cast<const uint16_t *>(payload + (nbytes & ~(int64_t)15));
@@ -3135,8 +3199,8 @@ DPWA_NO_PK_F32 __device__ __forceinline__ void pack_block(int64_t blk, const cha
     uint32_t q[QB / 4];
 #pragma unroll
     for (int d = 0; d < QB / 4; ++d) {
-        const uint32_t w = pack_q(x[4 * d], inv) | pack_q(x[4 * d + 1], inv) << 8 | pack_q(x[4 * d + 2], inv) << 16 |
-                           pack_q(x[4 * d + 3], inv) << 24;
+        const uint32_t w = noise.q(4 * d, x[4 * d], inv) | noise.q(4 * d + 1, x[4 * d + 1], inv) << 8 |
+                           noise.q(4 * d + 2, x[4 * d + 2], inv) << 16 | noise.q(4 * d + 3, x[4 * d + 3], inv) << 24;
         q[d] = normal ? w : 0u;
     }
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
@@ -3151,25 +3215,27 @@ DPWA_NO_PK_F32 __device__ __forceinline__ void pack_block(int64_t blk, const cha
     }
 }
 
-template <class Ops>
+template <class Ops, class Round>
 DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pack(const char *__restrict__ payload, int64_t nbytes,
-                                                       char *__restrict__ q_plane, float *__restrict__ scales)
+                                                       char *__restrict__ q_plane, float *__restrict__ scales,
+                                                       Round round)
 {
-    pack_block<Ops>((int64_t)blockIdx.x, payload, nbytes, q_plane, scales);
+    pack_block<Ops>((int64_t)blockIdx.x, payload, nbytes, q_plane, scales, round);
 }
 
 // k_pack behind the reuse guard of a publish whose image the average wrote: the guard's fix-up, if there was
 // one, left that image stale, and its verdict stays on the device.  Every wave returns at once unless the
 // verdict word carries this publish's generation; a hit repacks the whole payload, a capped grid striding over
 // the blocks as k_pull_unpack's, and a miss moves no payload byte.
-template <class Ops>
+template <class Ops, class Round>
 DPWA_NO_PK_F32 __global__ __launch_bounds__(kStreamBlock) void k_pack_if(const char *__restrict__ payload, int64_t nbytes,
                                                           char *__restrict__ q_plane, float *__restrict__ scales,
                                                           int64_t nblocks, const int32_t *__restrict__ dirty,
-                                                          int32_t gen)
+                                                          int32_t gen, Round round)
 {
     if (*dirty != gen) return;   // uniform
-    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) pack_block<Ops>(b, payload, nbytes, q_plane, scales);
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x)
+        pack_block<Ops>(b, payload, nbytes, q_plane, scales, round);
 }
 
 // The mirror image, shaped like k_pull: at most max_blocks one-wave workgroups stride over the blocks.
@@ -3235,28 +3301,40 @@ int64_t pack_image_bytes(int32_t dtype, int64_t n)
     return pack_scale_offset(dtype, n) + (pack_blocks(dtype, n) * kPackScales * 4 + 4095) / 4096 * 4096;
 }
 
+// A PackRounding as the policy object of the kernels above: f(RoundNearest{}) or f(RoundStochastic{nonce}).
+template <class F> static hipError_t with_round(const PackRounding &rounding, F &&f)
+{
+    return rounding.stochastic ? f(RoundStochastic{rounding.nonce}) : f(RoundNearest{});
+}
+
 hipError_t launch_pack(int32_t dtype, const void *payload, int64_t n, void *image, hipStream_t s,
-                       const LaunchTiming *timing)
+                       const LaunchTiming *timing, PackRounding rounding)
 {
     if (!is_float_dtype(dtype) || n < 0 || !payload || !image || !aligned16(payload, image)) return hipErrorInvalidValue;
     const int64_t blocks = pack_blocks(dtype, n);
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     return with_ops(dtype, [&](auto ops) {
-        return launch(k_pack<decltype(ops)>, dim3((uint32_t)blocks), dim3(kStreamBlock), s, timing, payload,
-                      n * (int64_t)dtype_size(dtype), image, (char *)image + pack_scale_offset(dtype, n));
+        return with_round(rounding, [&](auto round) {
+            return launch(k_pack<decltype(ops), decltype(round)>, dim3((uint32_t)blocks), dim3(kStreamBlock), s, timing,
+                          payload, n * (int64_t)dtype_size(dtype), image, (char *)image + pack_scale_offset(dtype, n),
+                          round);
+        });
     });
 }
 
 hipError_t launch_pack_if(int32_t dtype, const void *payload, int64_t n, void *image, const int32_t *dirty, int32_t gen,
-                          hipStream_t s, const LaunchTiming *timing)
+                          hipStream_t s, const LaunchTiming *timing, PackRounding rounding)
 {
     if (!is_float_dtype(dtype) || n < 0 || !payload || !image || !dirty || !aligned16(payload, image))
         return hipErrorInvalidValue;
     const int64_t blocks = pack_blocks(dtype, n);
     return with_ops(dtype, [&](auto ops) {
-        return launch(k_pack_if<decltype(ops)>, dim3((uint32_t)std::min<int64_t>(blocks, kPackIfBlocks)),
-                      dim3(kStreamBlock), s, timing, payload, n * (int64_t)dtype_size(dtype), image,
-                      (char *)image + pack_scale_offset(dtype, n), blocks, dirty, gen);
+        return with_round(rounding, [&](auto round) {
+            return launch(k_pack_if<decltype(ops), decltype(round)>,
+                          dim3((uint32_t)std::min<int64_t>(blocks, kPackIfBlocks)), dim3(kStreamBlock), s, timing,
+                          payload, n * (int64_t)dtype_size(dtype), image, (char *)image + pack_scale_offset(dtype, n),
+                          blocks, dirty, gen, round);
+        });
     });
 }
 
@@ -3394,10 +3472,16 @@ __device__ __forceinline__ uint32_t row_umax(uint32_t v)
 // crosses lanes by row_umax alone: no LDS memory, no ds_bpermute, no barrier.  The lane's q bytes go to q-plane
 // offset 64 PER span + PER lane (one coalesced 256- or 512-byte store per wave, where ImagePeer reads) and lane 0
 // of each row stores the group's scale (scales[4 span ..], 16 bytes per wave); both `sc1`, as the snapshot's
-// stores: a peer reads them next.  `item` is zeros in the lanes past the payload's end.
-template <class Ops>
+// stores: a peer reads them next.  `item` is zeros in the lanes past the payload's end.  `noise` is the
+// rounding policy's for the item's PER elements (emit_noise), taken by the caller behind its loads.
+template <int PER, class Round> __device__ __forceinline__ auto emit_noise(const Round &round, uint32_t span, int lane)
+{
+    return round.template noise<PER>(((uint64_t)span * kStreamBlock + (uint32_t)lane) * PER);
+}
+
+template <class Ops, class Noise>
 __device__ __forceinline__ void emit_item(u32x4 item, uint32_t span, int lane, char *__restrict__ q_out,
-                                          float *__restrict__ scales_out)
+                                          float *__restrict__ scales_out, const Noise &noise)
 {
     constexpr int PER = Ops::PER;
     float x[PER];
@@ -3418,8 +3502,8 @@ __device__ __forceinline__ void emit_item(u32x4 item, uint32_t span, int lane, c
     uint32_t q[PER / 4];
 #pragma unroll
     for (int d = 0; d < PER / 4; ++d) {
-        const uint32_t w = pack_q(x[4 * d], inv) | pack_q(x[4 * d + 1], inv) << 8 | pack_q(x[4 * d + 2], inv) << 16 |
-                           pack_q(x[4 * d + 3], inv) << 24;
+        const uint32_t w = noise.q(4 * d, x[4 * d], inv) | noise.q(4 * d + 1, x[4 * d + 1], inv) << 8 |
+                           noise.q(4 * d + 2, x[4 * d + 2], inv) << 16 | noise.q(4 * d + 3, x[4 * d + 3], inv) << 24;
         q[d] = normal ? w : 0u;
     }
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
@@ -3439,11 +3523,11 @@ __device__ __forceinline__ void emit_item(u32x4 item, uint32_t span, int lane, c
 // peer's item from `peer` (PayloadPeer / ImagePeer).  EMIT (with DUAL): the span also writes the image bytes of
 // what it stored into args.snap -- the averaged item, or in a no-op round the unchanged parameters -- so the
 // grid may reach past the payload (whole 4-KiB blocks): such spans have zero-range descriptors, touch neither
-// operand and emit q = 0 and scale = +0.0f.
-template <class Ops, bool DUAL, bool OOP, int POLICY, class Peer, bool EMIT>
+// operand and emit q = 0 and scale = +0.0f, whatever `round` is (a zero has no fraction to round).
+template <class Ops, bool DUAL, bool OOP, int POLICY, class Peer, bool EMIT, class Round>
 __device__ __forceinline__ void packed_span(typename Ops::V *__restrict__ param, const Peer &peer, int64_t n,
                                             const LerpArgs &args, char *__restrict__ q_out,
-                                            float *__restrict__ scales_out)
+                                            float *__restrict__ scales_out, const Round &round)
 {
     static_assert(!EMIT || DUAL, "the emitting forms are those that write a snapshot");
     using V = typename Ops::V;
@@ -3460,6 +3544,8 @@ __device__ __forceinline__ void packed_span(typename Ops::V *__restrict__ param,
     // issue this lane's loads before anything else
     const V p = span_load<V, P::param_load>(rp, lane_off);
     const auto raw = peer.template load<Ops>(blockIdx.x, lane, vbytes);
+    // EMIT: the rounding policy's noise for the item this lane will store, under the loads and the factor
+    [[maybe_unused]] const auto noise = emit_noise<EMIT ? PER : 1>(round, blockIdx.x, lane);
     const bool ragged = (nbytes & 15) && span_off + lane_off == vbytes;   // this lane owns the partial item
     [[maybe_unused]] S *const ps = reinterpret_cast<S *>(reinterpret_cast<char *>(param) + vbytes);
     [[maybe_unused]] S *const ss = reinterpret_cast<S *>(reinterpret_cast<char *>(args.snap) + vbytes);
@@ -3500,7 +3586,7 @@ __device__ __forceinline__ void packed_span(typename Ops::V *__restrict__ param,
                 }
         }
     }
-    if constexpr (EMIT) emit_item<Ops>(__builtin_bit_cast(u32x4, item), blockIdx.x, lane, q_out, scales_out);
+    if constexpr (EMIT) emit_item<Ops>(__builtin_bit_cast(u32x4, item), blockIdx.x, lane, q_out, scales_out, noise);
 }
 
 template <class Ops, bool DUAL, bool OOP, int POLICY, bool USCALE>
@@ -3510,7 +3596,7 @@ __global__ __launch_bounds__(kStreamBlock) void k_lerp_packed(typename Ops::V *_
                                                               LerpArgs args)
 {
     packed_span<Ops, DUAL, OOP, POLICY, ImagePeer<USCALE>, false>(param, ImagePeer<USCALE>{q_plane, scales}, n, args,
-                                                                  nullptr, nullptr);
+                                                                  nullptr, nullptr, RoundNearest{});
 }
 
 // The emitting form of the fused write-through average (include/dpwa_hip.h dpwa_average_pack): one-wave
@@ -3519,12 +3605,12 @@ __global__ __launch_bounds__(kStreamBlock) void k_lerp_packed(typename Ops::V *_
 // 3 + 0.52 for a 16-bit type) plus the peer operand, in one launch, where the average followed by k_pack moved
 // (3 + 1.27) n s in two.  There is no resident (OOP) form: resident parameters live in the slot and the step
 // that follows the average writes them there, so their image can only be taken at the publish.
-template <class Ops, int POLICY, class Peer>
+template <class Ops, int POLICY, class Peer, class Round>
 __global__ __launch_bounds__(kStreamBlock) void k_lerp_emit(typename Ops::V *__restrict__ param, Peer peer, int64_t n,
                                                             LerpArgs args, char *__restrict__ q_out,
-                                                            float *__restrict__ scales_out)
+                                                            float *__restrict__ scales_out, Round round)
 {
-    packed_span<Ops, true, false, POLICY, Peer, true>(param, peer, n, args, q_out, scales_out);
+    packed_span<Ops, true, false, POLICY, Peer, true>(param, peer, n, args, q_out, scales_out, round);
 }
 
 // How the wave gets its four scales (k_lerp_packed): the wave's one uniform load, or with
@@ -3585,7 +3671,7 @@ bool pack_fused()
 
 hipError_t launch_average_emit(int32_t dtype, void *param, int64_t n, const void *peer, const void *peer_image,
                                const FusedArgs &fa, void *snap, void *image_out, hipStream_t s,
-                               const LaunchTiming *timing)
+                               const LaunchTiming *timing, PackRounding rounding)
 {
     if (!is_float_dtype(dtype) || n < 0 || (!peer) == (!peer_image) || !param || !snap || !image_out ||
         snap == param || !aligned16(param, peer, peer_image) || !aligned16(snap, image_out))
@@ -3601,16 +3687,14 @@ hipError_t launch_average_emit(int32_t dtype, void *param, int64_t n, const void
     float *const scales_out = (float *)(q_out + scale_off);
     return with_ops(dtype, [&](auto ops) {
         using Ops = decltype(ops);
-        using V = typename Ops::V;
         const auto from = [&](auto src) {
             using Peer = decltype(src);
-            const auto run = [&](void (*kernel)(V *, Peer, int64_t, LerpArgs, char *, float *)) {
-                return launch(kernel, dim3((uint32_t)grid), dim3(kStreamBlock), s, timing, param, src, n, args, q_out,
-                              scales_out);
-            };
             // (the policies of launch_average_packed)
             return BySizePolicies::with(lerp_policy(nbytes), [&](auto policy) {
-                return run(k_lerp_emit<Ops, decltype(policy)::value, Peer>);
+                return with_round(rounding, [&](auto round) {
+                    return launch(k_lerp_emit<Ops, decltype(policy)::value, Peer, decltype(round)>, dim3((uint32_t)grid),
+                                  dim3(kStreamBlock), s, timing, param, src, n, args, q_out, scales_out, round);
+                });
             });
         };
         if (peer) return from(PayloadPeer{(const char *)peer});

@@ -287,11 +287,18 @@ hipError_t launch_release_system(hipStream_t s);
 //                 preceded by the system-scope acquire of launch_pull
 // Nothing is written behind the payload's last byte.  hipErrorInvalidValue, nothing queued: a dtype
 // that is no element type, n < 0, a null or not 16-B aligned pointer, max_blocks < 1.
+// How the three launches that write an image round (include/dpwa_hip.h "stochastic rounding"): to nearest,
+// the default, which launches the kernels there were before the choice existed, or stochastically with the
+// image's nonce, which launches their RoundStochastic instantiations.
+struct PackRounding {
+    bool stochastic = false;
+    uint64_t nonce = 0;
+};
 int64_t pack_blocks(int32_t dtype, int64_t n);
 int64_t pack_scale_offset(int32_t dtype, int64_t n);
 int64_t pack_image_bytes(int32_t dtype, int64_t n);
 hipError_t launch_pack(int32_t dtype, const void *payload, int64_t n, void *image, hipStream_t s,
-                       const LaunchTiming *timing = nullptr);
+                       const LaunchTiming *timing = nullptr, PackRounding rounding = {});
 hipError_t launch_pull_unpack(int32_t dtype, void *payload_out, int64_t n, const void *image, void *header_out,
                               const void *header, int max_blocks, bool remote, hipStream_t s,
                               const LaunchTiming *timing = nullptr);
@@ -314,11 +321,11 @@ hipError_t launch_average_packed(int32_t dtype, void *param, int64_t n, const vo
 // any pointer not 16-B aligned, more than 2^31 - 1 spans.
 hipError_t launch_average_emit(int32_t dtype, void *param, int64_t n, const void *peer, const void *peer_image,
                                const FusedArgs &fa, void *snap, void *image_out, hipStream_t s,
-                               const LaunchTiming *timing = nullptr);
+                               const LaunchTiming *timing = nullptr, PackRounding rounding = {});
 // launch_pack by a grid whose every wave returns at once unless *dirty == gen (device memory: the reuse
 // guard's verdict word and its generation of this publish).
 hipError_t launch_pack_if(int32_t dtype, const void *payload, int64_t n, void *image, const int32_t *dirty, int32_t gen,
-                          hipStream_t s, const LaunchTiming *timing = nullptr);
+                          hipStream_t s, const LaunchTiming *timing = nullptr, PackRounding rounding = {});
 // DPWA_PACK_FUSED: does a pack-enabled learner's write-through average emit the image (default)?
 bool pack_fused();
 

@@ -464,7 +464,9 @@ struct dpwa_learner {
     // average that wrote the slot, and pulled in place of the payload under DPWA_PULL_PACKED, see kernels.hip
     bool pack_on = false;
     uint64_t packs_by_publish = 0, packs_by_average = 0;   // images written by k_pack / by k_lerp_emit
-    bool pull_by_kernel = false;             // DPWA_PULL_PACKED_AVG with a block cap: the image moves by launch_pull
+    bool pack_stochastic = false;            // dpwa_learner_set_pack_rounding: every image of publish v is rounded
+    uint64_t pack_salt = 0;                  // ... stochastically with nonce salt ^ v (next_image_rounding)
+    bool pull_by_kernel = false;            // DPWA_PULL_PACKED_AVG with a block cap: the image moves by launch_pull
     int64_t pack_stride = 0;                 // bytes from image 0 to image 1
     DevMem pack_mem;                         // 2 images, IPC-exported
     std::unordered_map<int, const char *> pack_images;   // per peer: image 0 (IPC-mapped)
@@ -863,6 +865,14 @@ static int window_report(dpwa_learner *l)
                      "step", newly);
 }
 
+// How the image of the next publish (number version + 1) is rounded, whoever writes it: that publish's k_pack,
+// the k_pack_if behind its reuse guard, or the write-through average ahead of it, which all run before
+// `version` moves.  One nonce per publish, so the three give the same image of the same payload.
+static PackRounding next_image_rounding(const dpwa_learner *l)
+{
+    return PackRounding{l->pack_stochastic, l->pack_salt ^ (l->version + 1)};
+}
+
 static int publish_impl(dpwa_learner *l, const void *flat, double loss, const double *loss_dev, hipStream_t s,
                         bool reuse)
 {
@@ -916,11 +926,11 @@ static int publish_impl(dpwa_learner *l, const void *flat, double loss, const do
         // guard's fix-up can have left it stale, and its verdict is on the device: k_pack_if reads it there.
         char *const image = l->pack_mem.ptr + (size_t)k * (size_t)l->pack_stride;
         if (!(header_only && l->wt_image)) {
-            HIP_TRY(launch_pack(l->dtype, slot + kPayloadOff, l->n, image, s));
+            HIP_TRY(launch_pack(l->dtype, slot + kPayloadOff, l->n, image, s, nullptr, next_image_rounding(l)));
             l->packs_by_publish++;
         } else if (l->reuse_guard) {   // (never resident: average_prepare)
             HIP_TRY(launch_pack_if(l->dtype, slot + kPayloadOff, l->n, image, &l->ctl->guard_dirty,
-                                   (int32_t)(l->version + 1), s));
+                                   (int32_t)(l->version + 1), s, nullptr, next_image_rounding(l)));
         }
         if (l->exported) HIP_TRY(launch_release_system(s));
     }
@@ -1428,7 +1438,8 @@ static int average_launch(dpwa_learner *l, const AvgPlan &p, hipStream_t s)
         case AvgForm::packed:
         case AvgForm::contiguous:
             if (p.emit) {   // (that average, emitting: p.peer or p.image, whichever the form has)
-                HIP_TRY(launch_average_emit(l->dtype, p.flat, l->n, p.peer, p.image, p.fa, p.snap, p.emit, s, timing));
+                HIP_TRY(launch_average_emit(l->dtype, p.flat, l->n, p.peer, p.image, p.fa, p.snap, p.emit, s, timing,
+                                            next_image_rounding(l)));
             } else if (p.form == AvgForm::packed) {
                 HIP_TRY(launch_average_packed(l->dtype, p.flat, l->n, p.image, p.fa, p.snap, s, timing, p.oop));
             } else {
@@ -1971,6 +1982,19 @@ int dpwa_learner_pack_enable(dpwa_learner *l)
     l->pack_mem = std::move(m);
     l->pack_stride = stride;
     l->pack_on = true;
+    return DPWA_OK;
+}
+
+int dpwa_learner_set_pack_rounding(dpwa_learner *l, int mode, uint64_t salt)
+{
+    if (!l) return set_error(DPWA_ERR_ARG, "dpwa_learner_set_pack_rounding: NULL learner");
+    if (mode != 0 && mode != 1)
+        return set_error(DPWA_ERR_ARG, "dpwa_learner_set_pack_rounding: mode %d is neither 0 (nearest) nor 1 (stochastic)",
+                         mode);
+    if (!l->pack_on)
+        return set_error(DPWA_ERR_STATE, "dpwa_learner_set_pack_rounding: packed snapshots not enabled");
+    l->pack_stochastic = mode == 1;
+    l->pack_salt = salt;
     return DPWA_OK;
 }
 

@@ -1,5 +1,6 @@
 // pack.cpp -- packed snapshots without a learner: the stateless entry points of include/dpwa_hip.h
-// (dpwa_pack_bytes, dpwa_pack, dpwa_pack_if, dpwa_unpack, dpwa_average_packed, dpwa_average_pack).  A learner's
+// (dpwa_pack_bytes, dpwa_pack, dpwa_pack_if, dpwa_unpack, dpwa_average_packed, dpwa_average_pack, and the
+// stochastically rounding dpwa_pack_stochastic and dpwa_average_pack_stochastic).  A learner's
 // images, packed at a publish or by the average ahead of it and pulled in place of the payload
 // (DPWA_PULL_PACKED), are in learner.cpp, beside the slots they mirror.
 #include <hip/hip_runtime.h>
@@ -27,16 +28,30 @@ int dpwa_pack_bytes(int32_t dtype, int64_t n, int64_t *bytes)
     return DPWA_OK;
 }
 
+// dpwa_pack and dpwa_pack_stochastic: one set of refusals, one launcher, two rounding policies.
+static int pack_entry(const char *fn, int32_t dtype, const void *payload, int64_t n, void *image, PackRounding rounding,
+                      dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "%s: %s", fn, why);
+    if (!payload || !image || (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "%s: a NULL pointer, or one event without the other", fn);
+    if (!aligned16(payload, image))
+        return set_error(DPWA_ERR_ARG, "%s: the payload or the image is not 16-byte aligned (there is no unaligned form)", fn);
+    HIP_TRY(launch_pack(dtype, payload, n, image, (hipStream_t)stream, CallerTiming(start_event, stop_event), rounding));
+    return DPWA_OK;
+}
+
 int dpwa_pack(int32_t dtype, const void *payload, int64_t n, void *image, dpwa_stream_t stream, void *start_event,
               void *stop_event)
 {
-    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_pack: %s", why);
-    if (!payload || !image || (!start_event) != (!stop_event))
-        return set_error(DPWA_ERR_ARG, "dpwa_pack: a NULL pointer, or one event without the other");
-    if (!aligned16(payload, image))
-        return set_error(DPWA_ERR_ARG, "dpwa_pack: the payload or the image is not 16-byte aligned (there is no unaligned form)");
-    HIP_TRY(launch_pack(dtype, payload, n, image, (hipStream_t)stream, CallerTiming(start_event, stop_event)));
-    return DPWA_OK;
+    return pack_entry("dpwa_pack", dtype, payload, n, image, PackRounding{}, stream, start_event, stop_event);
+}
+
+int dpwa_pack_stochastic(int32_t dtype, const void *payload, int64_t n, void *image, uint64_t nonce,
+                         dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    return pack_entry("dpwa_pack_stochastic", dtype, payload, n, image, PackRounding{true, nonce}, stream, start_event,
+                      stop_event);
 }
 
 int dpwa_unpack(int32_t dtype, const void *image, int64_t n, void *payload_out, int max_blocks, dpwa_stream_t stream,
@@ -73,26 +88,44 @@ int dpwa_average_packed(int32_t dtype, void *param, const void *header, const vo
 
 // dpwa_average (peer_payload) or dpwa_average_packed (peer_image) writing through to snap_payload, and dpwa_pack of
 // that snapshot into image_out, in one launch (k_lerp_emit).
+static int average_pack_entry(const char *fn, int32_t dtype, void *param, const void *header, const void *peer_payload,
+                              const void *peer_image, int64_t n, const dpwa_interp *cfg, double *clock_dev, double loss,
+                              dpwa_coef *coef_dev, void *snap_payload, void *image_out, PackRounding rounding,
+                              dpwa_stream_t stream, void *start_event, void *stop_event)
+{
+    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "%s: %s", fn, why);
+    if (!cfg || !clock_dev || !coef_dev || !header || !param || !snap_payload || !image_out ||
+        (!start_event) != (!stop_event))
+        return set_error(DPWA_ERR_ARG, "%s: a NULL pointer, or one event without the other", fn);
+    if ((!peer_payload) == (!peer_image))
+        return set_error(DPWA_ERR_ARG, "%s: exactly one of peer_payload and peer_image", fn);
+    if (snap_payload == param) return set_error(DPWA_ERR_ARG, "%s: snap_payload is the parameters", fn);
+    if (int rc = check_method(cfg, fn)) return rc;
+    if (!aligned16(param, peer_payload, peer_image) || !aligned16(snap_payload, image_out))
+        return set_error(DPWA_ERR_ARG, "%s: the parameters, the peer's payload or image, the snapshot payload "
+                                       "or the image is not 16-byte aligned (there is no unaligned form)", fn);
+    const FusedArgs fa = stateless_args(cfg, clock_dev, header, loss, coef_dev);
+    HIP_TRY(launch_average_emit(dtype, param, n, peer_payload, peer_image, fa, snap_payload, image_out,
+                                (hipStream_t)stream, CallerTiming(start_event, stop_event), rounding));
+    return DPWA_OK;
+}
+
 int dpwa_average_pack(int32_t dtype, void *param, const void *header, const void *peer_payload, const void *peer_image,
                       int64_t n, const dpwa_interp *cfg, double *clock_dev, double loss, dpwa_coef *coef_dev,
                       void *snap_payload, void *image_out, dpwa_stream_t stream, void *start_event, void *stop_event)
 {
-    if (const char *why = pack_problem(dtype, n)) return set_error(DPWA_ERR_ARG, "dpwa_average_pack: %s", why);
-    if (!cfg || !clock_dev || !coef_dev || !header || !param || !snap_payload || !image_out ||
-        (!start_event) != (!stop_event))
-        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: a NULL pointer, or one event without the other");
-    if ((!peer_payload) == (!peer_image))
-        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: exactly one of peer_payload and peer_image");
-    if (snap_payload == param)
-        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: snap_payload is the parameters");
-    if (int rc = check_method(cfg, "dpwa_average_pack")) return rc;
-    if (!aligned16(param, peer_payload, peer_image) || !aligned16(snap_payload, image_out))
-        return set_error(DPWA_ERR_ARG, "dpwa_average_pack: the parameters, the peer's payload or image, the snapshot payload "
-                                       "or the image is not 16-byte aligned (there is no unaligned form)");
-    const FusedArgs fa = stateless_args(cfg, clock_dev, header, loss, coef_dev);
-    HIP_TRY(launch_average_emit(dtype, param, n, peer_payload, peer_image, fa, snap_payload, image_out,
-                                (hipStream_t)stream, CallerTiming(start_event, stop_event)));
-    return DPWA_OK;
+    return average_pack_entry("dpwa_average_pack", dtype, param, header, peer_payload, peer_image, n, cfg, clock_dev, loss,
+                              coef_dev, snap_payload, image_out, PackRounding{}, stream, start_event, stop_event);
+}
+
+int dpwa_average_pack_stochastic(int32_t dtype, void *param, const void *header, const void *peer_payload,
+                                 const void *peer_image, int64_t n, const dpwa_interp *cfg, double *clock_dev,
+                                 double loss, dpwa_coef *coef_dev, void *snap_payload, void *image_out,
+                                 dpwa_stream_t stream, void *start_event, void *stop_event, uint64_t nonce)
+{
+    return average_pack_entry("dpwa_average_pack_stochastic", dtype, param, header, peer_payload, peer_image, n, cfg,
+                              clock_dev, loss, coef_dev, snap_payload, image_out, PackRounding{true, nonce}, stream,
+                              start_event, stop_event);
 }
 
 // dpwa_pack behind a device-side condition (k_pack_if): the form a learner's reuse guard runs.

@@ -33,6 +33,10 @@ RELAY_PULLS = ("relay", "relay-avg")   # DistGroup's multi-link transports (dpwa
 # the packed pulls: 'packed' expands the image on arrival, 'packed-avg' leaves that to the averaging kernel; one
 # set of preconditions and refusals (the messages name 'packed' for both)
 PACKED_PULLS = ("packed", "packed-avg")
+PACK_ROUNDINGS = ("nearest", "stochastic")   # dpwa_learner_set_pack_rounding's modes, in order
+PACK_SALT = 0x9E3779B97F4A7C15               # times (node index + 1), mod 2^64: a node's rounding salt
+STOCHASTIC_UNPACKED = ("pack_rounding='stochastic' rounds the packed images this node publishes: create the "
+                       "connection with pull='packed' or 'packed-avg' (nothing is packed otherwise)")
 MIXED_PACKED = ("pull='packed' is not available for a model that mixes dtypes: the packed image holds one element "
                 "type (a segmented codec is not built); use 'kernel' or 'copy'")
 RELAY_PACKED = ("pull='packed' and the relay pulls do not combine (packed stripes for the relay are not built): a "
@@ -378,7 +382,8 @@ NonfiniteElements = collections.namedtuple("NonfiniteElements", "healed refused 
 
 class DpwaConnection:
     def __init__(self, name, config_file, seed=None, group=None, pull=None, layout=None, track_distance=False,
-                 parameter_ranges=None, distance_every=1, skip_nonfinite_peer=False, heal_nonfinite=False):
+                 parameter_ranges=None, distance_every=1, skip_nonfinite_peer=False, heal_nonfinite=False,
+                 pack_rounding="nearest"):
         """layout (extension): ``FlatParameters.layout`` when the flat buffer given to update_send
         is the segmented ``torch.uint8`` buffer of a model that mixes dtypes (dpwa_amd/flat.py);
         every peer must hold the same layout.
@@ -422,7 +427,23 @@ class DpwaConnection:
         ``update_wait_average_many`` a healing learner gets a launch of its own) and ``update_wait()``
         followed by ``average()``; the parameter buffer must be 16-byte aligned.  Optimizer state is
         not touched.  With ``skip_nonfinite_peer`` too, the pre-pass and its veto stay as they are.
-        Not available with ``pull='relay-avg'``."""
+        Not available with ``pull='relay-avg'``.
+
+        pack_rounding (extension; needs a packed pull at construction): how this node rounds the int8
+        images it publishes.  ``'nearest'`` (default) publishes every element below half a step of its
+        group as 0 in every round, so receivers shrink those weights round after round; ``'stochastic'``
+        rounds up with probability equal to the fraction (dpwa_hip.h "stochastic rounding"), so what
+        peers receive is the true value on average, at one step of error per element instead of half
+        and with no extra byte or launch.  The noise is a hash of (element index, nonce) with
+        nonce = salt ^ publish number and salt = (this node's index in the YAML's node list + 1) *
+        0x9E3779B97F4A7C15 mod 2^64: replicas round differently and a rerun reproduces its bits.
+        ``set_pull`` keeps the mode.  The image format is the same, so receivers need no knowledge of
+        the sender's mode and ranks may differ in it."""
+        if pack_rounding not in PACK_ROUNDINGS:
+            raise ValueError("pack_rounding must be 'nearest' or 'stochastic', got %r" % (pack_rounding,))
+        if pack_rounding == "stochastic" and (pull is None or pull.partition(":")[0] not in PACKED_PULLS):
+            raise ValueError(STOCHASTIC_UNPACKED)
+        self._pack_rounding = pack_rounding
         self.name = name
         self._layout = tuple(layout) if layout is not None else None
         if isinstance(track_distance, str) and track_distance != "per_parameter":
@@ -462,6 +483,7 @@ class DpwaConnection:
             node = Struct(**node)
             if node.name == name:
                 self.me = node
+                self._pack_salt = (i + 1) * PACK_SALT % 2 ** 64
             else:
                 self.peers += [node]
                 self._peer_node_index.append(i)
@@ -953,6 +975,9 @@ class DpwaConnection:
                 raise ValueError("the relay pull needs a DistGroup (one learner per rank)")
             self._group.relay_blocks = 1     # allocate + exchange the relay buffers in on_bind
         self._group.on_bind(self)
+        if self._pack_rounding == "stochastic":   # the images exist now; set_pull never touches the mode
+            _lib.call("dpwa_learner_set_pack_rounding", self._learner.handle, PACK_ROUNDINGS.index("stochastic"),
+                      ctypes.c_uint64(self._pack_salt))
         self.set_pull(self._pull)
         return self._learner
 

@@ -55,7 +55,9 @@ extern "C" {
  * dpwa_average_guarded, dpwa_average_guarded_mixed, dpwa_learner_set_heal, dpwa_learner_heal_record,
  * dpwa_node_set_heal.
  * Still 11, by additions only: the trimmed consensus (dpwa_consensus_record.reserved carries the trim) --
- * dpwa_consensus_trimmed, dpwa_consensus_trimmed_mixed, dpwa_learner_consensus_trimmed. */
+ * dpwa_consensus_trimmed, dpwa_consensus_trimmed_mixed, dpwa_learner_consensus_trimmed.
+ * Still 11, by additions only: stochastically rounded (unbiased) packed images -- dpwa_pack_stochastic,
+ * dpwa_average_pack_stochastic, dpwa_learner_set_pack_rounding. */
 #define DPWA_ABI_VERSION 11
 
 #define DPWA_OK 0
@@ -463,6 +465,48 @@ int dpwa_average_pack(int32_t dtype, void *param, const void *header, const void
                       void *snap_payload, void *image_out, dpwa_stream_t stream, void *start_event, void *stop_event);
 int dpwa_pack_if(int32_t dtype, const void *payload, int64_t n, void *image, const int32_t *dirty_dev, int32_t gen,
                  dpwa_stream_t stream, void *start_event, void *stop_event);
+/* Stochastic rounding (extension, opt-in per image): the codec above with an unbiased quantisation step.
+ * Rounding to nearest publishes every element with |x| < amax / 254 as 0, in every round and by every
+ * replica, so a receiver that averages with factor a shrinks those weights by (1 - a) a round, always the
+ * same way.  Here t = x * inv is rounded up with probability frac(t) instead, so what peers receive is x on
+ * average.  Groups, amax, the NaN-group rule, the < 0x1p-100f flush rule, scale, inv, the two planes,
+ * dpwa_pack_bytes and "back" are unchanged, so no receiver can tell, or needs to know, how an image was
+ * rounded.  Only q changes.  For the element at payload element index j (64 bits, counted from the payload's
+ * first element) of an image written with the 64-bit `nonce`, all fp32 operations separately rounded:
+ *   t    = x * inv                     (as above)
+ *   f    = floorf(t)                   (exact)
+ *   frac = t - f                       (one fp32 subtraction, in [0, 1]; exact but for -1 < t < 0, where 1 + t
+ *                                       rounds to nearest, by 2^-25 at most, and a t above -2^-25 gives 1.0f)
+ *   h    = fmix32(fmix32((uint32_t)j ^ (uint32_t)nonce) ^ (uint32_t)(j >> 32) ^ (uint32_t)(nonce >> 32))
+ *          fmix32(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16   (uint32_t)
+ *   u    = (float)(h >> 8) * 0x1p-24f  (exact: 24 bits, in [0, 1))
+ *   q    = clamp((int)f + (u < frac ? 1 : 0), -127, 127)
+ * The noise is a counter-based hash: no state, no stream of random numbers, and the same (payload, nonce)
+ * gives the same image on every device and in tests/test_pack_sr_host.py's numpy restatement.  What follows:
+ *   - an element with frac == 0 never moves (u < 0 is false): zeros, the padding behind the payload's end
+ *     among them, give q = 0 whatever u is, and +-amax stays +-127;
+ *   - P(up) = ceil(frac * 2^24) / 2^24 over the 2^24 values of u, frac to within 2^-24;
+ *   - q is f or f + 1 before the clamp, and the clamp only moves it towards t (t < -127 gives f = -128, t > 127
+ *     gives f + 1 = 128), so |q - t| < 1 where rounding to nearest has <= 0.5.  In units of the exact
+ *     amax / 127, with inv = 127 / amax (1 + e1), t = x inv (1 + e2), scale = amax / 127 (1 + e3) and the
+ *     product's own e4, every |e| <= 2^-24 and |q| <= 127:
+ *     x' - x = q (1 + e3)(1 + e4) - t / ((1 + e1)(1 + e2)), so
+ *     |x' - x| < 1 + 2 * 127 * 2^-24 + 127.001 * 2.001 * 2^-24 < 1 + 510 * 2^-24 < 1 + 2^-15:
+ *     |x' - x| < amax / 127 (1 + 2^-15) before a 16-bit type's own rounding, one step where the nearest
+ *     rounding's bound is half a step.
+ *   dpwa_pack_stochastic          dpwa_pack with this rule: same planes, same refusals.
+ *   dpwa_average_pack_stochastic  dpwa_average_pack with this rule (`nonce` is its last argument): param,
+ *                 snap_payload, *coef_dev and the clock end up exactly as dpwa_average_pack leaves them, and
+ *                 image_out byte for byte as dpwa_pack_stochastic(dtype, snap_payload, n, image_out, nonce) run
+ *                 afterwards would leave it, the no-op (ZeroDivision) round included.  Same refusals.
+ * Both launch instantiations of dpwa_pack's and dpwa_average_pack's kernels on a rounding policy; the
+ * nearest-rounding entries launch the code they launched before.  A learner: dpwa_learner_set_pack_rounding. */
+int dpwa_pack_stochastic(int32_t dtype, const void *payload, int64_t n, void *image, uint64_t nonce,
+                         dpwa_stream_t stream, void *start_event, void *stop_event);
+int dpwa_average_pack_stochastic(int32_t dtype, void *param, const void *header, const void *peer_payload,
+                                 const void *peer_image, int64_t n, const dpwa_interp *cfg, double *clock_dev,
+                                 double loss, dpwa_coef *coef_dev, void *snap_payload, void *image_out,
+                                 dpwa_stream_t stream, void *start_event, void *stop_event, uint64_t nonce);
 
 /* The per-parameter distance (extension, opt-in): the two sums above for every parameter tensor t of
  * the model, over that tensor's own elements only -- dist2_t = sum (double(q_i) - double(p_i))^2 and
@@ -912,8 +956,17 @@ int dpwa_learner_relay_phase2(dpwa_learner *l, const int32_t *picks_dev, int my_
  * its size, dpwa_pack_bytes(dtype, n); read-only, for tests and A/B runs.
  * pack_handle / pack_attach / pack_attach_fds export the images and map peer `peer_id`'s (whose slots are
  * IPC-attached already), as the relay buffer's calls do; fds come from export_fds with which = 2.
- * DPWA_ERR_ARG: a DPWA_MIXED learner, images of another n or dtype.  DPWA_ERR_STATE: enabled twice. */
+ * DPWA_ERR_ARG: a DPWA_MIXED learner, images of another n or dtype.  DPWA_ERR_STATE: enabled twice.
+ * set_pack_rounding: how this learner's images are rounded from now on -- mode 0 to nearest (the default: the
+ * launches and bits there were before the choice existed), mode 1 stochastically ("stochastic rounding"
+ * above).  In mode 1 every image the learner writes for publish number v has nonce = salt ^ v, whoever writes
+ * it: that publish's k_pack, the dpwa_pack_if behind its reuse guard, or the write-through average ahead of
+ * it, which writes the image of the next publish and so takes salt ^ (version + 1); DPWA_PACK_FUSED=0 and the
+ * fused path therefore give the same image.  Give replicas different salts, or they round alike.  Nothing is
+ * allocated, then or in a round; peers need not know.  DPWA_ERR_STATE before pack_enable, DPWA_ERR_ARG for
+ * any other mode. */
 int dpwa_learner_pack_enable(dpwa_learner *l);
+int dpwa_learner_set_pack_rounding(dpwa_learner *l, int mode, uint64_t salt);
 int dpwa_learner_pack_counts(dpwa_learner *l, uint64_t *by_publish, uint64_t *by_average);
 int dpwa_learner_pack_image(dpwa_learner *l, int k, const void **image, int64_t *bytes);
 int dpwa_learner_pack_handle(dpwa_learner *l, void *handle_out, int64_t handle_len);

@@ -19,6 +19,10 @@ sources ("payload": a contiguous peer, "image": a packed one) and both cold (a 1
 and cache-warm: "pair" dpwa_average / dpwa_average_packed + dpwa_pack of the snapshot, from the first dispatch's
 begin to the second's end (the two launches dpwa_average_pack replaces); "fused" dpwa_average_pack; "avg" the plain
 write-through average alone; "pack_if" dpwa_pack_if on a miss (what a guarded publish still launches).
+
+--sr measures what stochastic rounding costs (profiles/pack_sr_cost.json): dpwa_pack_stochastic against dpwa_pack
+and dpwa_average_pack_stochastic against dpwa_average_pack, for both peer sources, cache-warm, the four interleaved
+launch by launch on the same buffers.
 """
 import argparse
 import ctypes
@@ -225,6 +229,76 @@ def main_emit(args, lib, dev):
                            for k, v in e.items() if k != "numel"} for nm, e in out["sizes"].items()}))
 
 
+SR_FORMS = ("pack", "pack_sr", "emit", "emit_sr")
+
+
+def compare_sr(lib, code, tdtype, n, launches, warmup, dev, source):
+    """One repeat of the --sr forms, interleaved; compare_emit's buffers, the stochastic nonce changing every launch."""
+    esize = torch.empty((), dtype=tdtype).element_size()
+    off = _lib.SLOT_PAYLOAD_OFFSET // esize
+    param, snap = torch.empty(n, device=dev, dtype=tdtype).normal_(), torch.empty(n, device=dev, dtype=tdtype)
+    slot = torch.zeros(off + n, device=dev, dtype=tdtype)
+    slot[off:].normal_()
+    size = ctypes.c_int64()
+    _lib.call("dpwa_pack_bytes", code, n, ctypes.byref(size))
+    peer_image, out_image = (torch.zeros(size.value, dtype=torch.uint8, device=dev) for _ in range(2))
+    s = _lib.stream_handle(None)
+    _lib.call("dpwa_pack", code, slot[off:].data_ptr(), n, peer_image.data_ptr(), s, None, None)
+    clock = torch.zeros(2, dtype=torch.float64, device=dev)
+    coef = torch.zeros(32, dtype=torch.uint8, device=dev)
+    cfg = _lib.Interp(_lib.INTERP_CONSTANT, 0, 0.5, 0.0)
+    peer = (slot[off:].data_ptr(), None) if source == "payload" else (None, peer_image.data_ptr())
+    emit = (code, param.data_ptr(), slot.data_ptr(), *peer, n, ctypes.byref(cfg), clock.data_ptr(), 1.0, coef.data_ptr(),
+            snap.data_ptr(), out_image.data_ptr(), s)
+    total = warmup + launches
+    ev = {f: events(total) for f in SR_FORMS}
+    torch.cuda.synchronize()
+    for i in range(total):
+        k = i % len(SR_FORMS)
+        for form in SR_FORMS[k:] + SR_FORMS[:k]:
+            a0, a1 = (e.cuda_event for e in ev[form][i])
+            nonce = 0x9E3779B97F4A7C15 * (i + 1) % 2 ** 64
+            if form == "pack":
+                rc = lib.dpwa_pack(code, snap.data_ptr(), n, out_image.data_ptr(), s, a0, a1)
+            elif form == "pack_sr":
+                rc = lib.dpwa_pack_stochastic(code, snap.data_ptr(), n, out_image.data_ptr(), nonce, s, a0, a1)
+            elif form == "emit":
+                rc = lib.dpwa_average_pack(*emit, a0, a1)
+            else:
+                rc = lib.dpwa_average_pack_stochastic(*emit, a0, a1, nonce)
+            if rc:
+                raise _lib.DpwaError(form, rc, lib.dpwa_last_error().decode())
+    torch.cuda.synchronize()
+    return {f: [1e3 * a.elapsed_time(b) for a, b in pairs[warmup:]] for f, pairs in ev.items()}
+
+
+def main_sr(args, lib, dev):
+    out = {"what": "stochastic rounding against nearest: pack = dpwa_pack, pack_sr = dpwa_pack_stochastic, emit = "
+                   "dpwa_average_pack, emit_sr = dpwa_average_pack_stochastic (write-through, peer from a payload or "
+                   "from an image); interleaved launch by launch on the same local buffers, Infinity-Cache warm from "
+                   "the launch before; dispatch begin/end events; no link is measured",
+           "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "launches": args.launches,
+           "repeats": args.repeats, "sizes": {}}
+    for name, code, tdtype, n in SIZES:
+        entry = {"numel": n}
+        for source in ("payload", "image"):
+            reps = []
+            for _ in range(args.repeats):
+                r = {k: stats(v) for k, v in compare_sr(lib, code, tdtype, n, args.launches, args.warmup, dev, source).items()}
+                for f in ("pack", "emit"):
+                    r[f + "_sr_over_" + f] = round(r[f + "_sr"]["median_us"] / r[f]["median_us"], 3)
+                reps.append(r)
+                torch.cuda.empty_cache()
+            entry["peer_" + source] = reps
+        out["sizes"][name] = entry
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({nm: {k: [{f: r[f]["median_us"] for f in SR_FORMS} for r in v] for k, v in e.items() if k != "numel"}
+                      for nm, e in out["sizes"].items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=300)
@@ -234,11 +308,14 @@ def main():
     ap.add_argument("--out", default="pack_cost.json")
     ap.add_argument("--avg", action="store_true", help="measure dpwa_average_packed against what it replaces")
     ap.add_argument("--emit", action="store_true", help="measure dpwa_average_pack against what it replaces")
+    ap.add_argument("--sr", action="store_true", help="measure the stochastically rounding entries against the nearest")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pack_cost.py needs a GPU")
     dev = torch.device("cuda", 0)
     lib = _lib.load()
+    if args.sr:
+        return main_sr(args, lib, dev)
     if args.avg:
         return main_avg(args, lib, dev)
     if args.emit:
